@@ -449,6 +449,23 @@ class Timer:
         return {"min": 1e3 * self.reduce(mine, torch.distributed.ReduceOp.MIN) / steps, "max": 1e3 * self.reduce(mine) / steps}
 
 
+def returned_records(st_):
+    """Host copy of the scene records st_'s last step returned to its caller (gathered: every rank's scenes, global scene order)."""
+    return st_.pipe.results_to_numpy(st_.all_records)
+
+
+def dump_outputs(d, rec, workload):
+    """--dump-outputs DIR: one DIR/<field>.npy per field of the scene records (float32 fields as float32, the others as float64,
+    exact for these integers); the record's padding is not written, except --workload ensemble's pick (pad_[:, 0])."""
+    os.makedirs(d, exist_ok=True)
+    for name in rec.dtype.names:
+        if name != "pad_":
+            a = rec[name]
+            np.save(os.path.join(d, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
+    if workload == "ensemble":
+        np.save(os.path.join(d, "pick.npy"), rec["pad_"][:, 0].astype(np.float64))
+
+
 def sampled_steps(k, slots):
     """Which of k steps record their stage boundaries, and into which prepared event slot: up to `slots`, spread evenly."""
     n_s = min(k, slots)
@@ -478,6 +495,7 @@ def run_other_workload(args, rank, world, dev, backend, timer, pool, tel):
     sampled = sampled_steps(args.steps, Step.EVENT_SLOTS)
     with tel.window("single_stream_loop", torch.cuda.synchronize):
         dt1, mine, evs = timer.loop(args.steps, lambda i: step.run(timed=sampled.get(i)))      # single stream: stage events
+    outputs = returned_records(step)
     step.two = None
     dt = dt1
     if args.workload == "ensemble" and not args.single_stream:
@@ -495,6 +513,7 @@ def run_other_workload(args, rank, world, dev, backend, timer, pool, tel):
             step.run_two_streams(streams)
         with tel.window("two_stream_loop", torch.cuda.synchronize):
             dt, mine, _ = timer.loop(args.steps, lambda i: step.run_two_streams(streams))
+        outputs = returned_records(step)
         step.ops.mlp_reserve_cus(0)
         same = bool(torch.equal(step.pipe.selected, ref_sel) and torch.equal(step.pipe.result_slots, ref_slots))
         step.two = {"streams": 2, "mlp_reserved_cus": args.mlp_reserve_cus, "records_identical_to_single_stream": same, "value_single_stream": step.B * world * args.steps / dt1,
@@ -503,6 +522,8 @@ def run_other_workload(args, rank, world, dev, backend, timer, pool, tel):
                             "for the DINO scale; per-stage times come from the single-stream loop of the same run"}
     rank_ms = timer.per_rank(mine, args.steps)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs, args.workload)
         power = tel.finish()
         if args.workload == "ensemble" and oracle_out.get("ensemble"):
             both = [step.pipe.results_to_numpy(step.pipe.result_slots[m]) for m in (0, 1)]
@@ -719,6 +740,7 @@ def main():
             torch.cuda.synchronize()
             with tel.window("two_stream_loop"):
                 dt, mine, evs, ends = timed_loop(args.steps, pair=mode)
+            outputs = returned_records(mode.states[(mode.count - 1) % len(mode.states)])     # the Step of the last timed step
         pair = (all_steps, streams)
         intervals = completion_intervals(ends, group=len(streams))
         same = bool(all(torch.equal(s_.pipe.results, r_) for s_, r_ in zip(pair[0], refs)))
@@ -756,6 +778,7 @@ def main():
     else:
         with tel.window("single_stream_loop"):
             dt, mine, evs, ends = timed_loop(args.steps)
+        outputs = returned_records(step)
         intervals = completion_intervals(ends)
         intervals_single = None
         evs_single = evs
@@ -883,6 +906,8 @@ def main():
 
     failed = False
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs, args.workload)
         cpu = None
         if args.cpu_scenes > 0 and world == 1:     # CPU baseline + whole-batch agreement: rank 0 at N=1 only
             agree = None

@@ -38,7 +38,7 @@ def use_tuned_gemms():
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=_positive, default=100, help="timed steps of the headline loop (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scenes-per-gpu", type=int, default=64)
     ap.add_argument("--points", type=int, default=4096)
@@ -109,7 +109,17 @@ def parse(argv=None):
                          "inputs.  The default run also times the descriptor stage on voxel2mm clouds (value_voxel_density)")
     ap.add_argument("--no-voxel-density", action="store_true",
                     help="skip the extra timed loop of the default run on voxel2mm clouds (value_voxel_density)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the scene records the headline loop's last step returned (every rank's "
+                         "scenes, global scene order) as DIR/<field>.npy, float64 or float32, one file per record field")
     return ap.parse_args(argv)
+
+
+def _positive(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError("must be >= 1, got %d" % v)
+    return v
 
 
 def cdist_forced():

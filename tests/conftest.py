@@ -29,12 +29,14 @@ def _free_port():
 def _bench_jobs():
     """The bench.py runs tests/test_multi_rank_gpu.py reads, in the order they run (each alone on the GPU):
     * counters: the counter passes of a default run -- bench.py starts rocprofv3 children of itself before it touches the GPU;
-    * one_rank_16 / eight_ranks: the 8-rank launch path without 8 GPUs -- `bench.py --gpus 8 --scenes-per-gpu 2` starts eight fresh
-      ranks that share GPU 0 over gloo (port allocation, LOCAL_RANK % visible GPUs, per-rank core slices and TunableOp directories);
-      its 16 gathered records must equal, in global scene order, those of one rank holding all 16 scenes;
+    * one_rank_16 / four_ranks: the multi-rank launch path without more GPUs -- `bench.py --gpus 4 --scenes-per-gpu 4` starts four
+      fresh ranks that share GPU 0 over gloo (port allocation, LOCAL_RANK % visible GPUs, per-rank core slices and TunableOp
+      directories); its 16 gathered records must equal, in global scene order, those of one rank holding all 16 scenes.  Four, not
+      eight: a shared GPU host admits at most six processes with the device open at once, and rank 0's parent launcher and
+      telemetry child come on top of the ranks;
     * rccl_one_rank: `bench.py --gpus 1` with CPPF_DIST_FORCE_COLLECTIVE=1: init_process_group("nccl", device_id=...) and the path's
       all_gather (plus the bench's barrier and all_reduce) really run through RCCL, in a one-rank group;
-    * one_rank_512 / eight_ranks_64: the same at the real run's geometry -- eight ranks of 64 scenes against one rank of 512;
+    * one_rank_512 / four_ranks_128: the same at the real run's batch (512 scenes) -- four ranks of 128 scenes against one rank of 512;
     * refuse_two_gpus: plain `python bench.py --gpus 2` over RCCL on this one-GPU box must fail loudly;
     * two_ranks: plain `python bench.py --gpus 2` (no launcher environment): bench.py starts its two ranks itself; they share GPU 0,
       so the backend is gloo (CPPF_BENCH_BACKEND, the dry-run switch: one GPU cannot host two RCCL ranks)."""
@@ -52,10 +54,10 @@ def _bench_jobs():
     return [agreement, job("counters", ["--gpus", "1"] + one, counters=True),
             job("one_rank_16", ["--gpus", "1"] + one, scenes=16),
             # (no --no-counters here: the ranks of a multi-rank run must decline the counter passes by themselves)
-            job("eight_ranks", ["--gpus", "8"] + one, scenes=2, counters=True, CPPF_BENCH_BACKEND="gloo"),
-            # the same comparison at the batch geometry of the real 8-GPU run (64 scenes per rank = 512 scenes): round 6
+            job("four_ranks", ["--gpus", "4"] + one, scenes=4, counters=True, CPPF_BENCH_BACKEND="gloo"),
+            # the same comparison at the batch of the real 8-GPU run (512 scenes; there 64 per rank)
             job("one_rank_512", ["--gpus", "1"] + one, scenes=512),
-            job("eight_ranks_64", ["--gpus", "8"] + one, scenes=64, CPPF_BENCH_BACKEND="gloo"),
+            job("four_ranks_128", ["--gpus", "4"] + one, scenes=128, CPPF_BENCH_BACKEND="gloo"),
             job("rccl_one_rank", ["--gpus", "1"], CPPF_DIST_FORCE_COLLECTIVE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port())),
             job("refuse_two_gpus", ["--gpus", "2"]),
             job("two_ranks", ["--gpus", "2"], CPPF_BENCH_BACKEND="gloo")]

@@ -223,43 +223,44 @@ def test_bench_measures_its_counters_in_the_run():
     assert all(b is not None and 0.0 < b <= 1.0 for b in busy), r["mfma_busy_per_launch"]
 
 
-def test_bench_eight_ranks_dry_run_equals_one_rank():
-    """SURVEY 8e on the hardware there is: eight fresh rank processes (bench.py's own launcher) sharing GPU 0 over gloo, two
-    scenes each; the 16 records gathered in global scene order are byte-identical to one rank's 16 (records_sha256)."""
-    rc8, out8, err8 = _job("eight_ranks")
-    assert rc8 == 0, err8[-3000:]
+def test_bench_four_ranks_dry_run_equals_one_rank():
+    """SURVEY 8e on the hardware there is: four fresh rank processes (bench.py's own launcher) sharing GPU 0 over gloo, four
+    scenes each; the 16 records gathered in global scene order are byte-identical to one rank's 16 (records_sha256).  (Four ranks:
+    a shared GPU host admits at most six processes with the device open, see tests/conftest.py.)"""
+    rc4, out4, err4 = _job("four_ranks")
+    assert rc4 == 0, err4[-3000:]
     rc1, out1, err1 = _job("one_rank_16")
     assert rc1 == 0, err1[-3000:]
-    j8 = json.loads([ln for ln in out8.splitlines() if ln.startswith("{")][0])
+    j4 = json.loads([ln for ln in out4.splitlines() if ln.startswith("{")][0])
     j1 = json.loads([ln for ln in out1.splitlines() if ln.startswith("{")][0])
-    assert j8["n_gpus"] == 8 and j8["records_gathered"] == 16 and j8["collective"]["world"] == 8 and j8["config"]["scenes_per_gpu"] == 2
+    assert j4["n_gpus"] == 4 and j4["records_gathered"] == 16 and j4["collective"]["world"] == 4 and j4["config"]["scenes_per_gpu"] == 4
     assert j1["n_gpus"] == 1 and j1["records_gathered"] == 16
-    assert j8["records_sha256"] == j1["records_sha256"]
-    assert j8["pose_5deg5cm_vs_gt"] == 1.0 and j8["ok"] and j1["ok"]
+    assert j4["records_sha256"] == j1["records_sha256"]
+    assert j4["pose_5deg5cm_vs_gt"] == 1.0 and j4["ok"] and j1["ok"]
     # the line of a multi-rank run diagnoses itself: backend, world, op, per-rank step times, the records' hash
-    c8 = j8["collective"]
-    assert c8["backend"] == "gloo" and c8["op"] == "all_gather" and c8["records_sha256"] == j8["records_sha256"]
-    assert 0 < c8["ms_per_step_per_rank"]["min"] <= c8["ms_per_step_per_rank"]["max"] == pytest.approx(j8["ms_per_step"], rel=1e-6)
+    c4 = j4["collective"]
+    assert c4["backend"] == "gloo" and c4["op"] == "all_gather" and c4["records_sha256"] == j4["records_sha256"]
+    assert 0 < c4["ms_per_step_per_rank"]["min"] <= c4["ms_per_step_per_rank"]["max"] == pytest.approx(j4["ms_per_step"], rel=1e-6)
     # no rank of a multi-rank run starts profiler children (bench.py guards on world == 1), and says so
-    assert j8["counter_children_started"] == 0 and j8["roofline"]["traffic"] is None
-    assert "one rank only" in j8["roofline"]["hbm"]["traffic_source"]
-    # rank 0 of eight was pinned to its run of the host cores (an eighth of them)
-    cores = j8["host_cores_of_rank0"]
+    assert j4["counter_children_started"] == 0 and j4["roofline"]["traffic"] is None
+    assert "one rank only" in j4["roofline"]["hbm"]["traffic_source"]
+    # rank 0 of four was pinned to its run of the host cores (a quarter of them)
+    cores = j4["host_cores_of_rank0"]
     assert cores is None or (cores["cores"] >= 1 and cores["first"] <= cores["last"])
 
 
-def test_bench_eight_ranks_of_64_scenes_equal_one_rank_of_512():
-    """The dry run at the geometry of the real 8-GPU job (BASELINE configs[3]: 512 scenes, 64 per rank): eight rank processes of 64
-    scenes each sharing GPU 0 over gloo gather the 512 records one rank computes alone, byte for byte (records_sha256)."""
-    rc8, out8, err8 = _job("eight_ranks_64")
-    assert rc8 == 0, err8[-3000:]
+def test_bench_four_ranks_of_128_scenes_equal_one_rank_of_512():
+    """The dry run at the batch of the real 8-GPU job (BASELINE configs[3]: 512 scenes): four rank processes of 128 scenes each
+    sharing GPU 0 over gloo gather the 512 records one rank computes alone, byte for byte (records_sha256)."""
+    rc4, out4, err4 = _job("four_ranks_128")
+    assert rc4 == 0, err4[-3000:]
     rc1, out1, err1 = _job("one_rank_512")
     assert rc1 == 0, err1[-3000:]
-    j8 = json.loads([ln for ln in out8.splitlines() if ln.startswith("{")][0])
+    j4 = json.loads([ln for ln in out4.splitlines() if ln.startswith("{")][0])
     j1 = json.loads([ln for ln in out1.splitlines() if ln.startswith("{")][0])
-    assert j8["n_gpus"] == 8 and j8["records_gathered"] == 512 and j8["config"]["scenes_per_gpu"] == 64 and j8["collective"]["bytes_per_rank"] == 64 * 160
+    assert j4["n_gpus"] == 4 and j4["records_gathered"] == 512 and j4["config"]["scenes_per_gpu"] == 128 and j4["collective"]["bytes_per_rank"] == 128 * 160
     assert j1["n_gpus"] == 1 and j1["records_gathered"] == 512
-    assert j8["records_sha256"] == j1["records_sha256"] and j8["ok"] and j1["ok"]
+    assert j4["records_sha256"] == j1["records_sha256"] and j4["ok"] and j1["ok"]
 
 
 def test_bench_gathers_through_rccl_in_a_one_rank_group():
