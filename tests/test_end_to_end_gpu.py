@@ -25,26 +25,33 @@ sys.path.insert(0, ROOT)
 from oracle import pipeline_oracle as PO      # noqa: E402  (the checker)
 
 
-def _args(scenes):
-    return types.SimpleNamespace(scenes_per_gpu=scenes, points=4096, tuples=20000, rots=180, seed=0, vote_mode=0, eager_scale_head=False)
+def _args(scenes, tuples=20000):
+    return types.SimpleNamespace(scenes_per_gpu=scenes, points=4096, tuples=tuples, rots=180, seed=0, vote_mode=0, eager_scale_head=False)
 
 
 @pytest.mark.parametrize("cloud,scenes", [("synthetic", 2), ("voxel2mm", 1)])
 def test_full_size_step_equals_the_whole_scene_oracle(cloud, scenes):
     from cppf2_amd.benchlib import workloads as W
-    from cppf2_amd.metrics import rt_degree_cm
     dev = torch.device("cuda")
     st = W.Step(_args(scenes), 0, 1, dev, cloud=cloud)
     st.run()
     torch.cuda.synchronize()
+    check_step_against_the_oracle(st, scenes)
+
+
+def check_step_against_the_oracle(st, scenes, shot_threads=1):
+    """The bars of this file for every scene of a finished Step; returns the records and the oracle's outputs."""
+    from cppf2_amd.benchlib import workloads as W
+    from cppf2_amd.metrics import rt_degree_cm
     rec = st.pipe.results_to_numpy()
     bins = st.pipe.bins.reshape(scenes, st.T, 6).cpu().numpy()
     prior = st.prior_dense.reshape(scenes, st.T, 6, 32).cpu().numpy()          # the teacher prior's values, as the kernels add them
     weights = {k: v.detach().cpu().numpy() for k, v in st.model.state_dict().items()}
     trig = (st.pipe.cs.cpu().numpy(), st.pipe.sn.cpu().numpy())
+    outs = []
     for b in range(scenes):
         o = PO.run_scene_full(weights, st.scenes[b]["pc"], 0, st.scene0 + b, st.T, res=W.Cfg.res, num_rots=180, trig=trig,
-                              prior_fn=lambda idx, b=b: prior[b], topk_impl="c")
+                              prior_fn=lambda idx, b=b: prior[b], topk_impl="c", shot_threads=shot_threads)
         assert int(rec["argmax"][b]) == o["argmax"]
         assert int(rec["up_idx"][b]) == o["up_idx"] and int(rec["right_idx"][b]) == o["right_idx"]
         assert int(rec["kept"][b]) == int(o["pairs_mask"].sum())
@@ -58,3 +65,5 @@ def test_full_size_step_equals_the_whole_scene_oracle(cloud, scenes):
         assert int((bins[b] != o["bins"]).sum()) <= 6, "bin draws apart from the oracle's: more than the MLP's arithmetic explains"
         # the scene really was solved (teacher prior): the centre is the synthetic ground truth's
         assert np.linalg.norm(rec["t"][b] - st.scenes[b]["t"]) < 5e-3
+        outs.append(o)
+    return rec, outs

@@ -28,6 +28,21 @@ def _perturbed(R_gt, t_gt, deg=3.0, shift=0.01):
     return Rz @ R_gt, t_gt + np.array([shift, -shift, shift])
 
 
+RF_CACHED_PAIRS = 2048      # cppf_refine.hip: RF_CACHE x RF_THREADS = 4096 loss elements (2 per kept pair) live in registers
+
+
+def _kept_problem(kept, N=3000, tail_shift=0.01):
+    """A refinement problem of `kept` kept pairs (seeded by `kept`) for the kernel-level tests: pairs [0, kept) are the kept
+    ones, and the targets of those past the first RF_CACHED_PAIRS are offset by tail_shift (object frame, all three axes), so the
+    pairs the kernel re-reads from memory on every step pull the optimum away from where the register-held ones put it; kept // 4
+    more pairs follow that are not kept, with targets 5 cm off.  Returns (pc, idx, tgt, R0, t0), (R0, t0) the starting pose."""
+    pc, idx, tgt, R_gt, t_gt = _problem(kept, N=N, Tf=kept + kept // 4)
+    tgt[RF_CACHED_PAIRS:] += np.float32(tail_shift)
+    tgt[kept:] += np.float32(0.05)
+    R0, t0 = _perturbed(R_gt, t_gt, deg=2.0, shift=0.004)
+    return pc, idx, tgt, R0, t0
+
+
 def test_so3_matrix_is_the_rotation_for_unit_quaternions_and_lietorch_formula_otherwise():
     q = np.array([0.1, -0.2, 0.3, 0.9], np.float32)
     qn = q / np.linalg.norm(q)
@@ -76,15 +91,28 @@ def test_oracle_refinement_descends_from_a_perturbed_pose(y_only):
     assert np.allclose(zero[0], t0.astype(np.float32)) and np.allclose(zero[1], R0.astype(np.float32))
 
 
+@pytest.mark.parametrize("y_only", [False, True])
+def test_refinement_bars_see_the_pairs_past_the_register_cache(y_only):
+    """The GPU refinement tests compare with the oracle at 2e-4 (t) / 2e-3 (R).  On the 5 000-pair problem they use, a kernel
+    that refined with only the RF_CACHED_PAIRS pairs it holds in registers would land more than 10x those bars away."""
+    pc, idx, tgt, R0, t0 = _kept_problem(5000)
+    t_all, R_all = O.refine_pose(pc, idx[:5000], tgt[:5000], t0, R0, y_only)
+    t_head, R_head = O.refine_pose(pc, idx[:RF_CACHED_PAIRS], tgt[:RF_CACHED_PAIRS], t0, R0, y_only)
+    assert np.abs(t_all - t_head).max() > 10 * 2e-4, (t_all, t_head)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("y_only", [True, False])
-def test_hip_refinement_matches_the_oracle(y_only):
+@pytest.mark.parametrize("y_only,T", [pytest.param(y, 12000, id=str(y)) for y in (True, False)] +      # (the 12 000 cases keep their ids)
+                         [pytest.param(y, 50000, id="%s-50000" % y) for y in (True, False)])
+def test_hip_refinement_matches_the_oracle(y_only, T):
+    """T = 12 000 keeps ~1 200 pairs (every loss element in registers); T = 50 000, the reference's default num_pairs, keeps
+    ~5 000, so the kernel re-reads the pairs past RF_CACHED_PAIRS from memory on every step."""
     if not torch.cuda.is_available():
         pytest.skip("no HIP device")
     from cppf2_amd import ops, synth
     from cppf2_amd.pipeline import VotingPipeline
     dev = torch.device("cuda")
-    B, N, T = 3, 2048, 12000
+    B, N = 3, 2048
     scs = [synth.make_scene(6, b, N) for b in range(B)]
     pts = torch.from_numpy(np.concatenate([s["pc"] for s in scs])).to(dev)
     idx = ops.sample_tuples(N, T, 5, 6, tuple(range(B)))
@@ -96,6 +124,8 @@ def test_hip_refinement_matches_the_oracle(y_only):
     pipe.refine(pts, idx, y_only)
     after = pipe.results_to_numpy()
     kept_tuple, kept_count = pipe.kept_tuple.cpu().numpy(), pipe.kept_count.cpu().numpy()
+    # which side of the register cache the scenes' loss elements (2 per kept pair) fall on
+    assert np.all(kept_count < RF_CACHED_PAIRS) if T == 12000 else np.all(kept_count > RF_CACHED_PAIRS)
     scaled, idx_h = pipe.scaled.cpu().numpy(), idx.cpu().numpy()
     for b in range(B):
         rows = b * T + kept_tuple[b * T: b * T + kept_count[b]]
