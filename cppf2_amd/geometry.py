@@ -13,3 +13,26 @@ def rot_err_deg(R_est, R_gt, symmetric_up=False, up_axis=1):
     else:
         c = (np.trace(R_est.T @ R_gt) - 1.0) / 2.0
     return float(np.degrees(np.arccos(np.clip(c, -1.0, 1.0))))
+
+
+def map_sym(rot, axis):
+    """utils/util.py:71-81 (dataset.py:4 imports it): removes the rotation about `axis` (0, 1, 2) that a rotationally
+    symmetric object cannot show -- left-multiplies rot by the rotation about that axis which zeroes the angle
+    atan2(m10 - m01, m00 + m11) of rot's 2x2 block in the other two axes.  The training items of the symmetric categories
+    (bottle, bowl, can) pass rot.T through it (dataset.py:260-261)."""
+    rot = np.asarray(rot, dtype=np.float64)
+    o = [a for a in (0, 1, 2) if a != axis]
+    m = rot[np.ix_(o, o)]
+    alpha = np.arctan2(m[1, 0] - m[0, 1], m[0, 0] + m[1, 1])
+    c, s = np.cos(alpha), np.sin(alpha)
+    S = np.eye(3)
+    S[np.ix_(o, o)] = np.array([[c, s], [-s, c]])
+    return S @ rot
+
+
+def map_sym_discrete(rot, sym_rots):
+    """utils/util.py:66-68: sym.T @ rot for the symmetry rotation `sym` of `sym_rots` closest to rot (Frobenius norm of
+    sym.T @ rot - I; the first one on ties)."""
+    rot = np.asarray(rot, dtype=np.float64)
+    dist = [np.linalg.norm(np.asarray(s).T @ rot - np.eye(3)) for s in sym_rots]
+    return np.asarray(sym_rots[int(np.argmin(dist))]).T @ rot

@@ -1,16 +1,20 @@
 """`dataset` of the reference for the names its entry points import from it (eval.py:7,19,22: id2category, resize_crop, DINOV2;
 train_dino.py:9,165 and train_shot.py:9: ShapeNetExportDataset, id2category, generate_target_pairs, rotx/roty/rotz), so those
-lines resolve unchanged with this repository first on sys.path.  The ShapeNet / BlenderProc rendering datasets
-(dataset.py:140-336, 367-412) are outside the voting path; ShapeNetExportDataset -- the reader of the reference's
+lines resolve unchanged with this repository first on sys.path.  ShapeNetExportDataset -- the reader of the reference's
 EXPORTED training items, the only dataset class its trainers construct (train_shot.py:148, train_dino.py:159) -- is a thin adapter
-over cppf2_amd.training.ExportedItems.
+over cppf2_amd.training.ExportedItems.  ShapeNetDirectDataset / dump_data (dataset.py:177-319, 371-413) render ShapeNet models with
+the library's rasterizer (cppf2_amd.render) instead of pyrender; their items carry no `rgb` and the dumped files no `desc`.
+The BlenderProc datasets are not here.
 """
+import os
+
 import numpy as np
 import torch
 
 from cppf2_amd.ops import generate_target_pairs  # noqa: F401  dataset.py:118-135 -> cppf_generate_target_pairs (float64 on the GPU)
 from cppf2_amd.ops import interpolate_features   # noqa: F401  dataset.py:40-59   -> cppf_interpolate_features
 from utils.util import downsample                # noqa: F401  dataset.py:107-115 is utils/util.py:39-46 again
+from utils.util import map_sym, map_sym_discrete  # noqa: F401  dataset.py:4
 
 category2id = {"bottle": 1, "bowl": 2, "camera": 3, "can": 4, "laptop": 5, "mug": 6}          # dataset.py:29-37
 id2category = {v: k for k, v in category2id.items()}
@@ -42,6 +46,88 @@ class ShapeNetExportDataset(torch.utils.data.Dataset):
 
     def __len__(self):
         return len(self.items)
+
+
+shapenet_obj_scales = {                            # dataset.py:165-172: object size range (m) per ShapeNet synset
+    "02946921": [0.128, 0.18],
+    "02876657": [0.16, 0.25],
+    "02880940": [0.1851, 0.26],
+    "02942699": [0.1430, 0.28],
+    "03642806": [0.3862, 0.58],
+    "03797390": [0.1501, 0.1995],
+}
+
+
+class ShapeNetDirectDataset(torch.utils.data.Dataset):
+    """dataset.py:177-319: one rendered ShapeNet view per item -- dict with pc, pc_canon, trans, quat (wxyz), bound, scale,
+    point_idxs_all [10000, 2+num_more], depth, idxs, shot, normal (the reference's keys without `rgb`: there is no shading).
+
+    Models: `<shapenet_root>/<synset>/<model>/models/model_normalized.obj` (the reference's ShapeNetCore.v2 layout) for the lines
+    "<category id> <synset>/<model>" of the model lists whose id is cfg.category -- data/shapenet_{train,val}.txt resolved
+    against the working directory, as the reference does; the user supplies them.  Each view: the NOCS-limited pose (or
+    uniform SO(3) with full_rot), translation and a size from shapenet_obj_scales drawn from Generator(cfg.seed, item, attempt),
+    rendered at 640x480 with the reference's intrinsics (cppf2_amd.render.make_items), flip2nocs with the bound swap, map_sym
+    of the rotation for the symmetric categories 1, 2, 4.  Item `idx` is view `draw * len(self) + idx` (draw = self.draw,
+    0 by default), so items are reproducible; a view with fewer than 100 points is drawn again with the next attempt
+    number (the reference draws another model instead)."""
+
+    def __init__(self, cfg, full_rot=False, shapenet_root="data/ShapeNetCore.v2",
+                 model_list=("data/shapenet_train.txt", "data/shapenet_val.txt")):
+        super().__init__()
+        self.cfg = cfg
+        self.full_rot = full_rot
+        self.root = os.path.abspath(shapenet_root)
+        names = []
+        for path in ([model_list] if isinstance(model_list, str) else model_list):
+            with open(os.path.abspath(path)) as f:
+                names += [ln.split() for ln in f.read().splitlines() if ln.strip()]
+        self.model_names = [n[1] for n in names if int(n[0]) == int(cfg.category)]
+        get = cfg.get if hasattr(cfg, "get") else (lambda k, d=None: getattr(cfg, k, d))
+        self.seed = int(get("seed", 0) or 0)
+        self.draw = 0
+        self.sym_axis = int(np.where(cfg.up)[0][0]) if int(cfg.category) in (1, 2, 4) else None
+
+    def __len__(self):
+        return len(self.model_names)
+
+    def mesh(self, idx):
+        from cppf2_amd import render
+        return render.load_mesh(os.path.join(self.root, self.model_names[idx], "models", "model_normalized.obj"))
+
+    def items(self, idxs, draw=0):
+        """The items of models `idxs` (one batch of views) for pass `draw`."""
+        from cppf2_amd import render
+        idxs = [int(i) for i in idxs]
+        return render.make_items([self.mesh(i) for i in idxs], [draw * len(self) + i for i in idxs], seed=self.seed,
+                                 full_rot=self.full_rot, res=float(self.cfg.res), num_more=int(self.cfg.num_more),
+                                 scale_ranges=[shapenet_obj_scales[self.model_names[i].split("/")[0]] for i in idxs], nocs=True,
+                                 sym_axis=self.sym_axis)
+
+    def __getitem__(self, idx):
+        if idx >= len(self):
+            raise IndexError("Index out of bounds")
+        return self.items([idx], self.draw)[0]
+
+
+def dump_data(full_rot=False, categories=range(1, 7), draws=100, batch=64, shapenet_root="data/ShapeNetCore.v2",
+              model_list=("data/shapenet_train.txt", "data/shapenet_val.txt")):
+    """dataset.py:371-413: `draws` passes over every model of each category, written as {:06d}.pkl (pass * models + model) to
+    data/category_training_data[_full_rot]/<category>/ -- where ShapeNetExportDataset reads (the reference's own writer formats
+    the suffix as `'_full_rot' if full_rot else None`, i.e. data/category_training_dataNone/ when full_rot is False).  Each file
+    holds pc, pc_canon, bound, shot, normal of a 100-point subsample; no `desc` (no RGB, no DINO descriptor): train_shot.py
+    trains on them, train_dino.py does not."""
+    from cppf2_amd import render
+    from cppf2_amd.config import load_config
+    for cat in categories:
+        cfg = load_config("config", "config", ["category=%s" % id2category[int(cat)]])
+        ds = ShapeNetDirectDataset(cfg, full_rot=full_rot, shapenet_root=shapenet_root, model_list=model_list)
+        out = os.path.join("data", "category_training_data%s" % ("_full_rot" if full_rot else ""), str(cfg.category))
+        os.makedirs(out, exist_ok=True)
+        n = len(ds)
+        for d in range(int(draws)):
+            for a in range(0, n, int(batch)):
+                idxs = list(range(a, min(a + int(batch), n)))
+                render.write_items(out, ds.items(idxs, d), [d * n + i for i in idxs], ds.seed)
 
 
 def _rot4(a, i, j):

@@ -317,6 +317,31 @@ int64_t cppf_voxel_downsample_workspace_bytes(int64_t n);
 int cppf_voxel_downsample(const float* pts, int n, float res, uint64_t seed, int32_t* out_idx, int32_t* out_count,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- training-data generation (the render step of dataset.py:177-319 / :371-413 and train_custom.ipynb cell 4) ---------
+ * Batched depth-only triangle rasterizer: replaces pyrender's OffscreenRenderer depth read-back.  B views in one call.
+ *  - verts float32[num_verts,3] (model frame), tris int32[total_tris,3]; view b draws tris[tri_off[b] .. tri_off[b+1])
+ *    (tri_off int32[B+1], device, tri_off[0] = 0, tri_off[B] = total_tris).  A batch may mix meshes or repeat one.
+ *  - poses float32[B,12]: row-major 3x4 model -> OpenCV camera (x right, y down, z forward).  h_K = (fx, fy, cx, cy),
+ *    host doubles, used as float32; one K for every view.  u = fx*x/z + cx, v = fy*y/z + cy; pixel (r, c) is sampled at
+ *    (c + 0.5, r + 0.5).
+ *  - screen positions are snapped to 1/256 px; edge functions in int64 with the top-left rule (image y down): triangles that
+ *    share an edge cover each pixel on it exactly once.  depth = camera z of the triangle's 1/z plane over the snapped
+ *    positions; the nearest surface wins, equal depths go to the lower triangle id; a pixel whose z lies outside
+ *    [znear, zfar] is not covered.  cull: 0 = none, 1 = back faces ((v1-v0)x(v2-v0) pointing away from the camera).
+ *  - out: depth float32[B,H,W] (0 where nothing is drawn), tri_id int32[B,H,W] (optional; index within the view's range,
+ *    -1 where empty).  H, W <= 8192, B <= 65535.
+ *  - status int64[2] (device): [0] = triangles rejected (a vertex at z < znear or NaN -- no near-plane clipping --, a snapped
+ *    coordinate outside +-2^22 px, a vertex index outside [0, num_verts), a triangle outside every view's range);
+ *    [1] = tile-list entries the call needed.  If [1] > list_capacity, nothing is written past the workspace and depth /
+ *    tri_id stay cleared (invalid): size the workspace for status[1] entries and call again.
+ * The workspace (cppf_render_depth_workspace_bytes; < 0 for invalid sizes) holds 64 bytes per triangle, 12 per 16x16 tile
+ * of every view and 4 per list entry. */
+int64_t cppf_render_depth_workspace_bytes(int B, int64_t total_tris, int H, int W, int64_t list_capacity);
+int cppf_render_depth(int B, const float* verts, int64_t num_verts, const int32_t* tris, const int32_t* tri_off,
+                      int64_t total_tris, const float* poses, const double* h_K, int H, int W, float znear, float zfar, int cull,
+                      float* depth, int32_t* tri_id, int64_t* status, void* workspace, int64_t workspace_bytes,
+                      int64_t list_capacity, void* stream);
+
 /* DINO-branch feature plumbing: replaces interpolate_features (dataset.py:40-59) = grid_sample
  * (bilinear, zeros padding, align_corners=False) of the patch-token map desc at the pixel centres of pts float32[n,2]
  * (x, y), then L2 normalisation over the C channels.  desc is addressed as desc[c*stride_c + y*stride_y + x*stride_x]

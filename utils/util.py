@@ -15,10 +15,13 @@ import os
 import numpy as np
 import torch
 
+from cppf2_amd import geometry as _geometry
 from cppf2_amd import metrics as _metrics
 from cppf2_amd import ops as _ops
 
 fibonacci_sphere = _ops.fibonacci_sphere          # utils/util.py:191-207: list of 3-tuples, Python float64 math
+map_sym = _geometry.map_sym                        # utils/util.py:71-81 (dataset.py:4)
+map_sym_discrete = _geometry.map_sym_discrete      # utils/util.py:66-68 (dataset.py:4)
 
 
 def downsample(pc, res):
