@@ -4,6 +4,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <mutex>
+#include <set>
+#include <utility>
 #include "cppf_hip.h"
 #include "cppf_hip_experimental.h"
 
@@ -38,6 +41,41 @@ extern thread_local char g_cppf_err[256];
       return CPPF_EHIP;                                                                       \
     }                                                                                         \
   } while (0)
+
+#define CPPF_TRY(call)                                                                        \
+  do {                                                                                        \
+    const int rc_ = (call);                                                                   \
+    if (rc_ != CPPF_OK) return rc_;                                                           \
+  } while (0)
+
+// Per-device facts of the launches, queried on first use and cached (written once under a lock -- the library keeps no
+// other state, see cppf_hip.h); both return CPPF_OK or CPPF_EHIP.  cppf_device_cus: the current device and its CU count.
+// cppf_allow_dynamic_lds: lets `kernel` use `bytes` of dynamic LDS on device `dev` (above 64 KiB it must be declared), set
+// once per kernel and device -- every caller asks for one constant size per kernel, so later calls are not compared with the
+// first.  (The set is never destroyed: a launch from another thread during static destruction finds it intact.)
+inline int cppf_device_cus(int* dev, int* cus) {
+  static std::mutex mu;
+  static int count[64] = {0};
+  CPPF_HIP(hipGetDevice(dev));
+  std::lock_guard<std::mutex> lock(mu);
+  int& n = count[*dev & 63];
+  if (n == 0) {
+    CPPF_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, *dev));
+    if (n <= 0) n = 256;
+  }
+  *cus = n;
+  return CPPF_OK;
+}
+
+inline int cppf_allow_dynamic_lds(const void* kernel, int dev, int bytes) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>>& done = *new std::set<std::pair<const void*, int>>;
+  std::lock_guard<std::mutex> lock(mu);
+  if (done.count({kernel, dev})) return CPPF_OK;
+  CPPF_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done.insert({kernel, dev});
+  return CPPF_OK;
+}
 
 struct Axes9 {
   double a[9];

@@ -20,7 +20,6 @@
 // Per 32 rows: 16 + 16 global 16-byte accesses per lane, 128 LDS reads, 512 MFMAs (= 32 768 cycles of the SIMD's matrix
 // pipe); two wavefronts per SIMD cover each other's loads.  MFMA-bound: 84 GFLOP per layer.
 #include "cppf_common.h"
-#include <mutex>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -159,22 +158,12 @@ extern "C" int cppf_reslayer128(float* x, int64_t rows, const float* w1, const f
   CPPF_CHECK_ARG(x && w1 && b1 && w2 && rows >= 0);
   if (rows == 0) return CPPF_OK;
   const int lds_bytes = (2 * RL_DIM * RL_DIM + RL_DIM) * 4;
-  static std::mutex mu;
-  static int cus[64] = {0};
-  int dev = 0;
-  CPPF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (cus[dev & 63] == 0) {
-      hipDeviceProp_t prop;
-      CPPF_HIP(hipGetDeviceProperties(&prop, dev));
-      CPPF_HIP(hipFuncSetAttribute((const void*)reslayer128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-      cus[dev & 63] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-  }
+  int dev = 0, cus = 0;
+  CPPF_TRY(cppf_device_cus(&dev, &cus));
+  CPPF_TRY(cppf_allow_dynamic_lds((const void*)reslayer128_kernel, dev, lds_bytes));
   const int64_t tiles = (rows + RL_ROWS_PER_WAVE - 1) / RL_ROWS_PER_WAVE;
   int64_t blocks = (tiles + (RL_THREADS / 64) - 1) / (RL_THREADS / 64);
-  if (blocks > cus[dev & 63]) blocks = cus[dev & 63];
+  if (blocks > cus) blocks = cus;
   hipLaunchKernelGGL(reslayer128_kernel, dim3((unsigned)blocks), dim3(RL_THREADS), lds_bytes, (hipStream_t)stream, x, rows,
                      w1, b1, w2);
   CPPF_LAUNCH_CHECK();

@@ -40,7 +40,6 @@
 // HBM traffic per row: dim_in + dim_out floats per kernel (+ the residual re-read of an identity first layer: L2 / MALL).
 #include "cppf_common.h"
 #include <atomic>
-#include <mutex>
 #include <type_traits>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -79,8 +78,7 @@ __host__ __device__ constexpr int rs_waves(int nt) { return nt >= 6 ? 4 : 8; }
 // registers building the next block's sums in a second accumulator set during the products (2.2 ms without the loads -- one
 // wavefront per SIMD costs 20 % -- and 3.2 ms with them: spills).)
 __host__ __device__ constexpr int rs_waves_mode(int nt, int mode) { return mode == RS_LINEAR ? 8 : rs_waves(nt); }
-__host__ __device__ constexpr int rs_stage_tiles(int mode) { return 16; }     // tile-steps per ring stage
-__host__ __device__ constexpr int rs_wgs_per_cu(int mode) { return 1; }
+#define RS_STAGE_TILES 16                       // tile-steps per ring stage
 #define RS_FRAG_BYTES 1024                      // one operand fragment: 64 lanes x 8 bf16
 // one staged chunk: up to STG tile-steps of three fragments (16: 48 KiB; 8: 24 KiB)
 __host__ __device__ constexpr int rs_stage_bytes(int stg) { return stg * 3 * RS_FRAG_BYTES; }
@@ -88,7 +86,7 @@ __host__ __device__ constexpr int rs_stage_bytes(int stg) { return stg * 3 * RS_
 // operand, three products per K step; see the f16x2 section below)
 __host__ __device__ constexpr int rs_tile_bytes(int pc) { return pc * RS_FRAG_BYTES; }
 
-// measured variant kept as a switch: LDS fragments requested two tiles ahead instead of one (no faster, 12 registers more).
+// Measured and removed: LDS fragments requested two tiles ahead instead of one (no faster, 12 registers more).
 // (A hand-placed MFMA / filler interleave -- one MFMA, then a few independent instructions; or everything in front of each tile's
 // back-to-back MFMA chain -- was measured in round 3 and removed from the source in round 6: docs/experiments/r6_removed_mlp_variants.patch.)
 // Round 3 measurements (scratch/rs/: rs_probe.hip with the RS_DBG switches, filler_price.hip, mfma_chain.hip + PMC): the kernel is
@@ -100,23 +98,11 @@ __host__ __device__ constexpr int rs_tile_bytes(int pc) { return pc * RS_FRAG_BY
 // the compiler's own order within a tile region (fewer register moves, 5 % faster on the 256-wide identity kernel, equal elsewhere).
 // Also measured, not kept: two tiles per region with their MFMA chains alternating between the two accumulators (3-8 % slower),
 // output halves / quarters for the 256-wide layers at two wavefronts per SIMD (equal), register-staged instead of LDS-DMA weight
-// chunks, the residual of the 256-wide identity kernel loaded before the first product (RS_EARLY_RESIDUAL: 128 registers too many).
-#ifndef RS_DEEP_PREFETCH
-#define RS_DEEP_PREFETCH 0
-#endif
+// chunks, the residual of the 256-wide identity kernel loaded before the first product (128 registers more than there are: spills).
 // timing probes (scratch/rs/rs_probe.hip; results are wrong with any bit set): 1 no weight pieces, 2 no operand split,
 // 4 no LDS fragment reads, 8 no chunk barrier, 16 no x tiles, 32 no residual load / output store
 #ifndef RS_DBG
 #define RS_DBG 0
-#endif
-#ifndef RS_EXACT_PMAX
-#define RS_EXACT_PMAX 1
-#endif
-#ifndef RS_XCD_BLOCKS
-#define RS_XCD_BLOCKS 1          // 0: row blocks dealt round-robin over all workgroups (rounds 2-3)
-#endif
-#ifndef RS_EARLY_RESIDUAL
-#define RS_EARLY_RESIDUAL 0      // 1: the wide identity kernel then needs 128 registers more than there are (spills)
 #endif
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -216,7 +202,7 @@ struct RsStream {
   static constexpr int STG_ = STG, SPC0 = rs_spc(T0, STG), SPC1 = rs_spc(NT, STG), STAGE_BYTES = rs_stage_bytes(STG);
   // pieces of a chunk per wavefront, at most (a chunk = rs_spc(tiles) K steps of `tiles` tiles, three fragments each)
   static constexpr int P0 = (SPC0 * T0 * PC + WAVES - 1) / WAVES, P1 = (SPC1 * NT * PC + WAVES - 1) / WAVES;
-  static constexpr int PMAX = RS_EXACT_PMAX ? (P0 > P1 ? P0 : P1) : 48 / WAVES;
+  static constexpr int PMAX = P0 > P1 ? P0 : P1;
   int nseg;                    // 2 + 2 per chained identity layer
   int chunks;                  // chunks per row block
   const char* base;            // packed stream in global memory
@@ -319,20 +305,12 @@ __device__ __forceinline__ RsFrag rs_read(const u32x4* w, int tile) {
 // of the NEXT step's B operand, a quarter per call) and `dma(q)`, q < PMAX, the LDS-DMA issue of one piece of the next
 // weight chunk: both are placed in front of a tile's MFMAs so that they issue in their shadow; the scheduling barrier
 // per tile keeps the compiler from hoisting all the reads / all the filler to the step's front.
-template <int NTILES, bool PREFETCH, int PMAX, int PC, class F, class D>
+template <int NTILES, int PMAX, int PC, class F, class D>
 __device__ __forceinline__ void rs_step(f32x16 (&acc)[NTILES], const u32x4* w, const RsFrag& b, F&& filler, D&& dma) {
-  // PREFETCH: fragments are requested two tiles ahead (one wavefront per SIMD: nobody else covers the LDS latency);
-  // otherwise one tile ahead
   RsFrag a0 = rs_read<PC>(w, 0), a1 = a0;
-  if (PREFETCH && NTILES > 1) a1 = rs_read<PC>(w, 1);
 #pragma unroll
   for (int u = 0; u < NTILES; ++u) {
-    RsFrag a2 = a1;
-    if (PREFETCH) {
-      if (u + 2 < NTILES) a2 = rs_read<PC>(w, u + 2);
-    } else {
-      if (u + 1 < NTILES) a1 = rs_read<PC>(w, u + 1);
-    }
+    if (u + 1 < NTILES) a1 = rs_read<PC>(w, u + 1);
 #pragma unroll
     for (int q = (u * PMAX + NTILES - 1) / NTILES; q < ((u + 1) * PMAX + NTILES - 1) / NTILES; ++q) dma(q);
 #pragma unroll
@@ -340,7 +318,6 @@ __device__ __forceinline__ void rs_step(f32x16 (&acc)[NTILES], const u32x4* w, c
     rs_mma<PC>(acc[u], a0, b);
     __builtin_amdgcn_sched_barrier(0);
     a0 = a1;
-    if (PREFETCH) a1 = a2;
   }
 }
 
@@ -398,7 +375,7 @@ struct RsX {
 // weight pieces.  Step s: wait for tile s + 1 (two tiles younger: vmcnt(4) before, vmcnt(2) after the issue of tile
 // s + 3 -- the wait comes first), read it, issue tile s + 3 into the slot tile s left, split tile s + 1 in the shadow of
 // step s's MFMAs.
-template <int NTILES, bool PREFETCH, int PC, class X, class Stream>
+template <int NTILES, int PC, class X, class Stream>
 __device__ __forceinline__ void rs_product_x(f32x16 (&acc)[NTILES], const X xs, const RsRow rw, int ks1, Stream& ws) {
   constexpr int SPC = rs_spc(NTILES, Stream::STG_);
   float xv[8];
@@ -422,9 +399,9 @@ __device__ __forceinline__ void rs_product_x(f32x16 (&acc)[NTILES], const X xs, 
         xs.issue(s0 + i + 3, slot == 0 ? 2 : slot - 1, rw);
         slot = slot == 2 ? 0 : slot + 1;
         RsFrag bn;
-        rs_step<NTILES, PREFETCH, Stream::PMAX, PC>(acc, w + i * NTILES * PC * 64, b,
-                                  [&](int p) { rs_split_pair<PC, true>(xv[2 * p], xv[2 * p + 1], bn.h[p], bn.m[p], bn.l[p]); },
-                                  [&](int q) { if (i == 0) ws.piece(q); });
+        rs_step<NTILES, Stream::PMAX, PC>(acc, w + i * NTILES * PC * 64, b,
+                        [&](int p) { rs_split_pair<PC, true>(xv[2 * p], xv[2 * p + 1], bn.h[p], bn.m[p], bn.l[p]); },
+                        [&](int q) { if (i == 0) ws.piece(q); });
         b = bn;
       }
     }
@@ -436,7 +413,7 @@ __device__ __forceinline__ void rs_product_x(f32x16 (&acc)[NTILES], const X xs, 
 // that feature order.  The split of step + 1 runs in the shadow of step's MFMAs (pinned there, which also keeps CSE from
 // keeping a once-computed split alive across products at 24 registers per tile).
 // (bs: the factor the source tiles carry and the B operand must not -- 1 for the bf16 triples, 1 / weight scale for the fp16 pairs)
-template <int NS, int NTILES, bool PREFETCH, int PC, class Stream>
+template <int NS, int NTILES, int PC, class Stream>
 __device__ __forceinline__ void rs_product_h(f32x16 (&dst)[NTILES], const f32x16 (&src)[NS], Stream& ws, float bs) {
   constexpr int SPC = rs_spc(NTILES, Stream::STG_);
   static_assert((2 * NS) % SPC == 0, "whole chunks");
@@ -451,14 +428,14 @@ __device__ __forceinline__ void rs_product_h(f32x16 (&dst)[NTILES], const f32x16
     for (int i = 0; i < SPC; ++i) {
       const int step = c * SPC + i, nx = (step + 1 < 2 * NS) ? step + 1 : step;
       RsFrag bn = b;
-      rs_step<NTILES, PREFETCH, Stream::PMAX, PC>(dst, w + i * NTILES * PC * 64, b,
-                                [&](int p) {
-                                  if (step + 1 < 2 * NS) {
-                                    const float s0 = src[nx >> 1][8 * (nx & 1) + 2 * p], s1 = src[nx >> 1][8 * (nx & 1) + 2 * p + 1];
-                                    rs_split_pair<PC, true>(PC == 2 ? s0 * bs : s0, PC == 2 ? s1 * bs : s1, bn.h[p], bn.m[p], bn.l[p]);
-                                  }
-                                },
-                                [&](int q) { if (i == 0) ws.piece(q); });
+      rs_step<NTILES, Stream::PMAX, PC>(dst, w + i * NTILES * PC * 64, b,
+                      [&](int p) {
+                        if (step + 1 < 2 * NS) {
+                          const float s0 = src[nx >> 1][8 * (nx & 1) + 2 * p], s1 = src[nx >> 1][8 * (nx & 1) + 2 * p + 1];
+                          rs_split_pair<PC, true>(PC == 2 ? s0 * bs : s0, PC == 2 ? s1 * bs : s1, bn.h[p], bn.m[p], bn.l[p]);
+                        }
+                      },
+                      [&](int q) { if (i == 0) ws.piece(q); });
       b = bn;
     }
   }
@@ -698,7 +675,7 @@ __device__ __forceinline__ void rs_encode_coord_tiles(char* slots, int lane, int
 // multiplied by 1 / wscale (exact).  Activations are split unscaled: |x| < 65504 is required, subnormal lo pieces are honoured
 // by the matrix core (absolute resolution 2^-25 for small activations).
 template <int NT, bool PROJ, bool GATHER, bool DECODE = false, int PC = 3, int MODE = RS_RESLAYER>
-__global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) void reslayer_split_kernel(const float* x, int64_t ldx, int k_in, float* out,
+__global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), 1) void reslayer_split_kernel(const float* x, int64_t ldx, int k_in, float* out,
                                                                               int64_t ldo, int64_t rows,
                                                                               const char* __restrict__ wq,
                                                                               const float* __restrict__ b1,
@@ -713,7 +690,6 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
   constexpr bool LOCAL_IDX = MODE == RS_ENCODE || MODE == RS_SUMENCODE;    // gidx holds the sampler's scene-local indices
   static_assert(!SUMG || (PROJ && !GATHER), "the table sums stand for columns of a projection layer's input");
   static_assert(MODE != RS_ENCODE || (GATHER && !DECODE), "RS_ENCODE is a form of the gathering launch");
-  constexpr bool PF = RS_DEEP_PREFETCH && WAVES == 4;   // LDS read-ahead: two tiles or (measured no slower) one
   extern __shared__ __attribute__((aligned(16))) char s_ring[];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);       // wave-uniform: keeps its derived addresses scalar
@@ -725,7 +701,7 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
   // by side, so that the rows in flight on one XCD are neighbours -- the tuples of ONE scene, whose per-point table (1 MB for the
   // SHOT model) then stays in that XCD's L2 instead of being fetched by all eight.  Other grids: plain round-robin.
   int64_t bfirst = blockIdx.x, bstride = gridDim.x, bend = nblocks;
-  if (RS_XCD_BLOCKS && (gridDim.x & 7) == 0 && nblocks >= 64) {
+  if ((gridDim.x & 7) == 0 && nblocks >= 64) {
     const int64_t xcd = blockIdx.x & 7;
     bfirst = nblocks * xcd / 8 + (blockIdx.x >> 3);
     bend = nblocks * (xcd + 1) / 8;
@@ -740,12 +716,12 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
   // (accessed with workgroup-scope atomics only -- rs_claim_store / rs_claim_load: thread 0's stores and every lane's loads stay where
   // they are written relative to the barriers of the products; the s_barrier builtin carries no memory semantics the compiler would
   // have to respect for plain LDS accesses)
-  int* const s_claim = reinterpret_cast<int*>(s_ring + 2 * rs_stage_bytes(rs_stage_tiles(MODE)) + WAVES * 3 * 2048 + (2 + chain) * 32 * NT * 4);
+  int* const s_claim = reinterpret_cast<int*>(s_ring + 2 * rs_stage_bytes(RS_STAGE_TILES) + WAVES * 3 * 2048 + (2 + chain) * 32 * NT * 4);
   if (dyn) { bfirst = blockIdx.x; bstride = 0; bend = nblocks; }
   const int64_t mine = dyn ? (bfirst < bend ? 1 : 0) : (bend > bfirst ? (bend - bfirst + bstride - 1) / bstride : 0);
   if (dyn && threadIdx.x == 0) rs_claim_store(&s_claim[0], (int)gridDim.x + atomicAdd(&sched[0], 1));
 
-  constexpr int STG = rs_stage_tiles(MODE), RING_BYTES = 2 * rs_stage_bytes(STG);
+  constexpr int STG = RS_STAGE_TILES, RING_BYTES = 2 * rs_stage_bytes(STG);
   RsStream<NT, T0, WAVES, PC, LIN, STG> ws;
   // RS_LINEAR: `chain` is the number of column groups this workgroup evaluates (blockIdx.y selects which: grids with fewer row
   // blocks than CUs are spread over the groups as well)
@@ -844,7 +820,7 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
         f32x16 acc[NT];
 #pragma unroll
         for (int u = 0; u < NT; ++u) rs_load_tile(acc[u], s_b1 + 32 * (grp * NT + u), g);
-        rs_product_x<NT, false, PC>(acc, xs, cur, ks1, ws);
+        rs_product_x<NT, PC>(acc, xs, cur, ks1, ws);
         const bool last = grp + 1 == chain;
         if (!last || more) {                      // the x tiles of the next pass: the same rows again, or the next row block's
           const RsRow nx = last ? nxt : cur;
@@ -916,7 +892,7 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
         }
       }
     }
-    if (!PROJ && (WAVES == 8 || RS_EARLY_RESIDUAL)) {   // residual of an identity layer: requested before the first product (while
+    if (!PROJ && WAVES == 8) {                          // residual of an identity layer: requested before the first product (while
                                                         // the x tiles of the same rows are passing through L2)
 #pragma unroll
       for (int u = 0; u < NT; ++u) {
@@ -926,14 +902,14 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
     }
     {
       f32x16 (&first)[T0] = *reinterpret_cast<f32x16 (*)[T0]>(&acc[0]);
-      rs_product_x<T0, PF, PC>(first, xs, cur, ks1, ws);
+      rs_product_x<T0, PC>(first, xs, cur, ks1, ws);
     }
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) h[u][e] = (h[u][e] < 0.0f) ? 0.0f : h[u][e];        // NaN stays NaN like torch.relu
     }
-    if (!PROJ && WAVES == 4 && !RS_EARLY_RESIDUAL) {     // (measured alternative: after it; re-reads 1.2 GB per launch from HBM)
+    if (!PROJ && WAVES == 4) {                           // (measured alternative: after it; re-reads 1.2 GB per launch from HBM)
       if (PC == 2) {
         // scaled on the way in, two tiles at a time: the products are VALU results, which reach the accumulator half of the
         // register file through v_accvgpr_write -- all eight tiles at once would need 128 transient registers (spills)
@@ -958,7 +934,7 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
     if (more) first_tiles(nxt);
     cur = nxt;
     // ---- y^T = skip^T + W2 h^T --------------------------------------------------------------------------
-    rs_product_h<NT, NT, PF, PC>(o, h, ws, bs);
+    rs_product_h<NT, NT, PC>(o, h, ws, bs);
     if (tap.out && in) {                        // the first layer's output is needed in memory as well (the tuple features)
       float* trow = tap.out + row * tap.ld + 4 * g;
 #pragma unroll
@@ -979,13 +955,13 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), rs_wgs_per_cu(MODE)) 
       const float* bl = s_b1 + 32 * NT * (2 + l);
 #pragma unroll
       for (int u = 0; u < NT; ++u) rs_load_tile(h[u], bl + 32 * u, g);
-      rs_product_h<NT, NT, PF, PC>(h, o, ws, bs);
+      rs_product_h<NT, NT, PC>(h, o, ws, bs);
 #pragma unroll
       for (int u = 0; u < NT; ++u) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) h[u][e] = (h[u][e] < 0.0f) ? 0.0f : h[u][e];
       }
-      rs_product_h<NT, NT, PF, PC>(o, h, ws, bs);
+      rs_product_h<NT, NT, PC>(o, h, ws, bs);
     }
     if (DECODE) {
       // (the draw as the row block's own epilogue.  Cut into pieces and hidden under the NEXT block's first product it was
@@ -1030,6 +1006,12 @@ static int64_t rs_stream_bytes(int32_t k_in, int32_t n_out, int32_t proj, int32_
   return (ks1 * (proj ? 2 : 1) + (1 + 2 * (int64_t)chain) * 2 * nt) * nt * rs_tile_bytes(pc);
 }
 
+// RS_LINEAR: per column group of 256 outputs the first-product segment of pack_split for that group's 256 rows of W
+static int64_t rs_linear_stream_bytes(int32_t k_in, int32_t n_out, int pc) {
+  if (k_in <= 0 || n_out <= 0 || (n_out & 255) != 0) return -1;
+  return (int64_t)((k_in + 15) / 16) * (n_out / 32) * rs_tile_bytes(pc);
+}
+
 extern "C" int64_t cppf_reslayer_split_stream_bytes(int32_t k_in, int32_t n_out, int32_t proj, int32_t chain) {
   return rs_stream_bytes(k_in, n_out, proj, chain, 3);
 }
@@ -1049,52 +1031,172 @@ extern "C" int cppf_mlp_reserve_cus(int32_t cus) {
   return cus < 0 ? g_rs_reserved_cus.load() : g_rs_reserved_cus.exchange(cus);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Host side: every entry point below fills one RsRequest, rs_check validates it (all shape and alignment rules, once per
+// form) and rs_run maps it onto the kernel instantiations.  Nothing touches the device before the check or for rows == 0.
+// ---------------------------------------------------------------------------------------------------------------------
+enum class RsForm { plain, gather, encode, decode, linear, sumgather, sumencode };
+
+struct RsRequest {
+  const char* fn;               // the entry point, for the error message
+  int pc;                       // arithmetic: 3 = bf16 triples, 2 = f16x2 (rs_tile_bytes)
+  RsForm form;
+  const float* x;               // gather / sumgather: the head columns (k_in of them); encode / sumencode: NULL
+  int64_t ldx;
+  int k_in;                     // encode: 40, sumencode: 32 (the head columns the kernel builds)
+  float* out;
+  int64_t ldo;
+  int n_out;                    // decode: 192 whatever the caller says
+  int64_t rows;
+  const void* wq;
+  int64_t wq_bytes;
+  const float* b1;
+  const float* b0;              // NULL: identity skip (plain) or no projection (linear)
+  int chain;
+  float weight_scale;           // f16x2 only (1 for the bf16 triples)
+  int fdim;                     // gather / encode: the descriptor width, ga.slots descriptors per row
+  RsGather ga;                  // gidx / table / slots / tld / pts ... B, sched; head and fshift are rs_run's
+  RsDecode dc;
+  RsTap tap;                    // plain only
+  hipStream_t stream;
+};
+
+static RsRequest rs_request(const char* fn, int pc, RsForm form, const float* x, int64_t ldx, int k_in, float* out, int64_t ldo,
+                            int n_out, int64_t rows, const void* wq, int64_t wq_bytes, const float* b1, const float* b0, int chain,
+                            int32_t* sched, void* stream) {
+  RsRequest r{fn, pc, form, x, ldx, k_in, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, 1.0f, 0};
+  r.ga.sched = sched;
+  r.stream = (hipStream_t)stream;
+  return r;
+}
+
+#define RS_CHECK(cond)                                                                                    \
+  do {                                                                                                    \
+    if (!(cond)) {                                                                                        \
+      snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: invalid argument: %s", r.fn, #cond);                  \
+      return CPPF_EINVAL;                                                                                 \
+    }                                                                                                     \
+  } while (0)
+
+static int rs_unsupported(const RsRequest& r) {
+  snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: n_out = %d, %d points per tuple (the gathering and encoding kernels are the "
+           "128-wide projection layer of the tuple encoders; the encoding ones take 5-point tuples)", r.fn, r.n_out, r.ga.slots);
+  return CPPF_EUNSUPPORTED;
+}
+
+// The shapes: k_in a multiple of 8 (gather: >= 0 head columns; else > 0) with ldx >= k_in; every row stride a multiple of 4
+// and every streamed array 16-byte aligned; n_out in {64, 128, 192, 256} (plain), 192 (decode), a multiple of 256 (linear)
+// or 128 (the gathering and encoding forms, which build the tuple encoder's first layer: 5-point tuples); chain <= 15;
+// wq_bytes = the stream size of exactly this launch.  CPPF_EINVAL for a broken rule, CPPF_EUNSUPPORTED for a valid shape
+// without a kernel.
+static int rs_check(const RsRequest& r) {
+  const RsForm f = r.form;
+  const RsGather& ga = r.ga;
+  const bool gathers = f == RsForm::gather || f == RsForm::sumgather, encodes = f == RsForm::encode || f == RsForm::sumencode;
+  const bool tables = f == RsForm::sumgather || f == RsForm::sumencode;
+  RS_CHECK(r.wq && r.rows >= 0 && r.chain >= 0 && r.chain <= 15 && (r.b1 || f == RsForm::linear) && (r.x || encodes));
+  RS_CHECK(f == RsForm::decode || r.out);
+  RS_CHECK((((uintptr_t)r.x | (uintptr_t)r.out | (uintptr_t)r.wq | (uintptr_t)r.tap.out | (uintptr_t)ga.table |
+             (uintptr_t)r.dc.prior) & 15) == 0);
+  RS_CHECK((r.ldx & 3) == 0 && (r.ldo & 3) == 0 && (r.tap.ld & 3) == 0);
+  if (r.pc == 2) {
+    int e = 0;
+    RS_CHECK(r.weight_scale > 0.0f && frexpf(r.weight_scale, &e) == 0.5f);        // a power of two
+  }
+  RS_CHECK(!r.tap.out || (f == RsForm::plain && r.tap.out != r.out && r.tap.out != r.x && r.tap.ld >= r.n_out));
+  if (f == RsForm::gather) RS_CHECK(r.k_in >= 0 && (r.k_in & 7) == 0 && r.ldx >= r.k_in);
+  else if (!encodes) RS_CHECK(r.k_in > 0 && (r.k_in & 7) == 0 && r.ldx >= r.k_in);
+  if (f != RsForm::decode) RS_CHECK(r.ldo >= r.n_out);
+  if (f == RsForm::plain) RS_CHECK((r.n_out == 64 || r.n_out == 128 || r.n_out == 192 || r.n_out == 256) && (r.b0 || r.k_in == r.n_out));
+  if (f == RsForm::linear) RS_CHECK(r.n_out > 0 && (r.n_out & 255) == 0 && !r.b0);
+  if (f == RsForm::decode) {
+    RS_CHECK(r.b0 && r.dc.uniforms && r.dc.bins && r.chain == 0);
+    RS_CHECK(!(r.dc.prior && r.dc.prior_pos) && (!r.dc.prior_pos || (r.dc.prior_inv_sigma > 0.0f && r.dc.prior_inv_sigma < INFINITY)));
+  }
+  if (gathers || encodes) RS_CHECK(r.b0 && ga.gidx && ga.table);
+  if (encodes) RS_CHECK(ga.B > 0 && ga.pts && ga.pt_off && ga.tup_off && (f == RsForm::sumencode || ga.nrm));
+  if (gathers) RS_CHECK(ga.slots >= 1 && ga.slots <= 8);
+  if (f == RsForm::gather || f == RsForm::encode) RS_CHECK(r.fdim >= 8 && (r.fdim & (r.fdim - 1)) == 0);
+  if (tables) RS_CHECK(ga.tld >= (int64_t)ga.slots * 256 && (ga.tld & 3) == 0);
+  // the gathering and encoding kernels are the 128-wide projection layer of the tuple encoders (encoding: 5-point tuples)
+  const bool supported = !(gathers || encodes) || (r.n_out == 128 && (gathers || ga.slots == 5));
+  if (!supported && encodes) return rs_unsupported(r);     // (the tuple size decides the input width: before the stream size)
+  const int k = (f == RsForm::gather || f == RsForm::encode) ? r.k_in + ga.slots * r.fdim : r.k_in;
+  const int64_t stream_bytes = f == RsForm::linear ? rs_linear_stream_bytes(k, r.n_out, r.pc)
+                                                   : rs_stream_bytes(k, f == RsForm::decode ? 192 : r.n_out, r.b0 != nullptr, r.chain, r.pc);
+  RS_CHECK(r.wq_bytes == stream_bytes);
+  return supported ? CPPF_OK : rs_unsupported(r);
+}
+#undef RS_CHECK
+
 template <int NT, bool PROJ, bool GATHER = false, bool DECODE = false, int PC = 3, int MODE = RS_RESLAYER>
-static int rs_launch(const float* x, int64_t ldx, int k_in, float* out, int64_t ldo, int64_t rows, const char* wq,
-                     const float* b1, const float* b0, int chain, int cus, hipStream_t stream, RsGather ga = RsGather(),
-                     RsDecode dc = RsDecode(), RsTap tap = RsTap(), float wscale = 1.0f) {
+static int rs_launch(const RsRequest& r) {
   constexpr int WAVES = rs_waves_mode(NT, MODE), THREADS = 64 * WAVES, BLOCK_ROWS = 32 * WAVES;
-  const int64_t nblocks = (rows + BLOCK_ROWS - 1) / BLOCK_ROWS;
+  int dev = 0, cus = 0;
+  CPPF_TRY(cppf_device_cus(&dev, &cus));
+  const int64_t nblocks = (r.rows + BLOCK_ROWS - 1) / BLOCK_ROWS;
   const int forced = g_rs_debug_cus.load();
   if (forced > 0) cus = forced;
   else cus = cus - g_rs_reserved_cus.load() > cus / 2 ? cus - g_rs_reserved_cus.load() : (cus + 1) / 2;   // never below half the chip
-  cus *= rs_wgs_per_cu(MODE);
   const unsigned grid = (unsigned)(nblocks < cus ? nblocks : cus);
   // RS_LINEAR: `chain` = column groups of 32 NT outputs; with fewer row blocks than CUs the groups are spread over blockIdx.y
+  int chain = r.chain;
   unsigned gy = 1;
   if (MODE == RS_LINEAR && (int64_t)grid * 2 <= cus) {
     for (int d = chain; d >= 1; --d)
       if (chain % d == 0 && (int64_t)grid * d <= cus) { gy = (unsigned)d; break; }
     chain /= (int)gy;
   }
-  const int lds_bytes = 2 * rs_stage_bytes(rs_stage_tiles(MODE)) + WAVES * 3 * 2048 + (MODE == RS_LINEAR ? chain : 2 + chain) * 32 * NT * 4 + 16;
-  if (lds_bytes > 160 * 1024 / rs_wgs_per_cu(MODE)) {
+  const int lds_bytes = 2 * rs_stage_bytes(RS_STAGE_TILES) + WAVES * 3 * 2048 + (MODE == RS_LINEAR ? chain : 2 + chain) * 32 * NT * 4 + 16;
+  if (lds_bytes > 160 * 1024) {
     snprintf(g_cppf_err, sizeof(g_cppf_err), "reslayer_split: %d bytes of LDS for the biases of this launch (too many column groups)", lds_bytes);
     return CPPF_EINVAL;
   }
-  {
-    // more than 64 KiB of dynamic LDS: declared once per kernel and device
-    static std::mutex mu;
-    static bool done[64] = {false};
-    int dev = 0;
-    CPPF_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    if (!done[dev & 63]) {
-      CPPF_HIP(hipFuncSetAttribute((const void*)reslayer_split_kernel<NT, PROJ, GATHER, DECODE, PC, MODE>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      done[dev & 63] = true;
-    }
-  }
-  hipLaunchKernelGGL((reslayer_split_kernel<NT, PROJ, GATHER, DECODE, PC, MODE>), dim3(grid, gy), dim3(THREADS), lds_bytes, stream, x,
-                     ldx, k_in, out, ldo, rows, wq, b1, b0, chain, ga, dc, tap, wscale);
+  CPPF_TRY(cppf_allow_dynamic_lds((const void*)reslayer_split_kernel<NT, PROJ, GATHER, DECODE, PC, MODE>, dev, 160 * 1024));
+  hipLaunchKernelGGL((reslayer_split_kernel<NT, PROJ, GATHER, DECODE, PC, MODE>), dim3(grid, gy), dim3(THREADS), lds_bytes, r.stream, r.x, r.ldx, r.k_in, r.out, r.ldo, r.rows,
+                     static_cast<const char*>(r.wq), r.b1, r.b0, chain, r.ga, r.dc, r.tap, r.weight_scale);
   CPPF_LAUNCH_CHECK();
   return CPPF_OK;
 }
 
-static int rs_cus() {
-  int dev = 0, n_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 256;
-  return n_cu > 0 ? n_cu : 256;
+// a checked request onto its kernel (f16x2 has no encoding forms)
+template <int PC>
+static int rs_run(RsRequest r) {
+  if (r.rows == 0) return CPPF_OK;
+  const bool proj = r.b0 != nullptr;
+  if (r.form == RsForm::gather || r.form == RsForm::encode) {      // k_in head columns, then ga.slots descriptors of fdim
+    r.ga.head = r.k_in;
+    r.ga.fshift = __builtin_ctz((unsigned)r.fdim);
+    r.k_in += r.ga.slots * r.fdim;
+  }
+  switch (r.form) {
+    case RsForm::plain:
+      switch (r.n_out / 32) {
+        case 2: return proj ? rs_launch<2, true, false, false, PC>(r) : rs_launch<2, false, false, false, PC>(r);
+        case 4: return proj ? rs_launch<4, true, false, false, PC>(r) : rs_launch<4, false, false, false, PC>(r);
+        case 6: return proj ? rs_launch<6, true, false, false, PC>(r) : rs_launch<6, false, false, false, PC>(r);
+        default: return proj ? rs_launch<8, true, false, false, PC>(r) : rs_launch<8, false, false, false, PC>(r);
+      }
+    case RsForm::gather: return rs_launch<4, true, true, false, PC>(r);
+    case RsForm::decode:
+      r.out = nullptr;
+      r.ldo = 192;
+      if (!r.dc.prior_pos) r.dc.prior_inv_sigma = 0.0f;
+      return rs_launch<6, true, false, true, PC>(r);
+    case RsForm::linear:
+      r.chain = r.n_out / 256;
+      return rs_launch<8, false, false, false, PC, RS_LINEAR>(r);
+    case RsForm::sumgather: return rs_launch<4, true, false, false, PC, RS_SUMGATHER>(r);
+    default:
+      if constexpr (PC == 3) return r.form == RsForm::encode ? rs_launch<4, true, true, false, 3, RS_ENCODE>(r)
+                                                             : rs_launch<4, true, false, false, 3, RS_SUMENCODE>(r);
+      return rs_unsupported(r);
+  }
+}
+
+static int rs_submit(const RsRequest& r) {
+  CPPF_TRY(rs_check(r));
+  return r.pc == 2 ? rs_run<2>(r) : rs_run<3>(r);
 }
 
 // out[rows, n_out] = L_chain(...L_1(L_0(x))): L_0(x) = skip(x) + relu(x[:, :k_in] W1^T + b1) W2^T with skip = x (b0 == NULL;
@@ -1104,54 +1206,11 @@ static int rs_cus() {
 // 192, 256}.  wq = the layers' weights as the packed split stream (cppf_reslayer_split_stream_bytes bytes;
 // cppf2_amd.models.pack_split documents the order); b1 = float32[(1 + chain) * n_out], the first-layer biases of L_0,
 // L_1, ...  The second-layer biases are the caller's (carried as a pending offset by cppf2_amd.models.fused_stack).
-static int rs_dispatch(const float* x, int64_t ldx, int32_t k_in, float* out, int64_t ldo, int32_t n_out, int64_t rows,
-                       const void* wq, int64_t wq_bytes, const float* b1, const float* b0, int32_t chain, RsTap tap,
-                       int32_t* sched, void* stream, const char* fn) {
-  if (!(x && out && wq && b1 && rows >= 0) || !(k_in > 0 && (k_in & 7) == 0 && ldx >= k_in && (ldx & 3) == 0 && (ldo & 3) == 0 && ldo >= n_out) ||
-      !(n_out == 64 || n_out == 128 || n_out == 192 || n_out == 256) || !(b0 != nullptr || k_in == n_out) ||
-      !(chain >= 0 && chain <= 15) || (((uintptr_t)x | (uintptr_t)out | (uintptr_t)wq | (uintptr_t)tap.out) & 15) != 0 ||
-      (tap.out && ((tap.ld & 3) != 0 || tap.ld < n_out)) ||
-      wq_bytes != cppf_reslayer_split_stream_bytes(k_in, n_out, b0 != nullptr, chain)) {
-    snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: invalid argument (pointers, 16-byte alignment, k_in %% 8, strides %% 4, n_out in "
-             "{64,128,192,256}, chain <= 15, stream size)", fn);
-    return CPPF_EINVAL;
-  }
-  if (rows == 0) return CPPF_OK;
-  static std::mutex mu;
-  static int cus[64] = {0};
-  int dev = 0;
-  CPPF_HIP(hipGetDevice(&dev));
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (cus[dev & 63] == 0) {
-      hipDeviceProp_t prop;
-      CPPF_HIP(hipGetDeviceProperties(&prop, dev));
-      cus[dev & 63] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-  }
-  const int n_cu = cus[dev & 63];
-  const char* w = static_cast<const char*>(wq);
-  hipStream_t st = (hipStream_t)stream;
-  const bool proj = b0 != nullptr;
-  RsGather ga;
-  ga.sched = sched;
-  const RsDecode dc = RsDecode();
-  switch (n_out / 32) {
-    case 2: return proj ? rs_launch<2, true>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap)
-                        : rs_launch<2, false>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap);
-    case 4: return proj ? rs_launch<4, true>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap)
-                        : rs_launch<4, false>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap);
-    case 6: return proj ? rs_launch<6, true>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap)
-                        : rs_launch<6, false>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap);
-    default: return proj ? rs_launch<8, true>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap)
-                         : rs_launch<8, false>(x, ldx, k_in, out, ldo, rows, w, b1, b0, chain, n_cu, st, ga, dc, tap);
-  }
-}
-
 extern "C" int cppf_reslayer_split(const float* x, int64_t ldx, int32_t k_in, float* out, int64_t ldo, int32_t n_out,
                                    int64_t rows, const void* wq, int64_t wq_bytes, const float* b1, const float* b0,
                                    int32_t chain, int32_t* sched, void* stream) {
-  return rs_dispatch(x, ldx, k_in, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, RsTap(), sched, stream, __func__);
+  return rs_submit(rs_request(__func__, 3, RsForm::plain, x, ldx, k_in, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, sched,
+                              stream));
 }
 
 // cppf_reslayer_split with a second output: first_out [rows, >= n_out] (row stride ld_first) receives the activation after the
@@ -1161,14 +1220,11 @@ extern "C" int cppf_reslayer_split(const float* x, int64_t ldx, int32_t k_in, fl
 extern "C" int cppf_reslayer_split_tap(const float* x, int64_t ldx, int32_t k_in, float* first_out, int64_t ld_first, float* out,
                                        int64_t ldo, int32_t n_out, int64_t rows, const void* wq, int64_t wq_bytes,
                                        const float* b1, const float* b0, int32_t chain, int32_t* sched, void* stream) {
-  if (!first_out || first_out == out || first_out == x) {
-    snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: first_out must be a buffer of its own", __func__);
-    return CPPF_EINVAL;
-  }
-  RsTap tap;
-  tap.out = first_out;
-  tap.ld = ld_first;
-  return rs_dispatch(x, ldx, k_in, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, tap, sched, stream, __func__);
+  CPPF_CHECK_ARG(first_out != nullptr);
+  RsRequest r = rs_request(__func__, 3, RsForm::plain, x, ldx, k_in, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, sched, stream);
+  r.tap.out = first_out;
+  r.tap.ld = ld_first;
+  return rs_submit(r);
 }
 
 // The first ResLayer of the SHOT model's tuple encoder fed by the tuple encode itself (train_shot.py:75-83 never materialised):
@@ -1182,31 +1238,13 @@ extern "C" int cppf_reslayer_split_gather(const float* heads, int64_t ld_heads, 
                                           int32_t slots, const float* table, int32_t fdim, float* out, int64_t ldo,
                                           int32_t n_out, int64_t rows, const void* wq, int64_t wq_bytes, const float* b1,
                                           const float* b0, int32_t chain, int32_t* sched, void* stream) {
-  CPPF_CHECK_ARG(heads && gidx && table && out && wq && b1 && b0 && rows >= 0);
-  CPPF_CHECK_ARG(head_cols >= 0 && (head_cols & 7) == 0 && ld_heads >= head_cols && (ld_heads & 3) == 0);
-  CPPF_CHECK_ARG(slots >= 1 && slots <= 8 && fdim >= 8 && (fdim & (fdim - 1)) == 0);
-  CPPF_CHECK_ARG((ldo & 3) == 0 && ldo >= n_out && chain >= 0 && chain <= 15);
-  CPPF_CHECK_ARG((((uintptr_t)heads | (uintptr_t)table | (uintptr_t)out | (uintptr_t)wq) & 15) == 0);
-  const int k_in = head_cols + slots * fdim;
-  CPPF_CHECK_ARG(wq_bytes == cppf_reslayer_split_stream_bytes(k_in, n_out, 1, chain));
-  if (n_out != 128) {
-    snprintf(g_cppf_err, sizeof(g_cppf_err), "cppf_reslayer_split_gather: n_out = %d (only the 128-wide projection layer of the "
-             "tuple encoder has a gathering kernel)", n_out);
-    return CPPF_EUNSUPPORTED;
-  }
-  if (rows == 0) return CPPF_OK;
-  int dev = 0, n_cu = 0;
-  CPPF_HIP(hipGetDevice(&dev));
-  CPPF_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  RsGather ga;
-  ga.gidx = gidx;
-  ga.table = table;
-  ga.slots = slots;
-  ga.head = head_cols;
-  ga.fshift = __builtin_ctz((unsigned)fdim);
-  ga.sched = sched;
-  return rs_launch<4, true, true>(heads, ld_heads, k_in, out, ldo, rows, static_cast<const char*>(wq), b1, b0, chain,
-                                  n_cu > 0 ? n_cu : 256, (hipStream_t)stream, ga);
+  RsRequest r = rs_request(__func__, 3, RsForm::gather, heads, ld_heads, head_cols, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain,
+                           sched, stream);
+  r.ga.gidx = gidx;
+  r.ga.table = table;
+  r.ga.slots = slots;
+  r.fdim = fdim;
+  return rs_submit(r);
 }
 
 // cppf_reslayer_split_gather with the pair features built inside the kernel (RS_ENCODE): prepare_tuple_inputs (train_shot.py:75-83)
@@ -1217,31 +1255,18 @@ extern "C" int cppf_reslayer_split_encode(int B, const float* pts, const float* 
                                           const int32_t* pt_off, const int32_t* tup_off, const float* table, int32_t fdim,
                                           float* out, int64_t ldo, int32_t n_out, int64_t rows, const void* wq, int64_t wq_bytes,
                                           const float* b1, const float* b0, int32_t chain, int32_t* sched, void* stream) {
-  CPPF_CHECK_ARG(B > 0 && pts && normals && idx && pt_off && tup_off && table && out && wq && b1 && b0 && rows >= 0);
-  CPPF_CHECK_ARG(fdim >= 8 && (fdim & (fdim - 1)) == 0 && (ldo & 3) == 0 && ldo >= n_out && chain >= 0 && chain <= 15);
-  CPPF_CHECK_ARG((((uintptr_t)table | (uintptr_t)out | (uintptr_t)wq) & 15) == 0);
-  if (k != 5 || n_out != 128) {
-    snprintf(g_cppf_err, sizeof(g_cppf_err), "cppf_reslayer_split_encode: k = %d, n_out = %d (the kernel builds the 40 pair features of "
-             "5-point tuples for the 128-wide projection layer of the tuple encoder)", k, n_out);
-    return CPPF_EUNSUPPORTED;
-  }
-  const int k_in = 40 + k * fdim;
-  CPPF_CHECK_ARG(wq_bytes == cppf_reslayer_split_stream_bytes(k_in, n_out, 1, chain));
-  if (rows == 0) return CPPF_OK;
-  RsGather ga;
-  ga.gidx = idx;
-  ga.table = table;
-  ga.slots = k;
-  ga.head = 40;
-  ga.fshift = __builtin_ctz((unsigned)fdim);
-  ga.pts = pts;
-  ga.nrm = normals;
-  ga.pt_off = pt_off;
-  ga.tup_off = tup_off;
-  ga.B = B;
-  ga.sched = sched;
-  return rs_launch<4, true, true, false, 3, RS_ENCODE>(nullptr, 0, k_in, out, ldo, rows, static_cast<const char*>(wq), b1, b0, chain,
-                                                       rs_cus(), (hipStream_t)stream, ga);
+  RsRequest r = rs_request(__func__, 3, RsForm::encode, nullptr, 0, 40, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, sched,
+                           stream);
+  r.ga.gidx = idx;
+  r.ga.table = table;
+  r.ga.slots = k;
+  r.ga.pts = pts;
+  r.ga.nrm = normals;
+  r.ga.pt_off = pt_off;
+  r.ga.tup_off = tup_off;
+  r.ga.B = B;
+  r.fdim = fdim;
+  return rs_submit(r);
 }
 
 // The output layer of the logit head (train_shot.py:62-66: a 192-wide projection ResLayer = 6 coordinates x 32 bins) with the
@@ -1253,27 +1278,14 @@ extern "C" int cppf_reslayer_split_decode_prior(const float* x, int64_t ldx, int
                                                 const float* b1, const float* b0, const float* logit_prior, const float* prior_pos,
                                                 float prior_inv_sigma, const float* uniforms, int32_t* bins, int32_t* sched,
                                                 void* stream) {
-  CPPF_CHECK_ARG(x && wq && b1 && b0 && uniforms && bins && rows >= 0);
-  CPPF_CHECK_ARG(!(logit_prior && prior_pos) && (!prior_pos || (prior_inv_sigma > 0.0f && prior_inv_sigma < INFINITY)));
-  CPPF_CHECK_ARG(k_in > 0 && (k_in & 7) == 0 && ldx >= k_in && (ldx & 3) == 0);
-  CPPF_CHECK_ARG((((uintptr_t)x | (uintptr_t)wq | (uintptr_t)logit_prior) & 15) == 0);
-  CPPF_CHECK_ARG(wq_bytes == cppf_reslayer_split_stream_bytes(k_in, 192, 1, 0));
-  if (rows == 0) return CPPF_OK;
-  int dev = 0, n_cu = 0;
-  CPPF_HIP(hipGetDevice(&dev));
-  CPPF_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  RsDecode dc;
-  dc.prior = logit_prior;
-  dc.prior_pos = prior_pos;
-  dc.prior_inv_sigma = prior_pos ? prior_inv_sigma : 0.0f;
-  dc.uniforms = uniforms;
-  dc.bins = bins;
-  RsGather ga;
-  ga.sched = sched;
-  return rs_launch<6, true, false, true>(x, ldx, k_in, nullptr, 192, rows, static_cast<const char*>(wq), b1, b0, 0,
-                                         n_cu > 0 ? n_cu : 256, (hipStream_t)stream, ga, dc);
+  RsRequest r = rs_request(__func__, 3, RsForm::decode, x, ldx, k_in, nullptr, 0, 192, rows, wq, wq_bytes, b1, b0, 0, sched, stream);
+  r.dc.prior = logit_prior;
+  r.dc.prior_pos = prior_pos;
+  r.dc.prior_inv_sigma = prior_inv_sigma;
+  r.dc.uniforms = uniforms;
+  r.dc.bins = bins;
+  return rs_submit(r);
 }
-
 
 // the stable form: the reference draws from the network's own logits (eval.py:225-229)
 extern "C" int cppf_reslayer_split_decode(const float* x, int64_t ldx, int32_t k_in, int64_t rows, const void* wq, int64_t wq_bytes,
@@ -1282,7 +1294,6 @@ extern "C" int cppf_reslayer_split_decode(const float* x, int64_t ldx, int32_t k
   return cppf_reslayer_split_decode_prior(x, ldx, k_in, rows, wq, wq_bytes, b1, b0, nullptr, nullptr, 0.0f, uniforms, bins, sched, stream);
 }
 
-
 // A plain nn.Linear on the matrix cores in the same split arithmetic: out[rows, n_out] = x[rows, :k_in] W^T + bias (bias may be
 // NULL).  The DINO model's per-point transforms (train_dino.py:86-87: desc_transform over [N, 1024]; desc_pair_transform's
 // slices, folded with the first ResLayer's weights into per-point slot tables, see cppf_reslayer_split_sumgather) run through
@@ -1290,19 +1301,13 @@ extern "C" int cppf_reslayer_split_decode(const float* x, int64_t ldx, int32_t k
 // x each), k_in a multiple of 8; x / out as cppf_reslayer_split.  wq = cppf_linear_split_stream_bytes(k_in, n_out) bytes: per
 // column group the first-product segment of pack_split for that group's 256 rows of W (cppf2_amd.models.pack_linear).
 extern "C" int64_t cppf_linear_split_stream_bytes(int32_t k_in, int32_t n_out) {
-  if (k_in <= 0 || n_out <= 0 || (n_out & 255) != 0) return -1;
-  return (int64_t)((k_in + 15) / 16) * (n_out / 32) * rs_tile_bytes(3);
+  return rs_linear_stream_bytes(k_in, n_out, 3);
 }
 
 extern "C" int cppf_linear_split(const float* x, int64_t ldx, int32_t k_in, float* out, int64_t ldo, int32_t n_out, int64_t rows,
                                  const void* wq, int64_t wq_bytes, const float* bias, void* stream) {
-  CPPF_CHECK_ARG(x && out && wq && rows >= 0);
-  CPPF_CHECK_ARG(k_in > 0 && (k_in & 7) == 0 && ldx >= k_in && (ldx & 3) == 0 && n_out > 0 && (n_out & 255) == 0 && ldo >= n_out && (ldo & 3) == 0);
-  CPPF_CHECK_ARG((((uintptr_t)x | (uintptr_t)out | (uintptr_t)wq) & 15) == 0);
-  CPPF_CHECK_ARG(wq_bytes == cppf_linear_split_stream_bytes(k_in, n_out));
-  if (rows == 0) return CPPF_OK;
-  return rs_launch<8, false, false, false, 3, RS_LINEAR>(x, ldx, k_in, out, ldo, rows, static_cast<const char*>(wq), bias, nullptr,
-                                                         n_out / 256, rs_cus(), (hipStream_t)stream);
+  return rs_submit(rs_request(__func__, 3, RsForm::linear, x, ldx, k_in, out, ldo, n_out, rows, wq, wq_bytes, bias, nullptr, 0,
+                              nullptr, stream));
 }
 
 // The first ResLayer of a tuple encoder (a 128-wide projection layer, + `chain` identity layers) whose input row is
@@ -1320,28 +1325,14 @@ extern "C" int cppf_reslayer_split_sumgather(const float* heads, int64_t ld_head
                                              int32_t slots, const float* tables, int64_t ld_tables, float* out, int64_t ldo,
                                              int32_t n_out, int64_t rows, const void* wq, int64_t wq_bytes, const float* b1,
                                              const float* b0, int32_t chain, int32_t* sched, void* stream) {
-  CPPF_CHECK_ARG(heads && gidx && tables && out && wq && b1 && b0 && rows >= 0);
-  CPPF_CHECK_ARG(head_cols > 0 && (head_cols & 7) == 0 && ld_heads >= head_cols && (ld_heads & 3) == 0);
-  CPPF_CHECK_ARG(slots >= 1 && slots <= 8 && ld_tables >= (int64_t)slots * 256 && (ld_tables & 3) == 0);
-  CPPF_CHECK_ARG((ldo & 3) == 0 && ldo >= n_out && chain >= 0 && chain <= 15);
-  CPPF_CHECK_ARG((((uintptr_t)heads | (uintptr_t)tables | (uintptr_t)out | (uintptr_t)wq) & 15) == 0);
-  CPPF_CHECK_ARG(wq_bytes == cppf_reslayer_split_stream_bytes(head_cols, n_out, 1, chain));
-  if (n_out != 128) {
-    snprintf(g_cppf_err, sizeof(g_cppf_err), "cppf_reslayer_split_sumgather: n_out = %d (only the 128-wide projection layer of the "
-             "tuple encoders has this kernel)", n_out);
-    return CPPF_EUNSUPPORTED;
-  }
-  if (rows == 0) return CPPF_OK;
-  RsGather ga;
-  ga.gidx = gidx;
-  ga.table = tables;
-  ga.slots = slots;
-  ga.tld = ld_tables;
-  ga.sched = sched;
-  return rs_launch<4, true, false, false, 3, RS_SUMGATHER>(heads, ld_heads, head_cols, out, ldo, rows, static_cast<const char*>(wq), b1, b0,
-                                                           chain, rs_cus(), (hipStream_t)stream, ga);
+  RsRequest r = rs_request(__func__, 3, RsForm::sumgather, heads, ld_heads, head_cols, out, ldo, n_out, rows, wq, wq_bytes, b1, b0,
+                           chain, sched, stream);
+  r.ga.gidx = gidx;
+  r.ga.table = tables;
+  r.ga.slots = slots;
+  r.ga.tld = ld_tables;
+  return rs_submit(r);
 }
-
 
 // cppf_reslayer_split_sumgather with the coordinate columns built inside the kernel (RS_SUMENCODE): the DINO model's
 // prepare_tuple_inputs (train_dino.py:91-97) + its tuple encoder's first launch with no per-tuple array in between.  pts float32
@@ -1351,28 +1342,17 @@ extern "C" int cppf_reslayer_split_sumencode(int B, const float* pts, const int3
                                              const int32_t* tup_off, const float* tables, int64_t ld_tables, float* out, int64_t ldo,
                                              int32_t n_out, int64_t rows, const void* wq, int64_t wq_bytes, const float* b1,
                                              const float* b0, int32_t chain, int32_t* sched, void* stream) {
-  CPPF_CHECK_ARG(B > 0 && pts && idx && pt_off && tup_off && tables && out && wq && b1 && b0 && rows >= 0);
-  CPPF_CHECK_ARG(ld_tables >= (int64_t)k * 256 && (ld_tables & 3) == 0 && (ldo & 3) == 0 && ldo >= n_out && chain >= 0 && chain <= 15);
-  CPPF_CHECK_ARG((((uintptr_t)tables | (uintptr_t)out | (uintptr_t)wq) & 15) == 0);
-  if (k != 5 || n_out != 128) {
-    snprintf(g_cppf_err, sizeof(g_cppf_err), "cppf_reslayer_split_sumencode: k = %d, n_out = %d (5-point tuples, the 128-wide projection "
-             "layer of the tuple encoder)", k, n_out);
-    return CPPF_EUNSUPPORTED;
-  }
-  CPPF_CHECK_ARG(wq_bytes == cppf_reslayer_split_stream_bytes(32, n_out, 1, chain));
-  if (rows == 0) return CPPF_OK;
-  RsGather ga;
-  ga.gidx = idx;
-  ga.table = tables;
-  ga.slots = k;
-  ga.tld = ld_tables;
-  ga.pts = pts;
-  ga.pt_off = pt_off;
-  ga.tup_off = tup_off;
-  ga.B = B;
-  ga.sched = sched;
-  return rs_launch<4, true, false, false, 3, RS_SUMENCODE>(nullptr, 0, 32, out, ldo, rows, static_cast<const char*>(wq), b1, b0, chain,
-                                                           rs_cus(), (hipStream_t)stream, ga);
+  RsRequest r = rs_request(__func__, 3, RsForm::sumencode, nullptr, 0, 32, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, sched,
+                           stream);
+  r.ga.gidx = idx;
+  r.ga.table = tables;
+  r.ga.slots = k;
+  r.ga.tld = ld_tables;
+  r.ga.pts = pts;
+  r.ga.pt_off = pt_off;
+  r.ga.tup_off = tup_off;
+  r.ga.B = B;
+  return rs_submit(r);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1382,105 +1362,32 @@ extern "C" int64_t cppf_reslayer_split16_stream_bytes(int32_t k_in, int32_t n_ou
   return rs_stream_bytes(k_in, n_out, proj, chain, 2);
 }
 
-static RsGather rs16_gather(const CppfReslayerSplit16Args& a) {      // no gather: only the scheduling counters
-  RsGather ga;
-  ga.sched = a.sched;
-  return ga;
-}
-
-template <int NT, bool PROJ>
-static int rs16_plain(const CppfReslayerSplit16Args& a, int n_cu, RsTap tap) {
-  return rs_launch<NT, PROJ, false, false, 2>(a.x, a.ldx, a.k_in, a.out, a.ldo, a.rows, static_cast<const char*>(a.wq), a.b1, a.b0,
-                                              a.chain, n_cu, (hipStream_t)a.stream, rs16_gather(a), RsDecode(), tap, a.weight_scale);
-}
-
-// The ResLayer launch of cppf_reslayer_split / _tap / _gather / _decode in f16x2 arithmetic (see the kernel's comment): wq =
-// the fp16 (hi, lo) pairs of weight_scale x the weights in the same fragment order (cppf2_amd.models.pack_split(arith="f16x2");
-// cppf_reslayer_split16_stream_bytes bytes), b1 / b0 = weight_scale x the biases, weight_scale a power of two.  Exactly one of
-// {plain, gather (gidx != NULL; x = heads, k_in = head columns), decode (uniforms != NULL)} ; first_out (tap) only with plain.
+// The ResLayer launch of cppf_reslayer_split / _tap / _gather / _decode / cppf_linear_split (mode 1) / _sumgather (mode 2) in
+// f16x2 arithmetic (see the kernel's comment): wq = the fp16 (hi, lo) pairs of weight_scale x the weights in the same fragment
+// order (cppf2_amd.models.pack_split(arith="f16x2"); cppf_reslayer_split16_stream_bytes bytes), b1 / b0 = weight_scale x the
+// biases, weight_scale a power of two.  Mode 0: exactly one of {plain, gather (gidx != NULL; x = heads, k_in = head columns),
+// decode (uniforms != NULL)}; first_out (tap) only with plain.
 extern "C" int cppf_reslayer_split16(const CppfReslayerSplit16Args* args) {
   CPPF_CHECK_ARG(args != nullptr);
   const CppfReslayerSplit16Args& a = *args;
-  CPPF_CHECK_ARG(a.x && a.wq && (a.b1 || a.mode == 1) && a.rows >= 0 && a.chain >= 0 && a.chain <= 15);
-  {
-    int e = 0;
-    CPPF_CHECK_ARG(a.weight_scale > 0.0f && frexpf(a.weight_scale, &e) == 0.5f);        // a power of two
-  }
-  CPPF_CHECK_ARG((((uintptr_t)a.x | (uintptr_t)a.out | (uintptr_t)a.wq | (uintptr_t)a.first_out | (uintptr_t)a.table |
-                   (uintptr_t)a.logit_prior) & 15) == 0);
-  CPPF_CHECK_ARG((a.ldx & 3) == 0 && (a.ldo & 3) == 0 && (a.ld_first & 3) == 0);
-  const bool gather = a.gidx != nullptr, decode = a.uniforms != nullptr, proj = a.b0 != nullptr;
-  CPPF_CHECK_ARG(!(gather && decode) && !((gather || decode) && a.first_out));
-  CPPF_CHECK_ARG(a.mode == 0 || (a.mode == 1 && !gather && !decode && !proj && !a.first_out) || (a.mode == 2 && gather));
-  if (a.rows == 0) return CPPF_OK;
-  int dev = 0, n_cu = 0;
-  CPPF_HIP(hipGetDevice(&dev));
-  CPPF_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  if (n_cu <= 0) n_cu = 256;
-  const char* w = static_cast<const char*>(a.wq);
-  hipStream_t st = (hipStream_t)a.stream;
-  if (a.mode == 1) {                             // plain Linear (cppf_linear_split): b1 = weight_scale x the bias or NULL
-    CPPF_CHECK_ARG(a.out && a.k_in > 0 && (a.k_in & 7) == 0 && a.ldx >= a.k_in && a.n_out > 0 && (a.n_out & 255) == 0 && a.ldo >= a.n_out);
-    CPPF_CHECK_ARG(a.wq_bytes == (int64_t)((a.k_in + 15) / 16) * (a.n_out / 32) * rs_tile_bytes(2));
-    return rs_launch<8, false, false, false, 2, RS_LINEAR>(a.x, a.ldx, a.k_in, a.out, a.ldo, a.rows, w, a.b1, nullptr, a.n_out / 256, n_cu,
-                                                           st, RsGather(), RsDecode(), RsTap(), a.weight_scale);
-  }
-  if (a.mode == 2) {                             // per-point slot tables summed into the accumulators (cppf_reslayer_split_sumgather)
-    CPPF_CHECK_ARG(a.table && proj && a.out && a.n_out == 128 && a.ldo >= 128);
-    CPPF_CHECK_ARG(a.k_in > 0 && (a.k_in & 7) == 0 && a.ldx >= a.k_in);
-    CPPF_CHECK_ARG(a.slots >= 1 && a.slots <= 8 && a.ld_table >= (int64_t)a.slots * 256 && (a.ld_table & 3) == 0);
-    CPPF_CHECK_ARG(a.wq_bytes == rs_stream_bytes(a.k_in, 128, 1, a.chain, 2));
-    RsGather ga;
-    ga.gidx = a.gidx;
-    ga.table = a.table;
-    ga.slots = a.slots;
-    ga.tld = a.ld_table;
-    ga.sched = a.sched;
-    return rs_launch<4, true, false, false, 2, RS_SUMGATHER>(a.x, a.ldx, a.k_in, a.out, a.ldo, a.rows, w, a.b1, a.b0, a.chain, n_cu, st, ga,
-                                                             RsDecode(), RsTap(), a.weight_scale);
-  }
-  if (gather) {
-    CPPF_CHECK_ARG(a.table && proj && a.out && a.n_out == 128 && a.ldo >= 128);
-    CPPF_CHECK_ARG(a.k_in >= 0 && (a.k_in & 7) == 0 && (a.k_in == 0 || a.ldx >= a.k_in));
-    CPPF_CHECK_ARG(a.slots >= 1 && a.slots <= 8 && a.fdim >= 8 && (a.fdim & (a.fdim - 1)) == 0);
-    const int k_tot = a.k_in + a.slots * a.fdim;
-    CPPF_CHECK_ARG(a.wq_bytes == rs_stream_bytes(k_tot, 128, 1, a.chain, 2));
-    RsGather ga;
-    ga.gidx = a.gidx;
-    ga.table = a.table;
-    ga.slots = a.slots;
-    ga.head = a.k_in;
-    ga.fshift = __builtin_ctz((unsigned)a.fdim);
-    ga.sched = a.sched;
-    return rs_launch<4, true, true, false, 2>(a.x, a.ldx, k_tot, a.out, a.ldo, a.rows, w, a.b1, a.b0, a.chain, n_cu, st, ga,
-                                              RsDecode(), RsTap(), a.weight_scale);
-  }
-  CPPF_CHECK_ARG(a.k_in > 0 && (a.k_in & 7) == 0 && a.ldx >= a.k_in);
-  if (decode) {
-    CPPF_CHECK_ARG(proj && a.bins && a.chain == 0 && a.wq_bytes == rs_stream_bytes(a.k_in, 192, 1, 0, 2));
-    RsDecode dc;
-    CPPF_CHECK_ARG(!(a.logit_prior && a.prior_pos) && (!a.prior_pos || (a.prior_inv_sigma > 0.0f && a.prior_inv_sigma < INFINITY)));
-    dc.prior = a.logit_prior;
-    dc.prior_pos = a.prior_pos;
-    dc.prior_inv_sigma = a.prior_pos ? a.prior_inv_sigma : 0.0f;
-    dc.uniforms = a.uniforms;
-    dc.bins = a.bins;
-    return rs_launch<6, true, false, true, 2>(a.x, a.ldx, a.k_in, nullptr, 192, a.rows, w, a.b1, a.b0, 0, n_cu, st, rs16_gather(a), dc,
-                                              RsTap(), a.weight_scale);
-  }
-  CPPF_CHECK_ARG(a.out && (a.n_out == 64 || a.n_out == 128 || a.n_out == 192 || a.n_out == 256) && a.ldo >= a.n_out);
-  CPPF_CHECK_ARG(proj || a.k_in == a.n_out);
-  CPPF_CHECK_ARG(a.wq_bytes == rs_stream_bytes(a.k_in, a.n_out, proj, a.chain, 2));
-  RsTap tap;
-  if (a.first_out) {
-    CPPF_CHECK_ARG(a.first_out != a.out && a.first_out != a.x && a.ld_first >= a.n_out);
-    tap.out = a.first_out;
-    tap.ld = a.ld_first;
-  }
-  switch (a.n_out / 32) {
-    case 2: return proj ? rs16_plain<2, true>(a, n_cu, tap) : rs16_plain<2, false>(a, n_cu, tap);
-    case 4: return proj ? rs16_plain<4, true>(a, n_cu, tap) : rs16_plain<4, false>(a, n_cu, tap);
-    case 6: return proj ? rs16_plain<6, true>(a, n_cu, tap) : rs16_plain<6, false>(a, n_cu, tap);
-    default: return proj ? rs16_plain<8, true>(a, n_cu, tap) : rs16_plain<8, false>(a, n_cu, tap);
-  }
+  const bool gather = a.gidx != nullptr, decode = a.uniforms != nullptr;
+  CPPF_CHECK_ARG(!(gather && decode) && (a.mode == 0 || (a.mode == 1 && !gather && !decode) || (a.mode == 2 && gather)));
+  const RsForm form = a.mode == 1 ? RsForm::linear : a.mode == 2 ? RsForm::sumgather
+                      : gather ? RsForm::gather : decode ? RsForm::decode : RsForm::plain;
+  RsRequest r = rs_request(__func__, 2, form, a.x, a.ldx, a.k_in, a.out, a.ldo, a.n_out, a.rows, a.wq, a.wq_bytes, a.b1, a.b0, a.chain,
+                           a.sched, a.stream);
+  r.weight_scale = a.weight_scale;
+  r.fdim = a.fdim;
+  r.ga.gidx = a.gidx;
+  r.ga.table = a.table;
+  r.ga.slots = a.slots;
+  r.ga.tld = a.ld_table;
+  r.dc.prior = a.logit_prior;
+  r.dc.prior_pos = a.prior_pos;
+  r.dc.prior_inv_sigma = a.prior_inv_sigma;
+  r.dc.uniforms = a.uniforms;
+  r.dc.bins = a.bins;
+  r.tap.out = a.first_out;
+  r.tap.ld = a.ld_first;
+  return rs_submit(r);
 }

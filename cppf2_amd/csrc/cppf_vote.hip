@@ -1,7 +1,6 @@
 // cppf_vote.hip -- centre Hough vote + first-max, back-vote filter, rotation vote + sphere bins,
 // pose assembly.  gfx950 only.  See include/cppf_hip.h for the contract of each entry point.
 #include "cppf_common.h"
-#include <mutex>
 
 // =============================================================================================
 // a6. vote_center (train_dino.py:171-215)
@@ -849,26 +848,13 @@ extern "C" int cppf_vote_center(int B, const float* pts, const int32_t* pt_off, 
       if (P < 1) P = 1;
     }
     const int lds_bytes = VC_LDS_WORDS * 4;
-    // per device, on first use: the kernels' dynamic-LDS limit and the CU count (written once under a lock, read-only
-    // afterwards -- the library keeps no other state, see cppf_hip.h)
-    static std::mutex cu_mutex;
-    static int cu_count[64] = {0};
-    int dev = 0;
-    CPPF_HIP(hipGetDevice(&dev));
-    const int dslot = dev & 63;
-    {
-      std::lock_guard<std::mutex> lock(cu_mutex);
-      if (cu_count[dslot] == 0) {
-        hipDeviceProp_t prop;
-        CPPF_HIP(hipGetDeviceProperties(&prop, dev));
-        const void* fns[] = {(const void*)vote_center_slab_kernel<true, false>, (const void*)vote_center_slab_kernel<true, true>,
-                             (const void*)vote_center_slab_kernel<false, false>, (const void*)vote_center_slab_kernel<false, true>,
-                             (const void*)vote_center_persist_kernel<false>, (const void*)vote_center_persist_kernel<true>};
-        for (const void* f : fns) CPPF_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        cu_count[dslot] = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-      }
-    }
-    const int num_cus = cu_count[dslot];
+    // per device, on first use: the kernels' dynamic-LDS limit (cppf_common.h)
+    int dev = 0, num_cus = 0;
+    CPPF_TRY(cppf_device_cus(&dev, &num_cus));
+    const void* fns[] = {(const void*)vote_center_slab_kernel<true, false>, (const void*)vote_center_slab_kernel<true, true>,
+                         (const void*)vote_center_slab_kernel<false, false>, (const void*)vote_center_slab_kernel<false, true>,
+                         (const void*)vote_center_persist_kernel<false>, (const void*)vote_center_persist_kernel<true>};
+    for (const void* f : fns) CPPF_TRY(cppf_allow_dynamic_lds(f, dev, lds_bytes));
     // arcs need >1 slab to pay off and the table in LDS; mode 3 forces the exhaustive sweep (A/B reference)
     const bool arcs = (exhaustive == 0) && s_max > 1 && num_rots <= VC_MAX_LDS_ROTS && num_rots >= 8;
     // the persistent work-list kernel serves every batch size of the arcs path; the one-item-per-workgroup launch

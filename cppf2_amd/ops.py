@@ -365,12 +365,20 @@ def reslayer_split16_supported(k_in, n_out, proj, chain=0):
     return k_in % 8 == 0 and _L.cppf_reslayer_split16_stream_bytes(int(k_in), int(n_out), int(bool(proj)), int(chain)) > 0
 
 
+def _split16(what, wq, scale, **fields):
+    """One cppf_reslayer_split16 launch: the CppfReslayerSplit16Args of `fields` (pointers as ints, unset members zero) with the
+    stream, the weight stream and its scale filled in."""
+    from ._lib import ReslayerSplit16Args
+    a = ReslayerSplit16Args(wq=wq.data_ptr(), wq_bytes=wq.numel() * wq.element_size(), weight_scale=float(scale),
+                            stream=torch.cuda.current_stream().cuda_stream, **fields)
+    _lib.check(_L.cppf_reslayer_split16(C.byref(a)), what)
+
+
 def reslayer_split16(x, wq, b1, b0, n_out, scale, out=None, chain=0, tap=None, gather=None, decode=None):
     """The ResLayer launches of reslayer_split / _gather / _decode in f16x2 arithmetic (cppf_reslayer_split16; not the default):
     wq = models.pack_split(..., arith="f16x2", scale=scale), b1 / b0 = scale x the biases (scale a power of two).
     gather = (gidx int32 [rows, k], table float32 [points, F]): x are the head columns; decode = (uniforms, prior | None, bins)."""
-    from ._lib import ReslayerSplit16Args
-    a = ReslayerSplit16Args()
+    a = {}
     b1 = b1.contiguous()
     b0 = None if b0 is None else b0.contiguous()
     keep = [b1, b0]
@@ -378,43 +386,34 @@ def reslayer_split16(x, wq, b1, b0, n_out, scale, out=None, chain=0, tap=None, g
         gidx, table = gather
         rows = gidx.shape[0]
         heads = x
-        a.x = heads.data_ptr() if heads.shape[1] else table.data_ptr()
-        a.ldx = heads.stride(0) if heads.shape[1] else 0
-        a.k_in = heads.shape[1]
-        a.gidx, a.slots, a.table, a.fdim = gidx.data_ptr(), gidx.shape[1], table.data_ptr(), table.shape[1]
+        a.update(x=heads.data_ptr() if heads.shape[1] else table.data_ptr(), ldx=heads.stride(0) if heads.shape[1] else 0,
+                 k_in=heads.shape[1], gidx=gidx.data_ptr(), slots=gidx.shape[1], table=table.data_ptr(), fdim=table.shape[1])
         out = torch.empty((rows, n_out), dtype=torch.float32, device=table.device)
     else:
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
         rows = x.shape[0]
-        a.x, a.ldx, a.k_in = x.data_ptr(), x.stride(0), x.shape[1]
+        a.update(x=x.data_ptr(), ldx=x.stride(0), k_in=x.shape[1])
     if decode is not None:
         uniforms, prior, bins = decode
         uniforms = uniforms.contiguous()
         if isinstance(prior, BinPrior):
-            a.prior_pos, a.prior_inv_sigma = prior.pos.data_ptr(), prior.inv_sigma
+            a.update(prior_pos=prior.pos.data_ptr(), prior_inv_sigma=prior.inv_sigma)
             keep.append(prior.pos)
             prior = None
         prior = None if prior is None else prior.contiguous()
         if bins is None:
             bins = torch.empty((rows, 6), dtype=torch.int32, device=x.device)
-        a.uniforms, a.bins = uniforms.data_ptr(), bins.data_ptr()
-        a.logit_prior = None if prior is None else prior.data_ptr()
+        a.update(uniforms=uniforms.data_ptr(), bins=bins.data_ptr(), logit_prior=None if prior is None else prior.data_ptr())
         keep += [uniforms, prior]
         n_out = 192
     else:
         if out is None:
             out = x if b0 is None else torch.empty((rows, n_out), dtype=torch.float32, device=x.device)
-        a.out, a.ldo = out.data_ptr(), out.stride(0)
+        a.update(out=out.data_ptr(), ldo=out.stride(0))
     if tap is not None:
-        a.first_out, a.ld_first = tap.data_ptr(), tap.stride(0)
-    a.n_out, a.rows, a.chain = int(n_out), int(rows), int(chain)
-    a.wq, a.wq_bytes = wq.data_ptr(), wq.numel() * wq.element_size()
-    a.b1 = b1.data_ptr()
-    a.b0 = None if b0 is None else b0.data_ptr()
-    a.weight_scale = float(scale)
-    a.stream = torch.cuda.current_stream().cuda_stream
-    a.sched = _sched().value
-    _lib.check(_L.cppf_reslayer_split16(C.byref(a)), "cppf_reslayer_split16")
+        a.update(first_out=tap.data_ptr(), ld_first=tap.stride(0))
+    _split16("cppf_reslayer_split16", wq, scale, n_out=int(n_out), rows=int(rows), chain=int(chain), b1=b1.data_ptr(),
+             b0=None if b0 is None else b0.data_ptr(), sched=_sched().value, **a)
     return bins if decode is not None else out
 
 
@@ -624,15 +623,8 @@ def linear_split(x, wq, bias, n_out, out=None, scale=None):
     assert out.dtype == torch.float32 and out.shape == (rows, n_out) and out.stride(1) == 1
     bias = None if bias is None else bias.contiguous()
     if scale is not None:
-        from ._lib import ReslayerSplit16Args
-        a = ReslayerSplit16Args()
-        a.x, a.ldx, a.k_in = x.data_ptr(), x.stride(0), k_in
-        a.out, a.ldo, a.n_out, a.rows = out.data_ptr(), out.stride(0), int(n_out), int(rows)
-        a.wq, a.wq_bytes = wq.data_ptr(), wq.numel() * wq.element_size()
-        a.b1 = None if bias is None else bias.data_ptr()
-        a.weight_scale, a.mode = float(scale), 1
-        a.stream = torch.cuda.current_stream().cuda_stream
-        _lib.check(_L.cppf_reslayer_split16(C.byref(a)), "cppf_reslayer_split16(linear)")
+        _split16("cppf_reslayer_split16(linear)", wq, scale, mode=1, x=x.data_ptr(), ldx=x.stride(0), k_in=k_in, out=out.data_ptr(),
+                 ldo=out.stride(0), n_out=int(n_out), rows=int(rows), b1=None if bias is None else bias.data_ptr())
         return out
     _lib.check(_L.cppf_linear_split(_p(x), x.stride(0), k_in, _p(out), out.stride(0), int(n_out), rows, _p(wq),
                                     wq.numel() * wq.element_size(), _p(bias), _stream()), "cppf_linear_split")
@@ -672,17 +664,10 @@ def reslayer_split_sumgather(heads, gidx, tables, wq, b1, b0, n_out, chain=0, sc
     b0 = b0.contiguous()
     assert b1.numel() == (1 + chain) * n_out
     if scale is not None:
-        from ._lib import ReslayerSplit16Args
-        a = ReslayerSplit16Args()
-        a.x, a.ldx, a.k_in = heads.data_ptr(), heads.stride(0), heads.shape[1]
-        a.out, a.ldo, a.n_out, a.rows, a.chain = out.data_ptr(), out.stride(0), int(n_out), int(rows), int(chain)
-        a.wq, a.wq_bytes = wq.data_ptr(), wq.numel() * wq.element_size()
-        a.b1, a.b0 = b1.data_ptr(), b0.data_ptr()
-        a.gidx, a.slots, a.table, a.ld_table = gidx.data_ptr(), int(slots), tables.data_ptr(), tables.stride(0)
-        a.weight_scale, a.mode = float(scale), 2
-        a.stream = torch.cuda.current_stream().cuda_stream
-        a.sched = _sched().value
-        _lib.check(_L.cppf_reslayer_split16(C.byref(a)), "cppf_reslayer_split16(sumgather)")
+        _split16("cppf_reslayer_split16(sumgather)", wq, scale, mode=2, x=heads.data_ptr(), ldx=heads.stride(0), k_in=heads.shape[1],
+                 out=out.data_ptr(), ldo=out.stride(0), n_out=int(n_out), rows=int(rows), chain=int(chain), b1=b1.data_ptr(),
+                 b0=b0.data_ptr(), gidx=gidx.data_ptr(), slots=int(slots), table=tables.data_ptr(), ld_table=tables.stride(0),
+                 sched=_sched().value)
         return out
     _lib.check(_L.cppf_reslayer_split_sumgather(_p(heads), heads.stride(0), heads.shape[1], _p(gidx), slots, _p(tables),
                                                 tables.stride(0), _p(out), out.stride(0), n_out, rows, _p(wq),

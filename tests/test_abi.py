@@ -168,3 +168,289 @@ def test_no_kernel_of_the_library_uses_scratch_memory(tmp_path):
             elif name is not None:
                 assert int(m.group(2)) == 0, "%s: %s = %s" % (name, m.group(1), m.group(2))
     assert kernels >= 60
+
+
+def _untraced_lib():
+    """The CDLL itself: calls through it are not recorded in _lib.CALLED (tests/test_zz_stable_abi_coverage_gpu.py counts what
+    the GPU tests really ran)."""
+    from cppf2_amd import _lib
+    lib = _lib.load()
+    return lib._lib if isinstance(lib, _lib._Traced) else lib
+
+
+# fake device addresses, 16-byte aligned and never dereferenced: validation and the rows == 0 return come before any device work
+_X, _OUT, _WQ, _B1, _B0, _TAB, _IDX, _AUX, _AUX2, _TAP = (0x100000 * (i + 1) for i in range(10))
+_OK, _EINVAL, _EUNSUPPORTED = 0, -1, -2
+
+
+def _sb(k_in, n_out, proj, chain, pc=3):
+    lib = _untraced_lib()
+    fn = lib.cppf_reslayer_split_stream_bytes if pc == 3 else lib.cppf_reslayer_split16_stream_bytes
+    return fn(k_in, n_out, proj, chain)
+
+
+def _call_plain(lib, x=_X, ldx=64, k_in=64, out=_OUT, ldo=128, n_out=128, rows=0, wq=_WQ, wq_bytes=None, b1=_B1, b0=_B0, chain=0):
+    if wq_bytes is None:
+        wq_bytes = _sb(k_in, n_out, b0 is not None, chain)
+    return lib.cppf_reslayer_split(x, ldx, k_in, out, ldo, n_out, rows, wq, wq_bytes, b1, b0, chain, None, None)
+
+
+def _call_tap(lib, first=_TAP, ld_first=128, x=_X, out=_OUT, n_out=128, rows=0):
+    wq_bytes = _sb(64, n_out, 1, 1)
+    return lib.cppf_reslayer_split_tap(x, 64, 64, first, ld_first, out, 128, n_out, rows, _WQ, wq_bytes, _B1, _B0, 1, None, None)
+
+
+def _call_gather(lib, head_cols=40, ld_heads=40, slots=5, fdim=32, table=_TAB, ldo=128, n_out=128, rows=0, b0=_B0, wq_bytes=None,
+                 chain=0):
+    if wq_bytes is None:
+        wq_bytes = _sb(head_cols + slots * fdim, n_out, 1, chain)
+    return lib.cppf_reslayer_split_gather(_X, ld_heads, head_cols, _IDX, slots, table, fdim, _OUT, ldo, n_out, rows, _WQ, wq_bytes,
+                                          _B1, b0, chain, None, None)
+
+
+def _call_encode(lib, B=2, pts=_AUX, normals=_AUX2, idx=_IDX, k=5, pt_off=_AUX, tup_off=_AUX2, fdim=32, out=_OUT, ldo=128, n_out=128,
+                 rows=0, wq_bytes=None):
+    if wq_bytes is None:
+        wq_bytes = _sb(40 + 5 * fdim, 128, 1, 0)
+    return lib.cppf_reslayer_split_encode(B, pts, normals, idx, k, pt_off, tup_off, _TAB, fdim, out, ldo, n_out, rows, _WQ, wq_bytes,
+                                          _B1, _B0, 0, None, None)
+
+
+def _call_decode_prior(lib, x=_X, ldx=128, k_in=128, rows=0, b0=_B0, prior=None, prior_pos=None, sigma=0.0, uniforms=_AUX,
+                       bins=_IDX, wq_bytes=None):
+    if wq_bytes is None:
+        wq_bytes = _sb(k_in, 192, 1, 0)
+    return lib.cppf_reslayer_split_decode_prior(x, ldx, k_in, rows, _WQ, wq_bytes, _B1, b0, prior, prior_pos, sigma, uniforms, bins,
+                                                None, None)
+
+
+def _call_decode(lib, k_in=128, rows=0, wq_bytes=None, bins=_IDX):
+    if wq_bytes is None:
+        wq_bytes = _sb(k_in, 192, 1, 0)
+    return lib.cppf_reslayer_split_decode(_X, 128, k_in, rows, _WQ, wq_bytes, _B1, _B0, _AUX, bins, None, None)
+
+
+def _call_linear(lib, x=_X, ldx=64, k_in=64, ldo=256, n_out=256, rows=0, bias=None, wq_bytes=None):
+    if wq_bytes is None:
+        wq_bytes = _untraced_lib().cppf_linear_split_stream_bytes(k_in, n_out)
+    return lib.cppf_linear_split(x, ldx, k_in, _OUT, ldo, n_out, rows, _WQ, wq_bytes, bias, None)
+
+
+def _call_sumgather(lib, head_cols=32, ld_heads=32, slots=5, ld_tables=1280, tables=_TAB, n_out=128, rows=0, wq_bytes=None, chain=0):
+    if wq_bytes is None:
+        wq_bytes = _sb(head_cols, n_out, 1, chain)
+    return lib.cppf_reslayer_split_sumgather(_X, ld_heads, head_cols, _IDX, slots, tables, ld_tables, _OUT, 128, n_out, rows, _WQ,
+                                             wq_bytes, _B1, _B0, chain, None, None)
+
+
+def _call_sumencode(lib, B=2, k=5, ld_tables=1280, tables=_TAB, n_out=128, rows=0, wq_bytes=None):
+    if wq_bytes is None:
+        wq_bytes = _sb(32, n_out, 1, 0)
+    return lib.cppf_reslayer_split_sumencode(B, _AUX, _IDX, k, _AUX, _AUX2, tables, ld_tables, _OUT, 128, n_out, rows, _WQ, wq_bytes,
+                                             _B1, _B0, 0, None, None)
+
+
+def _call_reslayer128(lib, x=_X, rows=0, w1=_WQ):
+    return lib.cppf_reslayer128(x, rows, w1, _B1, _AUX, None)
+
+
+def _call_tail(lib, x=_X, ldx=64, k_in=64, n_out=3, rows=0, w0=_AUX, b0=_B0, scatter=None, valid=None, per_group=0, ldo=3):
+    return lib.cppf_reslayer_tail(x, ldx, k_in, n_out, rows, _WQ, _B1, w0, b0, _AUX2, scatter, valid, per_group, _OUT, ldo, None)
+
+
+def _call_split16(lib, **kw):
+    """cppf_reslayer_split16 on a plain projection layer (k_in 64 -> 128, one chained layer) unless kw says otherwise; the stream
+    size follows the form (gather: head + slot columns; decode: 192 outputs; mode 1: the Linear formula) unless given."""
+    from cppf2_amd._lib import ReslayerSplit16Args
+    a = dict(x=_X, ldx=64, k_in=64, out=_OUT, ldo=128, n_out=128, rows=0, wq=_WQ, b1=_B1, b0=_B0, chain=1, weight_scale=256.0)
+    a.update(kw)
+    if "wq_bytes" not in a:
+        if a.get("mode") == 1:
+            a["wq_bytes"] = _untraced_lib().cppf_linear_split_stream_bytes(a["k_in"], a["n_out"]) // 3 * 2
+        elif a.get("uniforms"):
+            a["wq_bytes"] = _sb(a["k_in"], 192, 1, 0, pc=2)
+        else:
+            k = a["k_in"] + (a.get("slots", 0) * a.get("fdim", 0) if a.get("gidx") and a.get("mode") != 2 else 0)
+            a["wq_bytes"] = _sb(k, a["n_out"], a["b0"] is not None, a["chain"], pc=2)
+    args = ReslayerSplit16Args(**a)
+    return lib.cppf_reslayer_split16(C.byref(args))
+
+
+_GATHER16 = dict(gidx=_IDX, slots=5, table=_TAB, fdim=32, k_in=40, ldx=40)
+_DECODE16 = dict(uniforms=_AUX, bins=_AUX2, out=None, ldo=0, chain=0, ldx=128, k_in=128)
+_LINEAR16 = dict(mode=1, b0=None, n_out=256, ldo=256, chain=0)
+_SUMGATHER16 = dict(mode=2, gidx=_IDX, slots=5, table=_TAB, ld_table=1280, k_in=32, ldx=32)
+
+_VALIDATION_CASES = [
+    # (entry, keyword arguments, expected return code)
+    ("plain", {}, _OK),
+    ("plain", dict(b0=None, k_in=128, ldx=128), _OK),
+    ("plain", dict(n_out=256, ldo=256, chain=3), _OK),
+    ("plain", dict(x=None), _EINVAL),
+    ("plain", dict(out=None), _EINVAL),
+    ("plain", dict(b1=None), _EINVAL),
+    ("plain", dict(rows=-1), _EINVAL),
+    ("plain", dict(k_in=60, ldx=64), _EINVAL),
+    ("plain", dict(ldx=66), _EINVAL),
+    ("plain", dict(ldx=56), _EINVAL),
+    ("plain", dict(ldo=130), _EINVAL),
+    ("plain", dict(ldo=64), _EINVAL),
+    ("plain", dict(n_out=96, ldo=96, wq_bytes=-1), _EINVAL),
+    ("plain", dict(chain=16), _EINVAL),
+    ("plain", dict(b0=None), _EINVAL),
+    ("plain", dict(x=_X + 4), _EINVAL),
+    ("plain", dict(wq=_WQ + 8), _EINVAL),
+    ("plain", dict(wq_bytes=1024), _EINVAL),
+    ("tap", {}, _OK),
+    ("tap", dict(first=None), _EINVAL),
+    ("tap", dict(first=_OUT), _EINVAL),
+    ("tap", dict(first=_X), _EINVAL),
+    ("tap", dict(ld_first=130), _EINVAL),
+    ("tap", dict(ld_first=64), _EINVAL),
+    ("tap", dict(first=_TAP + 4), _EINVAL),
+    ("gather", {}, _OK),
+    ("gather", dict(head_cols=0, ld_heads=0), _OK),
+    ("gather", dict(head_cols=36, ld_heads=40), _EINVAL),
+    ("gather", dict(ld_heads=42), _EINVAL),
+    ("gather", dict(slots=0), _EINVAL),
+    ("gather", dict(slots=9), _EINVAL),
+    ("gather", dict(fdim=24), _EINVAL),
+    ("gather", dict(fdim=4), _EINVAL),
+    ("gather", dict(table=_TAB + 4), _EINVAL),
+    ("gather", dict(b0=None), _EINVAL),
+    ("gather", dict(ldo=126), _EINVAL),
+    ("gather", dict(chain=16), _EINVAL),
+    ("gather", dict(wq_bytes=1024), _EINVAL),
+    ("gather", dict(n_out=64, ldo=64), _EUNSUPPORTED),
+    ("gather", dict(n_out=64, ldo=64, wq_bytes=1024), _EINVAL),
+    ("encode", {}, _OK),
+    ("encode", dict(B=0), _EINVAL),
+    ("encode", dict(normals=None), _EINVAL),
+    ("encode", dict(pts=None), _EINVAL),
+    ("encode", dict(idx=None), _EINVAL),
+    ("encode", dict(pt_off=None), _EINVAL),
+    ("encode", dict(tup_off=None), _EINVAL),
+    ("encode", dict(fdim=24), _EINVAL),
+    ("encode", dict(out=_OUT + 4), _EINVAL),
+    ("encode", dict(ldo=126), _EINVAL),
+    ("encode", dict(wq_bytes=1024), _EINVAL),
+    ("encode", dict(k=4), _EUNSUPPORTED),
+    ("encode", dict(k=4, wq_bytes=1024), _EUNSUPPORTED),
+    ("encode", dict(n_out=64, ldo=64), _EUNSUPPORTED),
+    ("decode_prior", {}, _OK),
+    ("decode_prior", dict(prior=_TAB), _OK),
+    ("decode_prior", dict(prior_pos=_TAB, sigma=2.0), _OK),
+    ("decode_prior", dict(x=None), _EINVAL),
+    ("decode_prior", dict(prior=_TAB, prior_pos=_TAB, sigma=2.0), _EINVAL),
+    ("decode_prior", dict(prior_pos=_TAB, sigma=0.0), _EINVAL),
+    ("decode_prior", dict(prior_pos=_TAB, sigma=float("inf")), _EINVAL),
+    ("decode_prior", dict(prior=_TAB + 4), _EINVAL),
+    ("decode_prior", dict(uniforms=None), _EINVAL),
+    ("decode_prior", dict(bins=None), _EINVAL),
+    ("decode_prior", dict(b0=None), _EINVAL),
+    ("decode_prior", dict(k_in=124, ldx=128), _EINVAL),
+    ("decode_prior", dict(ldx=130), _EINVAL),
+    ("decode_prior", dict(wq_bytes=1024), _EINVAL),
+    ("decode", {}, _OK),
+    ("decode", dict(bins=None), _EINVAL),
+    ("decode", dict(wq_bytes=1024), _EINVAL),
+    ("linear", {}, _OK),
+    ("linear", dict(bias=_B1, n_out=512, ldo=512), _OK),
+    ("linear", dict(x=None), _EINVAL),
+    ("linear", dict(n_out=128, ldo=128, wq_bytes=-1), _EINVAL),
+    ("linear", dict(k_in=12, ldx=64), _EINVAL),
+    ("linear", dict(ldo=258, n_out=256), _EINVAL),
+    ("linear", dict(ldo=252, n_out=256), _EINVAL),
+    ("linear", dict(ldx=60), _EINVAL),
+    ("linear", dict(x=_X + 4), _EINVAL),
+    ("linear", dict(wq_bytes=1024), _EINVAL),
+    ("sumgather", {}, _OK),
+    ("sumgather", dict(head_cols=0, ld_heads=0), _EINVAL),
+    ("sumgather", dict(slots=9, ld_tables=9 * 256), _EINVAL),
+    ("sumgather", dict(ld_tables=1276), _EINVAL),
+    ("sumgather", dict(ld_tables=1282), _EINVAL),
+    ("sumgather", dict(tables=_TAB + 4), _EINVAL),
+    ("sumgather", dict(chain=16), _EINVAL),
+    ("sumgather", dict(wq_bytes=1024), _EINVAL),
+    ("sumgather", dict(n_out=64), _EUNSUPPORTED),
+    ("sumgather", dict(n_out=64, wq_bytes=1024), _EINVAL),
+    ("sumencode", {}, _OK),
+    ("sumencode", dict(B=0), _EINVAL),
+    ("sumencode", dict(ld_tables=1276), _EINVAL),
+    ("sumencode", dict(tables=_TAB + 4), _EINVAL),
+    ("sumencode", dict(wq_bytes=1024), _EINVAL),
+    ("sumencode", dict(k=4), _EUNSUPPORTED),
+    ("sumencode", dict(n_out=64), _EUNSUPPORTED),
+    ("reslayer128", {}, _OK),
+    ("reslayer128", dict(x=None), _EINVAL),
+    ("reslayer128", dict(w1=None), _EINVAL),
+    ("reslayer128", dict(rows=-1), _EINVAL),
+    ("tail", {}, _OK),
+    ("tail", dict(w0=None, b0=None, k_in=4, ldx=4, n_out=4, ldo=4), _OK),
+    ("tail", dict(scatter=_IDX, valid=_AUX2, per_group=4), _OK),
+    ("tail", dict(n_out=9, ldo=9), _EINVAL),
+    ("tail", dict(k_in=62), _EINVAL),
+    ("tail", dict(x=_X + 4), _EINVAL),
+    ("tail", dict(b0=None), _EINVAL),
+    ("tail", dict(valid=_AUX2, per_group=4), _EINVAL),
+    ("tail", dict(scatter=_IDX, valid=_AUX2, per_group=0), _EINVAL),
+    # f16x2: one struct for every form (plain, tap, gather, decode; mode 1 = Linear, mode 2 = sumgather)
+    ("split16", {}, _OK),
+    ("split16", dict(b0=None, k_in=128, ldx=128), _OK),
+    ("split16", dict(first_out=_TAP, ld_first=128), _OK),
+    ("split16", _GATHER16, _OK),
+    ("split16", _DECODE16, _OK),
+    ("split16", dict(_DECODE16, prior_pos=_TAB, prior_inv_sigma=2.0), _OK),
+    ("split16", _LINEAR16, _OK),
+    ("split16", _SUMGATHER16, _OK),
+    ("split16", dict(x=None), _EINVAL),
+    ("split16", dict(wq=None), _EINVAL),
+    ("split16", dict(b1=None), _EINVAL),
+    ("split16", dict(rows=-1), _EINVAL),
+    ("split16", dict(chain=16), _EINVAL),
+    ("split16", dict(weight_scale=3.0), _EINVAL),
+    ("split16", dict(weight_scale=0.0), _EINVAL),
+    ("split16", dict(x=_X + 4), _EINVAL),
+    ("split16", dict(ldo=130), _EINVAL),
+    ("split16", dict(first_out=_TAP + 4, ld_first=128), _EINVAL),
+    ("split16", dict(_GATHER16, uniforms=_AUX, bins=_AUX2), _EINVAL),
+    ("split16", dict(_GATHER16, first_out=_TAP, ld_first=128), _EINVAL),
+    ("split16", dict(_LINEAR16, b0=_B0), _EINVAL),
+    ("split16", dict(mode=2), _EINVAL),
+    ("split16", dict(mode=3), _EINVAL),
+    # f16x2 rules of the form itself: checked before the rows == 0 return, like the bf16 forms
+    ("split16", dict(k_in=60), _EINVAL),
+    ("split16", dict(ldx=56), _EINVAL),
+    ("split16", dict(n_out=96, ldo=96, wq_bytes=-1), _EINVAL),
+    ("split16", dict(ldo=64), _EINVAL),
+    ("split16", dict(b0=None), _EINVAL),
+    ("split16", dict(wq_bytes=1024), _EINVAL),
+    ("split16", dict(out=None), _EINVAL),
+    ("split16", dict(first_out=_OUT, ld_first=128), _EINVAL),
+    ("split16", dict(first_out=_TAP, ld_first=64), _EINVAL),
+    ("split16", dict(_GATHER16, fdim=24), _EINVAL),
+    ("split16", dict(_GATHER16, slots=9), _EINVAL),
+    ("split16", dict(_GATHER16, table=None), _EINVAL),
+    ("split16", dict(_GATHER16, b0=None), _EINVAL),
+    ("split16", dict(_GATHER16, n_out=64, ldo=64), _EUNSUPPORTED),
+    ("split16", dict(_GATHER16, k_in=0, ldx=-4), _EINVAL),
+    ("split16", dict(_DECODE16, bins=None), _EINVAL),
+    ("split16", dict(_DECODE16, b0=None), _EINVAL),
+    ("split16", dict(_DECODE16, logit_prior=_TAB, prior_pos=_TAB, prior_inv_sigma=2.0), _EINVAL),
+    ("split16", dict(_DECODE16, wq_bytes=1024), _EINVAL),
+    ("split16", dict(_LINEAR16, n_out=128, ldo=128, wq_bytes=-1), _EINVAL),
+    ("split16", dict(_LINEAR16, wq_bytes=1024), _EINVAL),
+    ("split16", dict(_SUMGATHER16, ld_table=1276), _EINVAL),
+    ("split16", dict(_SUMGATHER16, table=None), _EINVAL),
+    ("split16", dict(_SUMGATHER16, n_out=64, ldo=64), _EUNSUPPORTED),
+]
+
+
+@pytest.mark.parametrize("entry,kw,expected", _VALIDATION_CASES,
+                         ids=["%s-%d" % (c[0], i) for i, c in enumerate(_VALIDATION_CASES)])
+def test_mlp_launch_validation_return_codes(entry, kw, expected):
+    """Every ResLayer launch entry point: a valid call with rows = 0 returns 0 (no device work), and a call that breaks one shape,
+    stride, alignment, pointer or stream-size rule returns its exact code, without a GPU."""
+    lib = _untraced_lib()
+    got = globals()["_call_" + entry](lib, **kw)
+    assert got == expected, (entry, kw, got, lib.cppf_last_error_string())
