@@ -1351,109 +1351,132 @@ __global__ __launch_bounds__(64) void shot_hist_kernel(int B, const float* __res
 // ---------------------------------------------------------------------------------------------
 static inline int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
 
-struct ShotWs {
-  CellHdr* hdr; int32_t* cell_start; int32_t* sorted_idx; float4* sorted_pts; double* sums; LrfPre* pre;
-  int32_t* scene_of; float4* sorted_nrm; int32_t* nbr_cnt; int32_t* nbr_list;
+// Byte offsets of the workspace, shared by every entry point.  The colour form appends two float4 Lab tables (the caller's order,
+// the cell-sorted order) to the 352 layout.
+struct ShotLayout {
+  int64_t hdr, cell_start, sorted_idx, sorted_pts, sums, pre, scene_of, sorted_nrm, nbr_cnt, nbr_list, lab, sorted_lab, bytes;
 };
 
-static ShotWs carve(void* ws, int B, int64_t n) {
-  char* p = (char*)ws;
-  ShotWs w;
-  w.hdr = (CellHdr*)p; p += up256((int64_t)B * sizeof(CellHdr));
-  w.cell_start = (int32_t*)p; p += up256((int64_t)B * (CELL_CAP + 1) * 4);
-  w.sorted_idx = (int32_t*)p; p += up256(n * 4);
-  w.sorted_pts = (float4*)p; p += up256(n * 16);
-  w.sums = (double*)p; p += up256(n * NSUM * 8);
-  w.pre = (LrfPre*)p; p += up256(n * (int64_t)sizeof(LrfPre));
-  w.scene_of = (int32_t*)p; p += up256(n * 4);
-  w.sorted_nrm = (float4*)p; p += up256(n * 16);
-  w.nbr_cnt = (int32_t*)(p + 256); p += up256(n * 4 + 256);        // one slot before the counts: the lists' radius
-  w.nbr_list = (int32_t*)p;
-  return w;
+static ShotLayout shot_layout(int B, int64_t n, bool color) {
+  ShotLayout L;
+  L.hdr = 0;
+  L.cell_start = L.hdr + up256((int64_t)B * sizeof(CellHdr));
+  L.sorted_idx = L.cell_start + up256((int64_t)B * (CELL_CAP + 1) * 4);
+  L.sorted_pts = L.sorted_idx + up256(n * 4);
+  L.sums = L.sorted_pts + up256(n * 16);
+  L.pre = L.sums + up256(n * NSUM * 8);
+  L.scene_of = L.pre + up256(n * (int64_t)sizeof(LrfPre));
+  L.sorted_nrm = L.scene_of + up256(n * 4);
+  L.nbr_cnt = L.sorted_nrm + up256(n * 16) + 256;                     // one slot before the counts: the lists' radius
+  L.nbr_list = L.nbr_cnt - 256 + up256(n * 4 + 256);
+  L.lab = L.nbr_list + up256(n * (int64_t)NBR_CAP * 4);
+  L.sorted_lab = L.lab + (color ? up256(n * 16) : 0);
+  L.bytes = L.sorted_lab + (color ? up256(n * 16) : 0);
+  return L;
 }
 
 extern "C" int64_t cppf_shot352_workspace_bytes(int B, int64_t total_points) {
   if (B <= 0 || total_points <= 0) return 0;
-  return up256((int64_t)B * sizeof(CellHdr)) + up256((int64_t)B * (CELL_CAP + 1) * 4) + up256(total_points * 4) +
-         up256(total_points * 16) + up256(total_points * NSUM * 8) + up256(total_points * (int64_t)sizeof(LrfPre)) +
-         up256(total_points * 4) + up256(total_points * 16) + up256(total_points * 4 + 256) +
-         up256(total_points * (int64_t)NBR_CAP * 4);
+  return shot_layout(B, total_points, false).bytes;
 }
+
+// One call of the pipeline.  prepare (runs when a radius is given): cells -> covariances (-> PCL long lists) -> eigen-solves.
+// describe (runs when out_shot is given): normals into the cell order (-> Lab of the colours) -> histograms.  rs > 0 means a
+// describe follows, now or in a later call: the neighbour lists and the local frames are kept.
+struct ShotRequest {
+  int B; const float* pts; const int32_t* pt_off; int64_t n; hipStream_t st;
+  bool pcl; float rn, rs; float* out_normal;                                                              // prepare
+  const float* normals; const float* colors; float shot_r; int nan_to_zero; float* out_shot; float* out_rf;   // describe
+  char* ws; ShotLayout L;
+  template <class T> T* at(int64_t off) const { return (T*)(ws + off); }
+};
 
 // CPPF_SHOT_F64_NORMALS (flags bit 0 of the entry points): the round-1..3 arithmetic for the normals -- float64 covariance about
 // the query point, Jacobi -- instead of pcl::NormalEstimation's (single-pass float32 sums of the raw coordinates in
 // (distance, index) order, closed-form eigen33, float32 viewpoint flip), which is the default since round 4.
-template <class... Args>
-static void launch_cov(bool pcl, dim3 grid, hipStream_t st, Args... args) {
-  if (pcl) hipLaunchKernelGGL(shot_cov_kernel<true>, grid, dim3(64), 0, st, args...);
-  else hipLaunchKernelGGL(shot_cov_kernel<false>, grid, dim3(64), 0, st, args...);
+static int shot_prepare(const ShotRequest& r) {
+  const ShotLayout& L = r.L;
+  const bool keep = r.rs > 0.0f;
+  int32_t* lists = (keep || r.pcl) ? r.at<int32_t>(L.nbr_list) : nullptr;      // (PCL normals read long lists back from it)
+  int32_t* counts = (keep || r.pcl) ? r.at<int32_t>(L.nbr_cnt) : nullptr;
+  hipLaunchKernelGGL(shot_cells_kernel, dim3(r.B), dim3(1024), 0, r.st, r.pts, r.pt_off, fmaxf(r.rn, r.rs), r.at<CellHdr>(L.hdr),
+                     r.at<int32_t>(L.cell_start), r.at<int32_t>(L.sorted_idx), r.at<float4>(L.sorted_pts), r.at<int32_t>(L.scene_of));
+  CPPF_LAUNCH_CHECK();
+  hipLaunchKernelGGL((r.pcl ? shot_cov_kernel<true> : shot_cov_kernel<false>), dim3((unsigned)r.n), dim3(64), 0, r.st, r.B, r.pts,
+                     r.pt_off, r.at<CellHdr>(L.hdr), r.at<int32_t>(L.cell_start), r.at<float4>(L.sorted_pts), r.at<int32_t>(L.scene_of),
+                     r.rn, r.rs, r.at<double>(L.sums), lists, counts);
+  CPPF_LAUNCH_CHECK();
+  if (r.pcl && r.rn > 0.0f) {
+    const int64_t blocks = std::min<int64_t>((r.n + PCL_LONG_SCAN - 1) / PCL_LONG_SCAN, 16384);
+    hipLaunchKernelGGL(shot_pcl_long_kernel, dim3((unsigned)blocks), dim3(64), 0, r.st, r.n, r.pts, r.pt_off, r.at<float4>(L.sorted_pts),
+                       r.at<int32_t>(L.scene_of), r.rn, lists, counts, r.at<double>(L.sums));
+    CPPF_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(shot_eig_kernel, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, r.st, r.n, r.pts, r.at<double>(L.sums),
+                     r.out_normal, keep ? r.at<LrfPre>(L.pre) : nullptr, (int)r.pcl);
+  CPPF_LAUNCH_CHECK();
+  return CPPF_OK;
 }
 
-static int shot_run(int B, const float* pts, const int32_t* pt_off, int64_t n, float normal_r, float shot_r,
-                    const float* normals_in, float* out_normal, float* out_shot, float* out_rf, void* workspace,
-                    int64_t workspace_bytes, hipStream_t st, int flags) {
-  const bool pcl = !(flags & CPPF_SHOT_F64_NORMALS);
-  CPPF_CHECK_ARG(workspace && workspace_bytes >= cppf_shot352_workspace_bytes(B, n));
-  const ShotWs w = carve(workspace, B, n);
-  const bool want_n = out_normal != nullptr, want_s = out_shot != nullptr;
-  const float rn = want_n ? normal_r : 0.0f, rs = want_s ? shot_r : 0.0f;
-  hipLaunchKernelGGL(shot_cells_kernel, dim3(B), dim3(1024), 0, st, pts, pt_off, fmaxf(rn, rs), w.hdr, w.cell_start,
-                     w.sorted_idx, w.sorted_pts, w.scene_of);
+static int shot_describe(const ShotRequest& r) {
+  const ShotLayout& L = r.L;
+  const bool color = r.colors != nullptr;
+  float4* lab = color ? r.at<float4>(L.lab) : nullptr;
+  float4* sorted_lab = color ? r.at<float4>(L.sorted_lab) : nullptr;
+  hipLaunchKernelGGL(shot_sort_normals_kernel, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, r.st, r.n, r.normals, r.pt_off,
+                     r.at<int32_t>(L.scene_of), r.at<int32_t>(L.sorted_idx), r.at<float4>(L.sorted_nrm));
+  if (color)
+    hipLaunchKernelGGL(shot_lab_kernel, dim3((unsigned)((r.n + 255) / 256)), dim3(256), 0, r.st, r.n, r.colors, r.pt_off,
+                       r.at<int32_t>(L.scene_of), r.at<int32_t>(L.sorted_idx), lab, sorted_lab);
   CPPF_LAUNCH_CHECK();
-  launch_cov(pcl, dim3((unsigned)n), st, B, pts, pt_off, (const CellHdr*)w.hdr, (const int32_t*)w.cell_start,
-             (const float4*)w.sorted_pts, (const int32_t*)w.scene_of, rn, rs, w.sums,
-             (want_s || pcl) ? w.nbr_list : (int32_t*)nullptr,      // (PCL normals read long lists back from it)
-             (want_s || pcl) ? w.nbr_cnt : (int32_t*)nullptr);
+  hipLaunchKernelGGL((color ? shot_hist_kernel<true> : shot_hist_kernel<false>), dim3((unsigned)r.n), dim3(64), 0, r.st, r.B, r.pts,
+                     r.pt_off, r.at<CellHdr>(L.hdr), r.at<int32_t>(L.cell_start), r.at<int32_t>(L.sorted_idx), r.at<float4>(L.sorted_pts),
+                     r.at<int32_t>(L.scene_of), r.at<float4>(L.sorted_nrm), r.at<LrfPre>(L.pre), r.shot_r, r.nan_to_zero,
+                     r.at<int32_t>(L.nbr_list), r.at<int32_t>(L.nbr_cnt), r.out_shot, r.out_rf, lab, sorted_lab);
   CPPF_LAUNCH_CHECK();
-  if (pcl && want_n) {
-    hipLaunchKernelGGL(shot_pcl_long_kernel, dim3((unsigned)((n + PCL_LONG_SCAN - 1) / PCL_LONG_SCAN < 16384 ? (n + PCL_LONG_SCAN - 1) / PCL_LONG_SCAN : 16384)), dim3(64), 0, st, n, pts, pt_off,
-                       (const float4*)w.sorted_pts, (const int32_t*)w.scene_of, rn, (const int32_t*)w.nbr_list,
-                       (const int32_t*)w.nbr_cnt, w.sums);
-    CPPF_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(shot_eig_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, pts, w.sums,
-                     out_normal, want_s ? w.pre : (LrfPre*)nullptr, (int)pcl);
-  CPPF_LAUNCH_CHECK();
-  if (want_s) {
-    hipLaunchKernelGGL(shot_sort_normals_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n,
-                       normals_in ? normals_in : out_normal, pt_off, w.scene_of, w.sorted_idx, w.sorted_nrm);
-    CPPF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(shot_hist_kernel<false>, dim3((unsigned)n), dim3(64), 0, st, B, pts, pt_off, w.hdr, w.cell_start,
-                       w.sorted_idx, w.sorted_pts, w.scene_of, w.sorted_nrm, w.pre, shot_r, 0, w.nbr_list, w.nbr_cnt,
-                       out_shot, out_rf);
-    CPPF_LAUNCH_CHECK();
-  }
   return CPPF_OK;
+}
+
+// Called after the entry point's own argument checks: no points is a valid call with nothing to do; a workspace smaller than
+// the layout is refused before any device work.
+static int shot_run(ShotRequest r, void* workspace, int64_t workspace_bytes) {
+  CPPF_CHECK_ARG(r.n >= 0 && r.n <= 0x7fffffffLL);
+  if (r.n == 0) return CPPF_OK;
+  r.L = shot_layout(r.B, r.n, r.colors != nullptr);
+  CPPF_CHECK_ARG(workspace && workspace_bytes >= r.L.bytes);
+  r.ws = (char*)workspace;
+  if (r.rn > 0.0f || r.rs > 0.0f) CPPF_TRY(shot_prepare(r));
+  return r.out_shot ? shot_describe(r) : CPPF_OK;
 }
 
 extern "C" int cppf_estimate_normals(int B, const float* pts, const int32_t* pt_off, int64_t total_points,
                                      float normal_r, float* out_normal, void* workspace, int64_t workspace_bytes,
                                      int flags, void* stream) {
   CPPF_CHECK_ARG(B > 0 && pts && pt_off && out_normal && normal_r > 0.0f);
-  CPPF_CHECK_ARG(total_points >= 0 && total_points <= 0x7fffffffLL);
-  if (total_points <= 0) return CPPF_OK;
-  return shot_run(B, pts, pt_off, total_points, normal_r, 0.0f, nullptr, out_normal, nullptr, nullptr, workspace,
-                  workspace_bytes, (hipStream_t)stream, flags);
+  ShotRequest r = {B, pts, pt_off, total_points, (hipStream_t)stream};
+  r.pcl = !(flags & CPPF_SHOT_F64_NORMALS); r.rn = normal_r; r.out_normal = out_normal;
+  return shot_run(r, workspace, workspace_bytes);
 }
 
 extern "C" int cppf_shot352(int B, const float* pts, const int32_t* pt_off, int64_t total_points, float normal_r,
                             float shot_r, float* out_shot, float* out_normal, float* out_rf, void* workspace,
                             int64_t workspace_bytes, int flags, void* stream) {
   CPPF_CHECK_ARG(B > 0 && pts && pt_off && out_shot && out_normal && normal_r > 0.0f && shot_r > 0.0f);
-  CPPF_CHECK_ARG(total_points >= 0 && total_points <= 0x7fffffffLL);
-  if (total_points <= 0) return CPPF_OK;
-  return shot_run(B, pts, pt_off, total_points, normal_r, shot_r, nullptr, out_normal, out_shot, out_rf, workspace,
-                  workspace_bytes, (hipStream_t)stream, flags);
+  ShotRequest r = {B, pts, pt_off, total_points, (hipStream_t)stream};
+  r.pcl = !(flags & CPPF_SHOT_F64_NORMALS); r.rn = normal_r; r.rs = shot_r; r.out_normal = out_normal;
+  r.normals = out_normal; r.shot_r = shot_r; r.out_shot = out_shot; r.out_rf = out_rf;
+  return shot_run(r, workspace, workspace_bytes);
 }
 
+// The caller's normals replace the estimated ones; prepare still computes the local frames (with the PCL-form covariances).
 extern "C" int cppf_shot352_from_normals(int B, const float* pts, const int32_t* pt_off, int64_t total_points,
                                          const float* normals, float shot_r, float* out_shot, float* out_rf,
                                          void* workspace, int64_t workspace_bytes, void* stream) {
   CPPF_CHECK_ARG(B > 0 && pts && pt_off && normals && out_shot && shot_r > 0.0f);
-  CPPF_CHECK_ARG(total_points >= 0 && total_points <= 0x7fffffffLL);
-  if (total_points <= 0) return CPPF_OK;
-  return shot_run(B, pts, pt_off, total_points, 0.0f, shot_r, normals, nullptr, out_shot, out_rf, workspace,
-                  workspace_bytes, (hipStream_t)stream, 0);
+  ShotRequest r = {B, pts, pt_off, total_points, (hipStream_t)stream};
+  r.pcl = true; r.rs = shot_r;
+  r.normals = normals; r.shot_r = shot_r; r.out_shot = out_shot; r.out_rf = out_rf;
+  return shot_run(r, workspace, workspace_bytes);
 }
 
 // Two-call form of cppf_shot352 sharing one workspace: prepare = cells + covariances + eigen-solves (normals out,
@@ -1463,96 +1486,36 @@ extern "C" int cppf_shot_prepare(int B, const float* pts, const int32_t* pt_off,
                                  float shot_r, float* out_normal, void* workspace, int64_t workspace_bytes,
                                  int flags, void* stream) {
   CPPF_CHECK_ARG(B > 0 && pts && pt_off && out_normal && normal_r > 0.0f && shot_r > 0.0f);
-  CPPF_CHECK_ARG(total_points >= 0 && total_points <= 0x7fffffffLL);
-  if (total_points <= 0) return CPPF_OK;
-  CPPF_CHECK_ARG(workspace && workspace_bytes >= cppf_shot352_workspace_bytes(B, total_points));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = total_points;
-  const ShotWs w = carve(workspace, B, n);
-  hipLaunchKernelGGL(shot_cells_kernel, dim3(B), dim3(1024), 0, st, pts, pt_off, fmaxf(normal_r, shot_r), w.hdr,
-                     w.cell_start, w.sorted_idx, w.sorted_pts, w.scene_of);
-  CPPF_LAUNCH_CHECK();
-  const bool pcl = !(flags & CPPF_SHOT_F64_NORMALS);
-  launch_cov(pcl, dim3((unsigned)n), st, B, pts, pt_off, (const CellHdr*)w.hdr, (const int32_t*)w.cell_start,
-             (const float4*)w.sorted_pts, (const int32_t*)w.scene_of, normal_r, shot_r, w.sums, w.nbr_list, w.nbr_cnt);
-  CPPF_LAUNCH_CHECK();
-  if (pcl) {
-    hipLaunchKernelGGL(shot_pcl_long_kernel, dim3((unsigned)((n + PCL_LONG_SCAN - 1) / PCL_LONG_SCAN < 16384 ? (n + PCL_LONG_SCAN - 1) / PCL_LONG_SCAN : 16384)), dim3(64), 0, st, n, pts, pt_off,
-                       (const float4*)w.sorted_pts, (const int32_t*)w.scene_of, normal_r, (const int32_t*)w.nbr_list,
-                       (const int32_t*)w.nbr_cnt, w.sums);
-    CPPF_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(shot_eig_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, pts, w.sums, out_normal,
-                     w.pre, (int)pcl);
-  CPPF_LAUNCH_CHECK();
-  return CPPF_OK;
+  ShotRequest r = {B, pts, pt_off, total_points, (hipStream_t)stream};
+  r.pcl = !(flags & CPPF_SHOT_F64_NORMALS); r.rn = normal_r; r.rs = shot_r; r.out_normal = out_normal;
+  return shot_run(r, workspace, workspace_bytes);
 }
 
 extern "C" int cppf_shot_describe(int B, const float* pts, const int32_t* pt_off, int64_t total_points,
                                   const float* normals, float shot_r, int nan_to_zero, float* out_shot, float* out_rf,
-                                  void* workspace,
-                                  int64_t workspace_bytes, void* stream) {
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
   CPPF_CHECK_ARG(B > 0 && pts && pt_off && normals && out_shot && shot_r > 0.0f);
-  CPPF_CHECK_ARG(total_points >= 0 && total_points <= 0x7fffffffLL);
-  if (total_points <= 0) return CPPF_OK;
-  CPPF_CHECK_ARG(workspace && workspace_bytes >= cppf_shot352_workspace_bytes(B, total_points));
-  const ShotWs w = carve(workspace, B, total_points);
-  hipLaunchKernelGGL(shot_sort_normals_kernel, dim3((unsigned)((total_points + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, total_points, normals, pt_off, w.scene_of, w.sorted_idx, w.sorted_nrm);
-  CPPF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(shot_hist_kernel<false>, dim3((unsigned)total_points), dim3(64), 0, (hipStream_t)stream, B, pts, pt_off,
-                     w.hdr, w.cell_start, w.sorted_idx, w.sorted_pts, w.scene_of, w.sorted_nrm, w.pre, shot_r, nan_to_zero,
-                     w.nbr_list, w.nbr_cnt, out_shot, out_rf);
-  CPPF_LAUNCH_CHECK();
-  return CPPF_OK;
+  ShotRequest r = {B, pts, pt_off, total_points, (hipStream_t)stream};
+  r.normals = normals; r.shot_r = shot_r; r.nan_to_zero = nan_to_zero; r.out_shot = out_shot; r.out_rf = out_rf;
+  return shot_run(r, workspace, workspace_bytes);
 }
 
 // ---------------------------------------------------------------------------------------------
 // shot.compute_color (src_shot/shot.cpp:102-161): SHOT1344 = 352 shape + 992 colour entries per point.
 // Same pipeline as cppf_shot352 with the two-channel histogram kernel; the colour of a point enters through its
-// normalised CIELab triple (shot_lab_kernel).  Workspace = cppf_shot352's + two float4 tables of Lab values.
+// normalised CIELab triple (shot_lab_kernel), kept in the two tables the colour layout adds.
 // ---------------------------------------------------------------------------------------------
 extern "C" int64_t cppf_shot1344_workspace_bytes(int B, int64_t total_points) {
   if (B <= 0 || total_points <= 0) return 0;
-  return cppf_shot352_workspace_bytes(B, total_points) + 2 * up256(total_points * 16);
+  return shot_layout(B, total_points, true).bytes;
 }
 
 extern "C" int cppf_shot1344(int B, const float* pts, const float* colors, const int32_t* pt_off, int64_t total_points,
                              float normal_r, float shot_r, float* out_shot, float* out_normal, void* workspace,
                              int64_t workspace_bytes, int flags, void* stream) {
   CPPF_CHECK_ARG(B > 0 && pts && colors && pt_off && out_shot && out_normal && normal_r > 0.0f && shot_r > 0.0f);
-  CPPF_CHECK_ARG(total_points >= 0 && total_points <= 0x7fffffffLL);
-  if (total_points <= 0) return CPPF_OK;
-  CPPF_CHECK_ARG(workspace && workspace_bytes >= cppf_shot1344_workspace_bytes(B, total_points));
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = total_points;
-  const ShotWs w = carve(workspace, B, n);
-  float4* lab = (float4*)((char*)workspace + cppf_shot352_workspace_bytes(B, n));
-  float4* sorted_lab = (float4*)((char*)lab + up256(n * 16));
-  hipLaunchKernelGGL(shot_cells_kernel, dim3(B), dim3(1024), 0, st, pts, pt_off, fmaxf(normal_r, shot_r), w.hdr,
-                     w.cell_start, w.sorted_idx, w.sorted_pts, w.scene_of);
-  CPPF_LAUNCH_CHECK();
-  const bool pcl = !(flags & CPPF_SHOT_F64_NORMALS);
-  launch_cov(pcl, dim3((unsigned)n), st, B, pts, pt_off, (const CellHdr*)w.hdr, (const int32_t*)w.cell_start,
-             (const float4*)w.sorted_pts, (const int32_t*)w.scene_of, normal_r, shot_r, w.sums, w.nbr_list, w.nbr_cnt);
-  CPPF_LAUNCH_CHECK();
-  if (pcl) {
-    hipLaunchKernelGGL(shot_pcl_long_kernel, dim3((unsigned)((n + PCL_LONG_SCAN - 1) / PCL_LONG_SCAN < 16384 ? (n + PCL_LONG_SCAN - 1) / PCL_LONG_SCAN : 16384)), dim3(64), 0, st, n, pts, pt_off,
-                       (const float4*)w.sorted_pts, (const int32_t*)w.scene_of, normal_r, (const int32_t*)w.nbr_list,
-                       (const int32_t*)w.nbr_cnt, w.sums);
-    CPPF_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(shot_eig_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, pts, w.sums, out_normal,
-                     w.pre, (int)pcl);
-  CPPF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(shot_sort_normals_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, out_normal, pt_off,
-                     w.scene_of, w.sorted_idx, w.sorted_nrm);
-  hipLaunchKernelGGL(shot_lab_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, colors, pt_off, w.scene_of,
-                     w.sorted_idx, lab, sorted_lab);
-  CPPF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(shot_hist_kernel<true>, dim3((unsigned)n), dim3(64), 0, st, B, pts, pt_off, w.hdr, w.cell_start,
-                     w.sorted_idx, w.sorted_pts, w.scene_of, w.sorted_nrm, w.pre, shot_r, 0, w.nbr_list, w.nbr_cnt,
-                     out_shot, (float*)nullptr, (const float4*)lab, (const float4*)sorted_lab);
-  CPPF_LAUNCH_CHECK();
-  return CPPF_OK;
+  ShotRequest r = {B, pts, pt_off, total_points, (hipStream_t)stream};
+  r.pcl = !(flags & CPPF_SHOT_F64_NORMALS); r.rn = normal_r; r.rs = shot_r; r.out_normal = out_normal;
+  r.normals = out_normal; r.colors = colors; r.shot_r = shot_r; r.out_shot = out_shot;
+  return shot_run(r, workspace, workspace_bytes);
 }

@@ -25,7 +25,7 @@
 //      from the list.  When there are fewer slabs than CUs (small batches) the list kernel splits every slab's pair
 //      list into parts; the parts merge through a zeroed area with device atomics and a ticket per slab.
 // vote_center_slab_kernel (one item per workgroup, (scene, part, rank) launch) remains for the exhaustive A/B mode and
-// on request (mode bit 0x800); there the parts of a small batch merge into the zeroed global grid.
+// on request (mode bit VC_MODE_NO_PERSIST); there the parts of a small batch merge into the zeroed global grid.
 // Mode 2 (global atomics, one thread per pair, exhaustive sweep) is the independent A/B reference; mode 3 is
 // the slab kernel with the exhaustive rotation sweep and exact divisions.
 // =============================================================================================
@@ -790,17 +790,75 @@ __global__ __launch_bounds__(256) void grid_zero_kernel(uint32_t* __restrict__ g
 
 static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
+// slabs of a grid of cells_cap cells, and at least VC_ARG_BLOCKS: entries per scene of the partial-maximum table
 static inline int vc_parts(int64_t cells_cap) {
-  int64_t s_max = (cells_cap + VC_SLAB_CELLS - 1) / VC_SLAB_CELLS;
-  if (s_max < VC_ARG_BLOCKS) s_max = VC_ARG_BLOCKS;
-  return (int)s_max;
+  return (int)std::max<int64_t>((cells_cap + VC_SLAB_CELLS - 1) / VC_SLAB_CELLS, VC_ARG_BLOCKS);
+}
+
+// Byte offsets of the workspace.  best: the partial-maximum table; ctl, list: the persistent kernel's control words (next item,
+// item count, parts per slab, slab cells) and work list; tickets: one arrival counter per (scene, slab) of the pair-split merge;
+// grid: the merge area, or the accumulator when the caller passes no grid; frames: the per-pair circle frames.
+struct VcLayout {
+  int64_t best, ctl, list, tickets, grid, frames, bytes;
+};
+
+static VcLayout vc_layout(int B, int64_t cells_cap, int64_t total_tuples) {
+  const int64_t parts = (int64_t)B * vc_parts(cells_cap);
+  VcLayout L;
+  L.best = 0;
+  L.ctl = L.best + align_up(parts * (int64_t)sizeof(SlabBest), 256);
+  L.list = L.ctl + 256;
+  L.tickets = L.ctl + align_up(parts * 4 + 256, 256);
+  L.grid = L.tickets + align_up(parts * 4, 256);
+  L.frames = L.grid + align_up((int64_t)B * cells_cap * 4, 256);
+  L.bytes = L.frames + align_up(total_tuples * VC_FRAME_FLOATS * 4, 256);
+  return L;
 }
 
 extern "C" int64_t cppf_vote_center_workspace_bytes(int B, int64_t cells_cap, int64_t total_tuples) {
   if (B <= 0 || cells_cap <= 0 || total_tuples < 0) return 0;
-  return align_up((int64_t)B * vc_parts(cells_cap) * (int64_t)sizeof(SlabBest), 256) +
-         align_up((int64_t)B * vc_parts(cells_cap) * 4 + 256, 256) + align_up((int64_t)B * vc_parts(cells_cap) * 4, 256) +
-         align_up((int64_t)B * cells_cap * 4, 256) + align_up(total_tuples * VC_FRAME_FLOATS * 4, 256);
+  return vc_layout(B, cells_cap, total_tuples).bytes;
+}
+
+// mode bit: the arcs path launches one (scene, slab) item per workgroup (vote_center_slab_kernel), not the persistent kernel
+constexpr int VC_MODE_NO_PERSIST = 0x800;
+
+enum VcPath { VC_PERSIST, VC_SLAB, VC_GLOBAL };
+
+// Every launch decision of one call, taken before any launch.  P: VC_SLAB splits each slab's pair list P ways, merged with
+// atomics into a zeroed grid.  max_parts: the most parts VC_PERSIST's work-list kernel may split a slab into (> 1 costs a zeroed
+// merge area and tickets).  prepare / vote: the halves of the two-call form this call runs.
+struct VcPlan {
+  VcPath path;
+  bool arcs, weighted, prepare, vote;
+  int P, max_parts, s_max, s_max_parts;
+};
+
+static int vc_plan(int mode, int B, int max_t, int num_rots, int64_t cells_cap, bool weighted, VcPlan* p) {
+  const int s_max = (int)((cells_cap + VC_SLAB_CELLS - 1) / VC_SLAB_CELLS);
+  int m = mode & 0xff;
+  if (m == 0) m = (s_max <= 64) ? 1 : 2;
+  if (max_t <= 0) m = 2;
+  if (m < 1 || m > 3) {
+    snprintf(g_cppf_err, sizeof(g_cppf_err), "cppf_vote_center: unknown mode %d", m);
+    return CPPF_EINVAL;
+  }
+  // arcs need >1 slab to pay off and the table in LDS; mode 3 is the exhaustive sweep (A/B reference).  The persistent work-list
+  // kernel serves every batch size of the arcs path; the one-item-per-workgroup launch remains for mode 3 and on request.
+  const bool arcs = m == 1 && s_max > 1 && num_rots <= VC_MAX_LDS_ROTS && num_rots >= 8;
+  const bool persist = arcs && B <= 0xffff && s_max <= 0xffff && !(mode & VC_MODE_NO_PERSIST);
+  // two-call form (lets a caller put events around the vote kernel alone): CPPF_VC_FRAMES_ONLY runs the preparation (frames,
+  // work list) and returns, CPPF_VC_FRAMES_READY skips it; the global path ignores both bits
+  *p = VcPlan{m == 2 ? VC_GLOBAL : persist ? VC_PERSIST : VC_SLAB, arcs, weighted, m == 2 || !(mode & CPPF_VC_FRAMES_READY),
+              m == 2 || !(mode & CPPF_VC_FRAMES_ONLY), 1, 1, s_max, vc_parts(cells_cap)};
+  // Small batches may have fewer slabs than CUs.  How many is only known on the device (scene bounds), so the persistent path's
+  // work-list kernel picks the parts per slab; the host only bounds them (parts of at least VC_THREADS pairs).  The slab path
+  // splits when its (scene, slab) workgroups cannot fill 256 CUs.
+  const int pmax_t = (max_t + VC_THREADS - 1) / VC_THREADS;
+  const int64_t wgs = (int64_t)B * s_max;
+  if (persist && B <= 48) p->max_parts = std::min(pmax_t, 64);
+  if (p->path == VC_SLAB && wgs < 256) p->P = (int)std::min<int64_t>((256 + wgs - 1) / wgs, pmax_t);
+  return CPPF_OK;
 }
 
 extern "C" int cppf_vote_center(int B, const float* pts, const int32_t* pt_off, const int32_t* idx, int k,
@@ -812,143 +870,72 @@ extern "C" int cppf_vote_center(int B, const float* pts, const int32_t* pt_off, 
   CPPF_CHECK_ARG(B > 0 && pts && pt_off && idx && tup_off && tr && cos_tab && sin_tab && grids && out_argmax);
   CPPF_CHECK_ARG(k >= 2 && num_rots > 0 && res > 0.0 && cells_cap > 0 && cells_cap <= 0x7fffffffLL);
   CPPF_CHECK_ARG(total_tuples >= 0 && max_t >= 0 && (int64_t)max_t <= total_tuples);
-  CPPF_CHECK_ARG(workspace && workspace_bytes >= cppf_vote_center_workspace_bytes(B, cells_cap, total_tuples));
+  const VcLayout L = vc_layout(B, cells_cap, total_tuples);
+  CPPF_CHECK_ARG(workspace && workspace_bytes >= L.bytes);
   CPPF_CHECK_ARG(grid == nullptr || grid_off != nullptr);
+  VcPlan p;
+  CPPF_TRY(vc_plan(mode, B, max_t, num_rots, cells_cap, vote_wt != nullptr, &p));
   hipStream_t st = (hipStream_t)stream;
-  const int s_max_parts = vc_parts(cells_cap);
-  SlabBest* best = (SlabBest*)workspace;
-  char* wsp = (char*)workspace + align_up((int64_t)B * s_max_parts * sizeof(SlabBest), 256);
-  int* ws_ctl = (int*)wsp;                        // persistent kernel: next item, item count, parts; then the work list
-  uint32_t* ws_list = (uint32_t*)(wsp + 256);
-  wsp += align_up((int64_t)B * s_max_parts * 4 + 256, 256);
-  int* ws_tickets = (int*)wsp;                    // one arrival counter per (scene, slab) of the pair-split merge
-  wsp += align_up((int64_t)B * s_max_parts * 4, 256);
-  uint32_t* ws_grid = (uint32_t*)wsp;
-  float* frames = (float*)(wsp + align_up((int64_t)B * cells_cap * 4, 256));
-  const int s_max = (int)((cells_cap + VC_SLAB_CELLS - 1) / VC_SLAB_CELLS);
-  // two-call form (lets a caller put events around the vote kernel alone): CPPF_VC_FRAMES_ONLY fills the per-pair
-  // frames in the workspace and returns; CPPF_VC_FRAMES_READY skips that step
-  const bool frames_only = (mode & CPPF_VC_FRAMES_ONLY) != 0, frames_ready = (mode & CPPF_VC_FRAMES_READY) != 0;
-  const int mode_bits = mode;                     // bit 11 (0x800): one-item-per-workgroup launch even for big batches
-  mode &= 0xff;
-  if (mode == 0) mode = (s_max <= 64) ? 1 : 2;
-  int exhaustive = 0;
-  if (mode == 3) { mode = 1; exhaustive = 1; }
+  char* ws = (char*)workspace;
+  SlabBest* best = (SlabBest*)(ws + L.best);
+  int *ctl = (int*)(ws + L.ctl), *tickets = (int*)(ws + L.tickets);
+  uint32_t *list = (uint32_t*)(ws + L.list), *ws_grid = (uint32_t*)(ws + L.grid);
+  float* frames = (float*)(ws + L.frames);
   const float res32 = (float)res;
-  if (max_t <= 0) mode = 2;
-
-  if (mode == 1) {
-    // enough (scene, slab) workgroups to fill 256 CUs?  otherwise split each slab's pair list P ways
-    int P = 1;
-    const int64_t wgs = (int64_t)B * s_max;
-    if (wgs < 256) {
-      P = (int)((256 + wgs - 1) / wgs);
-      const int pmax = (max_t + VC_THREADS - 1) / VC_THREADS;
-      if (P > pmax) P = pmax;
-      if (P < 1) P = 1;
-    }
-    const int lds_bytes = VC_LDS_WORDS * 4;
+  const int lds_bytes = VC_LDS_WORDS * 4;
+  int dev = 0, num_cus = 0;
+  if (p.path != VC_GLOBAL) {
     // per device, on first use: the kernels' dynamic-LDS limit (cppf_common.h)
-    int dev = 0, num_cus = 0;
     CPPF_TRY(cppf_device_cus(&dev, &num_cus));
     const void* fns[] = {(const void*)vote_center_slab_kernel<true, false>, (const void*)vote_center_slab_kernel<true, true>,
                          (const void*)vote_center_slab_kernel<false, false>, (const void*)vote_center_slab_kernel<false, true>,
                          (const void*)vote_center_persist_kernel<false>, (const void*)vote_center_persist_kernel<true>};
     for (const void* f : fns) CPPF_TRY(cppf_allow_dynamic_lds(f, dev, lds_bytes));
-    // arcs need >1 slab to pay off and the table in LDS; mode 3 forces the exhaustive sweep (A/B reference)
-    const bool arcs = (exhaustive == 0) && s_max > 1 && num_rots <= VC_MAX_LDS_ROTS && num_rots >= 8;
-    // the persistent work-list kernel serves every batch size of the arcs path; the one-item-per-workgroup launch
-    // remains for the exhaustive A/B mode and on request (mode bit 0x800)
-    const bool persist = arcs && B <= 0xffff && s_max <= 0xffff && (mode_bits & 0x800) == 0;
-    uint32_t* g_use = grid;
-    const int64_t* goff_use = grid_off;
-    if (P > 1 && !persist) {
-      if (!g_use) { g_use = ws_grid; goff_use = nullptr; }
-      // slabs are merged with atomics -> the target must start from zero
-      hipLaunchKernelGGL(grid_zero_kernel, dim3(64, B), dim3(256), 0, st, g_use, goff_use, cells_cap, grids);
-      CPPF_LAUNCH_CHECK();
-    }
-    if (persist) {
-      // Small batches may have fewer slabs than CUs; how many is only known on the device (scene bounds), so the work
-      // list kernel picks the number of parts per slab.  The host only decides whether a split is possible at all:
-      // it costs a zeroed merge area and ticket counters per call, which a 64-scene batch never needs.
-      const int pmax_t = (max_t + VC_THREADS - 1) / VC_THREADS;
-      const int max_parts = (B <= 48) ? (pmax_t < 64 ? (pmax_t < 1 ? 1 : pmax_t) : 64) : 1;
-      if (!frames_ready) {
-        hipLaunchKernelGGL(vote_frames_kernel, dim3((max_t + 255) / 256, B), dim3(256), 0, st, pts, pt_off, idx, k,
-                           tup_off, tr, vote_wt, res32, num_rots, total_tuples, frames);
-        // the work list belongs to the preparation half of the two-call form
-        hipLaunchKernelGGL(vote_worklist_kernel, dim3(1), dim3(1024), 0, st, grids, B, cells_cap, s_max_parts, max_parts,
-                           2 * num_cus, ws_list, ws_ctl);
-        if (max_parts > 1) {
-          hipLaunchKernelGGL(grid_zero_kernel, dim3(64, B), dim3(256), 0, st, ws_grid, (const int64_t*)nullptr, cells_cap,
-                             grids);
-          CPPF_HIP(hipMemsetAsync(ws_tickets, 0, (size_t)B * s_max_parts * 4, st));
-        }
-        CPPF_LAUNCH_CHECK();
+  }
+  // The global path and a split slab path merge with atomics into a zeroed grid: the caller's, else the workspace's.  Both calls
+  // of the two-call form zero it.
+  const bool merge = p.path == VC_GLOBAL || p.P > 1;
+  uint32_t* target = (merge && !grid) ? ws_grid : grid;
+  const int64_t* target_off = (merge && !grid) ? nullptr : grid_off;
+  if (merge) {
+    hipLaunchKernelGGL(grid_zero_kernel, dim3(64, B), dim3(256), 0, st, target, target_off, cells_cap, grids);
+    CPPF_LAUNCH_CHECK();
+  }
+  if (p.prepare && p.path != VC_GLOBAL) {
+    hipLaunchKernelGGL(vote_frames_kernel, dim3((max_t + 255) / 256, B), dim3(256), 0, st, pts, pt_off, idx, k, tup_off, tr, vote_wt,
+                       res32, num_rots, total_tuples, frames);
+    if (p.path == VC_PERSIST) {
+      hipLaunchKernelGGL(vote_worklist_kernel, dim3(1), dim3(1024), 0, st, grids, B, cells_cap, p.s_max_parts, p.max_parts,
+                         2 * num_cus, list, ctl);
+      if (p.max_parts > 1) {
+        hipLaunchKernelGGL(grid_zero_kernel, dim3(64, B), dim3(256), 0, st, ws_grid, (const int64_t*)nullptr, cells_cap, grids);
+        CPPF_HIP(hipMemsetAsync(tickets, 0, (size_t)B * p.s_max_parts * 4, st));
       }
-      if (frames_only) return CPPF_OK;
-      if (vote_wt)
-        hipLaunchKernelGGL(vote_center_persist_kernel<true>, dim3(num_cus), dim3(VC_THREADS), lds_bytes, st, frames,
-                           total_tuples, tup_off, res32, num_rots, cos_tab, sin_tab, grids, grid, grid_off, cells_cap, best,
-                           s_max_parts, ws_list, ws_ctl, max_parts > 1 ? ws_grid : (uint32_t*)nullptr, ws_tickets);
-      else
-        hipLaunchKernelGGL(vote_center_persist_kernel<false>, dim3(num_cus), dim3(VC_THREADS), lds_bytes, st, frames,
-                           total_tuples, tup_off, res32, num_rots, cos_tab, sin_tab, grids, grid, grid_off, cells_cap, best,
-                           s_max_parts, ws_list, ws_ctl, max_parts > 1 ? ws_grid : (uint32_t*)nullptr, ws_tickets);
-      CPPF_LAUNCH_CHECK();
-      hipLaunchKernelGGL(grid_argmax_final_kernel, dim3(B), dim3(64), 0, st, best, s_max_parts, 0, (const int*)ws_ctl, grids, cells_cap, res,
-                         out_argmax, out_peak, out_world);
-      CPPF_LAUNCH_CHECK();
-      return CPPF_OK;
-    }
-    if (!frames_ready) {
-      hipLaunchKernelGGL(vote_frames_kernel, dim3((max_t + 255) / 256, B), dim3(256), 0, st, pts, pt_off, idx, k,
-                         tup_off, tr, vote_wt, res32, num_rots, total_tuples, frames);
-      CPPF_LAUNCH_CHECK();
-    }
-    if (frames_only) return CPPF_OK;
-    {
-      const dim3 gr(B, P, s_max), bl(VC_THREADS);
-#define VC_LAUNCH_SLAB(A, W)                                                                                          \
-  hipLaunchKernelGGL((vote_center_slab_kernel<A, W>), gr, bl, lds_bytes, st, frames, total_tuples, tup_off, res32,       \
-                     num_rots, cos_tab, sin_tab, grids, g_use, goff_use, cells_cap, best, s_max_parts, P)
-      if (arcs) { if (vote_wt) VC_LAUNCH_SLAB(true, true); else VC_LAUNCH_SLAB(true, false); }
-      else      { if (vote_wt) VC_LAUNCH_SLAB(false, true); else VC_LAUNCH_SLAB(false, false); }
-#undef VC_LAUNCH_SLAB
     }
     CPPF_LAUNCH_CHECK();
-    if (P == 1) {
-      hipLaunchKernelGGL(grid_argmax_final_kernel, dim3(B), dim3(64), 0, st, best, s_max_parts, 0, (const int*)nullptr, grids, cells_cap,
-                         res, out_argmax, out_peak, out_world);
-    } else {
-      hipLaunchKernelGGL(grid_argmax_partial_kernel, dim3(VC_ARG_BLOCKS, B), dim3(256), 0, st, g_use, goff_use,
-                         cells_cap, grids, best, s_max_parts);
-      hipLaunchKernelGGL(grid_argmax_final_kernel, dim3(B), dim3(64), 0, st, best, s_max_parts, VC_ARG_BLOCKS, (const int*)nullptr, grids,
-                         cells_cap, res, out_argmax, out_peak, out_world);
-    }
-    CPPF_LAUNCH_CHECK();
-    return CPPF_OK;
   }
-  if (mode == 2) {
-    uint32_t* g_use = grid ? grid : ws_grid;
-    const int64_t* goff_use = grid ? grid_off : nullptr;
-    hipLaunchKernelGGL(grid_zero_kernel, dim3(64, B), dim3(256), 0, st, g_use, goff_use, cells_cap, grids);
-    CPPF_LAUNCH_CHECK();
-    if (max_t > 0) {
-      hipLaunchKernelGGL(vote_center_global_kernel, dim3((max_t + 255) / 256, B), dim3(256), 0, st, pts, pt_off, idx,
-                         k, tup_off, tr, vote_wt, res32, num_rots, cos_tab, sin_tab, grids, g_use, goff_use, cells_cap);
-      CPPF_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(grid_argmax_partial_kernel, dim3(VC_ARG_BLOCKS, B), dim3(256), 0, st, g_use, goff_use,
-                       cells_cap, grids, best, s_max_parts);
-    hipLaunchKernelGGL(grid_argmax_final_kernel, dim3(B), dim3(64), 0, st, best, s_max_parts, VC_ARG_BLOCKS, (const int*)nullptr, grids,
-                       cells_cap, res, out_argmax, out_peak, out_world);
-    CPPF_LAUNCH_CHECK();
-    return CPPF_OK;
-  }
-  snprintf(g_cppf_err, sizeof(g_cppf_err), "cppf_vote_center: unknown mode %d", mode);
-  return CPPF_EINVAL;
+  if (!p.vote) return CPPF_OK;
+  if (p.path == VC_PERSIST)
+    hipLaunchKernelGGL((p.weighted ? vote_center_persist_kernel<true> : vote_center_persist_kernel<false>), dim3(num_cus),
+                       dim3(VC_THREADS), lds_bytes, st, frames, total_tuples, tup_off, res32, num_rots, cos_tab, sin_tab, grids, grid,
+                       grid_off, cells_cap, best, p.s_max_parts, list, ctl, p.max_parts > 1 ? ws_grid : nullptr, tickets);
+  else if (p.path == VC_SLAB)
+    hipLaunchKernelGGL((p.arcs ? (p.weighted ? vote_center_slab_kernel<true, true> : vote_center_slab_kernel<true, false>)
+                               : (p.weighted ? vote_center_slab_kernel<false, true> : vote_center_slab_kernel<false, false>)),
+                       dim3(B, p.P, p.s_max), dim3(VC_THREADS), lds_bytes, st, frames, total_tuples, tup_off, res32, num_rots, cos_tab,
+                       sin_tab, grids, target, target_off, cells_cap, best, p.s_max_parts, p.P);
+  else if (max_t > 0)
+    hipLaunchKernelGGL(vote_center_global_kernel, dim3((max_t + 255) / 256, B), dim3(256), 0, st, pts, pt_off, idx, k, tup_off, tr,
+                       vote_wt, res32, num_rots, cos_tab, sin_tab, grids, target, target_off, cells_cap);
+  CPPF_LAUNCH_CHECK();
+  // first maximum: of the per-slab maxima the vote kernel left or, after an atomic merge, of a pass over the grid
+  if (merge)
+    hipLaunchKernelGGL(grid_argmax_partial_kernel, dim3(VC_ARG_BLOCKS, B), dim3(256), 0, st, target, target_off, cells_cap, grids,
+                       best, p.s_max_parts);
+  hipLaunchKernelGGL(grid_argmax_final_kernel, dim3(B), dim3(64), 0, st, best, p.s_max_parts, merge ? VC_ARG_BLOCKS : 0,
+                     p.path == VC_PERSIST ? ctl : nullptr, grids, cells_cap, res, out_argmax, out_peak, out_world);
+  CPPF_LAUNCH_CHECK();
+  return CPPF_OK;
 }
 
 // =============================================================================================

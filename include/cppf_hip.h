@@ -172,10 +172,12 @@ int cppf_generate_target_pairs(int B, const float* pairs, const int32_t* tup_off
  *     int64 device offsets); pass NULL to keep the accumulator on-chip only.
  *   cells_cap: upper bound on ncell of any scene in the batch (sizes the launch; scenes above it get
  *     flags bit2 and no votes).  mode: 0 = auto, 1 = LDS-slab accumulation (per-slab rotation arcs),
- *     2 = global atomics, 3 = LDS-slab with the exhaustive rotation sweep (A/B reference).
+ *     2 = global atomics, 3 = LDS-slab with the exhaustive rotation sweep (A/B reference).  max_t <= 0 takes the
+ *     global-atomics path whatever the mode.  Bit 0x800 OR-ed into modes 0/1 launches the LDS-slab arcs one
+ *     (scene, slab) item per workgroup instead of through the persistent work list.
  *     Mode 1 may be OR-ed with CPPF_VC_FRAMES_ONLY (compute the per-pair circle frames into the workspace and
  *     return) or CPPF_VC_FRAMES_READY (the workspace already holds them): the two-call form of the same work, for
- *     callers that time or overlap the vote kernel separately.
+ *     callers that time or overlap the vote kernel separately.  Mode 2 ignores both bits and does the whole work.
  *   vote_wt: NULL = every vote counts 1 (the reference).  Otherwise per-pair weights in [0, 4]; a vote adds
  *     round(w*256) to its cell (integer accumulation, deterministic) -- the uncertainty-weighted accumulator of
  *     BASELINE config 5, an extension the reference does not have; w == 1 yields 256 x the reference grid.

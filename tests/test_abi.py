@@ -454,3 +454,118 @@ def test_mlp_launch_validation_return_codes(entry, kw, expected):
     lib = _untraced_lib()
     got = globals()["_call_" + entry](lib, **kw)
     assert got == expected, (entry, kw, got, lib.cppf_last_error_string())
+
+
+# Workspace sizes of the multi-kernel stages, as the layouts gave them before they were written once per stage:
+# (B, total_points) -> (cppf_shot352_workspace_bytes, cppf_shot1344_workspace_bytes)
+_SHOT_WORKSPACE_BYTES = {
+    (1, 0): (0, 0), (4, 0): (0, 0), (0, 100): (0, 0), (-1, 100): (0, 0), (4, -5): (0, 0),
+    (1, 1): (70144, 70656), (1, 7): (83712, 84224), (1, 255): (653056, 661248), (1, 257): (658944, 667648),
+    (1, 10000): (23067136, 23387136), (1, 123457): (284018944, 287970048),
+    (4, 1): (266752, 267264), (4, 257): (855552, 864256), (4, 1000): (2563584, 2595840), (4, 10000): (23263744, 23583744),
+    (64, 1): (4200704, 4201216), (64, 7): (4214272, 4214784), (64, 255): (4783616, 4791808), (64, 1000): (6497536, 6529792),
+    (64, 10000): (27197696, 27517696), (64, 123457): (288149504, 292100608),
+}
+# (B, cells_cap, total_tuples) -> cppf_vote_center_workspace_bytes
+_VC_WORKSPACE_BYTES = {
+    (0, 100, 10): 0, (4, 0, 10): 0, (4, 100, -1): 0,
+    (1, 1, 0): 1536, (1, 1, 999): 49664, (1, 1000, 1): 5632, (1, 36864, 0): 148736, (1, 36865, 999): 197120,
+    (1, 1048576, 1280000): 65635584, (1, 1179649, 1): 4720640,
+    (4, 1, 1): 3840, (4, 1000, 999): 67584, (4, 36864, 1280000): 62033152, (4, 36865, 0): 593408, (4, 1048576, 1): 16780800,
+    (4, 1179649, 999): 18926848,
+    (64, 1, 0): 49664, (64, 1000, 1): 305664, (64, 36864, 999): 9534720, (64, 36865, 1280000): 70926848,
+    (64, 1048576, 0): 268484864, (64, 1048576, 1280000): 329924864, (64, 1179649, 999): 302089216,
+}
+
+
+def test_stage_workspace_bytes_are_pinned():
+    lib = _untraced_lib()
+    for (B, n), (b352, b1344) in _SHOT_WORKSPACE_BYTES.items():
+        assert lib.cppf_shot352_workspace_bytes(B, n) == b352, (B, n)
+        assert lib.cppf_shot1344_workspace_bytes(B, n) == b1344, (B, n)
+    for (B, cells, T), want in _VC_WORKSPACE_BYTES.items():
+        assert lib.cppf_vote_center_workspace_bytes(B, cells, T) == want, (B, cells, T)
+
+
+_SHOT_PARAMS = {
+    "cppf_estimate_normals": ("B", "pts", "pt_off", "n", "normal_r", "out_normal", "ws", "ws_bytes", "flags", "stream"),
+    "cppf_shot352": ("B", "pts", "pt_off", "n", "normal_r", "shot_r", "out_shot", "out_normal", "out_rf", "ws", "ws_bytes", "flags",
+                     "stream"),
+    "cppf_shot352_from_normals": ("B", "pts", "pt_off", "n", "normals", "shot_r", "out_shot", "out_rf", "ws", "ws_bytes", "stream"),
+    "cppf_shot_prepare": ("B", "pts", "pt_off", "n", "normal_r", "shot_r", "out_normal", "ws", "ws_bytes", "flags", "stream"),
+    "cppf_shot_describe": ("B", "pts", "pt_off", "n", "normals", "shot_r", "nan_to_zero", "out_shot", "out_rf", "ws", "ws_bytes",
+                           "stream"),
+    "cppf_shot1344": ("B", "pts", "colors", "pt_off", "n", "normal_r", "shot_r", "out_shot", "out_normal", "ws", "ws_bytes", "flags",
+                      "stream"),
+}
+
+
+def _call_shot(lib, entry, short=0, **kw):
+    """`entry` with valid fake arguments for 1000 points, but for `kw`; the workspace is `short` bytes smaller than it needs."""
+    a = dict(B=2, pts=_X, colors=_AUX2, pt_off=_AUX, n=1000, normal_r=0.02, shot_r=0.03, normals=_IDX, out_shot=_OUT,
+             out_normal=_TAB, out_rf=_B0, nan_to_zero=0, ws=_WQ, flags=0, stream=None)
+    a.update(kw)
+    need = lib.cppf_shot1344_workspace_bytes if entry == "cppf_shot1344" else lib.cppf_shot352_workspace_bytes
+    a["ws_bytes"] = need(a["B"], max(a["n"], 1)) - short
+    return getattr(lib, entry)(*(a[p] for p in _SHOT_PARAMS[entry]))
+
+
+def _call_vc(lib, short=0, **kw):
+    """cppf_vote_center with valid fake arguments (4 scenes, 1000 pairs, mode 1), but for `kw`."""
+    a = dict(B=4, pts=_X, pt_off=_AUX, idx=_IDX, k=5, tup_off=_AUX2, max_t=300, T=1000, tr=_B1, vote_wt=None, res=0.01, num_rots=90,
+             cos_tab=_TAB, sin_tab=_TAP, grids=_B0, grid=None, grid_off=None, cells_cap=200000, mode=1, ws=_WQ, out_argmax=_OUT,
+             out_peak=None, out_world=None)
+    a.update(kw)
+    ws_bytes = lib.cppf_vote_center_workspace_bytes(a["B"], a["cells_cap"], a["T"]) - short
+    return lib.cppf_vote_center(a["B"], a["pts"], a["pt_off"], a["idx"], a["k"], a["tup_off"], a["max_t"], a["T"], a["tr"],
+                                a["vote_wt"], a["res"], a["num_rots"], a["cos_tab"], a["sin_tab"], a["grids"], a["grid"],
+                                a["grid_off"], a["cells_cap"], a["mode"], a["ws"], ws_bytes, a["out_argmax"], a["out_peak"],
+                                a["out_world"], None)
+
+
+_REQUIRED = {
+    "cppf_estimate_normals": ("pts", "pt_off", "out_normal"),
+    "cppf_shot352": ("pts", "pt_off", "out_shot", "out_normal"),
+    "cppf_shot352_from_normals": ("pts", "pt_off", "normals", "out_shot"),
+    "cppf_shot_prepare": ("pts", "pt_off", "out_normal"),
+    "cppf_shot_describe": ("pts", "pt_off", "normals", "out_shot"),
+    "cppf_shot1344": ("pts", "colors", "pt_off", "out_shot", "out_normal"),
+}
+_STAGE_CASES = []
+for _e, _req in _REQUIRED.items():
+    _radii = [r for r in ("normal_r", "shot_r") if r in _SHOT_PARAMS[_e]]
+    _STAGE_CASES += [("shot", _e, {p: None}, _EINVAL) for p in _req]
+    _STAGE_CASES += [("shot", _e, {r: v}, _EINVAL) for r in _radii for v in (0.0, -0.01)]
+    _STAGE_CASES += [
+        ("shot", _e, dict(B=0), _EINVAL),
+        ("shot", _e, dict(n=-1), _EINVAL),
+        ("shot", _e, dict(n=0), _OK),
+        ("shot", _e, dict(n=0, ws=None), _OK),
+        ("shot", _e, dict(short=1), _EINVAL),
+        ("shot", _e, dict(ws=None), _EINVAL),
+    ]
+_STAGE_CASES += [
+    ("vc", None, dict(out_argmax=None), _EINVAL),
+    ("vc", None, dict(grids=None), _EINVAL),
+    ("vc", None, dict(k=1), _EINVAL),
+    ("vc", None, dict(num_rots=0), _EINVAL),
+    ("vc", None, dict(cells_cap=0), _EINVAL),
+    ("vc", None, dict(max_t=1001), _EINVAL),
+    ("vc", None, dict(grid=_AUX2), _EINVAL),
+    ("vc", None, dict(short=1), _EINVAL),
+    ("vc", None, dict(short=1, mode=2), _EINVAL),
+    ("vc", None, dict(ws=None), _EINVAL),
+    ("vc", None, dict(mode=4), _EINVAL),
+    ("vc", None, dict(mode=4 | 0x800), _EINVAL),
+    ("vc", None, dict(mode=0xff), _EINVAL),
+]
+
+
+@pytest.mark.parametrize("kind,entry,kw,expected", _STAGE_CASES,
+                         ids=["%s-%d" % (c[1] or "cppf_vote_center", i) for i, c in enumerate(_STAGE_CASES)])
+def test_shot_and_vote_center_validation_return_codes(kind, entry, kw, expected):
+    """The six SHOT entry points and cppf_vote_center: a null required pointer, a non-positive radius or size, a workspace one
+    byte short and an unknown mode are refused, and no points is a valid call, all before any device work."""
+    lib = _untraced_lib()
+    got = _call_shot(lib, entry, **kw) if kind == "shot" else _call_vc(lib, **kw)
+    assert got == expected, (entry, kw, got, lib.cppf_last_error_string())
