@@ -2,6 +2,7 @@
 """Throughput benchmark of the CPPF++ voting hot path on MI355X.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full      # + counters, CPU baseline, agreement, comparison loops, power
     python bench.py --gpus 8                      # no launcher environment: starts its 8 rank processes itself (one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
@@ -22,7 +23,9 @@ pairs, max over ranks) -- and the CPU-baseline leg (the only code that imports o
 launch (command line, rank processes), counters (rocprofv3 passes), workloads (the Step classes), report (the JSON line + roofline
 arithmetic), evidence (untimed accuracy checks).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields + `roofline` (the dominant kernel -- the tuple MLP: `frac` =
+A plain run sets up, warms up, times the headline loop, writes --dump-outputs and prints ONE JSON line (rank 0) with the driver's
+contract fields (report.report_plain; --workload ensemble / dense64k print their own lines, without counters, CPU baseline and power).
+With --full that line also carries `roofline` (the dominant kernel -- the tuple MLP: `frac` =
 algorithmic float32 flops / time / bf16 MFMA peak, `frac_executed` = the pipe's utilisation including the operand-splitting
 overhead; the longest bandwidth-bound kernel under `roofline.hbm`) + `cpu_baseline` (the oracle timed on the host cores, bounded
 sample) + `collective` + untimed accuracy evidence (`mlp_error_vs_f64`, `bin_flip_rate_vs_expf`).
@@ -449,6 +452,15 @@ class Timer:
         return {"min": 1e3 * self.reduce(mine, torch.distributed.ReduceOp.MIN) / steps, "max": 1e3 * self.reduce(mine) / steps}
 
 
+def plain_run(args):
+    """A plain run (no --full) and a counter pass's child: every leg beside the headline loop switched off -- the counter passes,
+    the CPU baseline with the oracle-agreement workers, the comparison loops, the per-launch power loops, the accuracy evidence.
+    (main() also leaves the power / clock sampler, the two-stream records self-check and the single-stream loop to --full.)"""
+    args.no_reference_order = args.no_native_arith = args.no_f16x2 = args.no_evidence = args.no_counters = True
+    args.no_voxel_density = args.no_prior_variants = args.no_launch_power = True
+    args.cpu_scenes = 0
+
+
 def returned_records(st_):
     """Host copy of the scene records st_'s last step returned to its caller (gathered: every rank's scenes, global scene order)."""
     return st_.pipe.results_to_numpy(st_.all_records)
@@ -584,11 +596,12 @@ def main():
               "or run `python bench.py --gpus %d` without a launcher environment and it starts the ranks itself"
               % (args.gpus, world, args.gpus, args.gpus), file=sys.stderr)
         sys.exit(2)
-    if args.counter_child:              # a child of collect_counters: the bare single-stream loop, nothing else
-        args.single_stream = args.no_reference_order = args.no_native_arith = args.no_f16x2 = args.no_evidence = args.no_counters = True
-        args.no_voxel_density = args.no_prior_variants = args.no_launch_power = True
-        args.cpu_scenes = 0
     COUNTERS = counters.COUNTERS
+    if args.counter_child:              # a child of collect_counters: the bare single-stream loop, nothing else
+        args.single_stream = True
+    if args.counter_child or not args.full:
+        plain_run(args)
+        COUNTERS["reason"] = "a plain run (the counter passes run with --full)"
     profiled = any(k_.startswith(("ROCP_", "ROCPROF")) for k_ in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
     if profiled and not args.no_counters:
         # this process is itself being profiled (the tool's library is loaded and has initialised the GPU): no children from here
@@ -596,7 +609,7 @@ def main():
         COUNTERS["reason"] = "running under a profiler: the counter passes are started by unprofiled runs only"
     # CPU workers of the whole-batch agreement check and the power / clock sampler: fresh children, started before the GPU is touched
     pool = start_oracle_pool(args, rank, world)
-    tel = telemetry.Telemetry.start() if (rank == 0 and not args.counter_child and not profiled) else telemetry.Telemetry()
+    tel = telemetry.Telemetry.start() if (rank == 0 and args.full and not args.counter_child and not profiled) else telemetry.Telemetry()
     counter_children = 0
     if world == 1 and rank == 0 and not args.no_counters and not launch.cdist_forced():
         # BEFORE this process initialises the GPU: fresh children under rocprofv3, one counter pass each (one rank only: a rank of
@@ -722,10 +735,11 @@ def main():
         from cppf2_amd.pipeline import BatchMode
         all_steps = [step] + others
         refs = []
-        for s_ in all_steps:             # every pipeline alone on the current stream: the records of ITS scenes
-            s_.run()
-            torch.cuda.synchronize()
-            refs.append(s_.pipe.results.clone())
+        if args.full:
+            for s_ in all_steps:             # every pipeline alone on the current stream: the records of ITS scenes
+                s_.run()
+                torch.cuda.synchronize()
+                refs.append(s_.pipe.results.clone())
         # The library's batch mode (cppf2_amd.pipeline.BatchMode): one stream per Step, and while it is active the persistent MLP
         # launches leave one CU per shader engine to the other stream's kernels (cppf_mlp_reserve_cus; a queue's workgroups are
         # placed round-robin over the engines, so ONE full engine stalls the other stream's whole launch: 31 reserved CUs change
@@ -743,37 +757,39 @@ def main():
             outputs = returned_records(mode.states[(mode.count - 1) % len(mode.states)])     # the Step of the last timed step
         pair = (all_steps, streams)
         intervals = completion_intervals(ends, group=len(streams))
-        same = bool(all(torch.equal(s_.pipe.results, r_) for s_, r_ in zip(pair[0], refs)))
-        distinct = bool(all(not torch.equal(refs[0], r_) for r_ in refs[1:]))
-        with tel.window("single_stream_loop"):
-            dt_single, _, evs_single, ends_single = timed_loop(args.steps)
-        intervals_single = completion_intervals(ends_single)
-        two = {"streams": ns, "mlp_reserved_cus": args.mlp_reserve_cus, "records_identical_to_single_stream": same, "pipelines_hold_different_scenes": distinct,
-               "note": "steps alternate between two HIP streams with double-buffered state; the pipelines hold different scene batches, and "
-                       "each one's records are compared byte for byte with what the same pipeline produced alone on one stream in this "
-                       "run; per-stage times of the headline are measured on the stage's own stream while the other stream's kernels "
-                       "share the chip (per_stage_ms_two_streams; per_stage_ms: the same stages alone)"}
-        # the same loop (batch mode, same protocol) WITHOUT the teacher prior -- what a trained checkpoint runs: the reference has no
-        # prior (eval.py:225-235); the bench's random-init weights need one for votes to cluster -- and with the prior as a
-        # [T, 6, 32] array (rounds 1-4; ADVICE r5: the generator form removed 983 MB of reads per step from the timed region)
-        if report.FUSED_DRAW and not args.no_prior_variants and world == 1 and not args.array_prior:
-            def prior_variant(form):
+        intervals_single = None
+        if args.full:                    # the records self-check, the single-stream loop and the prior-variant loops
+            same = bool(all(torch.equal(s_.pipe.results, r_) for s_, r_ in zip(pair[0], refs)))
+            distinct = bool(all(not torch.equal(refs[0], r_) for r_ in refs[1:]))
+            with tel.window("single_stream_loop"):
+                dt_single, _, evs_single, ends_single = timed_loop(args.steps)
+            intervals_single = completion_intervals(ends_single)
+            two = {"streams": ns, "mlp_reserved_cus": args.mlp_reserve_cus, "records_identical_to_single_stream": same, "pipelines_hold_different_scenes": distinct,
+                   "note": "steps alternate between two HIP streams with double-buffered state; the pipelines hold different scene batches, and "
+                           "each one's records are compared byte for byte with what the same pipeline produced alone on one stream in this "
+                           "run; per-stage times of the headline are measured on the stage's own stream while the other stream's kernels "
+                           "share the chip (per_stage_ms_two_streams; per_stage_ms: the same stages alone)"}
+            # the same loop (batch mode, same protocol) WITHOUT the teacher prior -- what a trained checkpoint runs: the reference has no
+            # prior (eval.py:225-235); the bench's random-init weights need one for votes to cluster -- and with the prior as a
+            # [T, 6, 32] array (rounds 1-4; ADVICE r5: the generator form removed 983 MB of reads per step from the timed region)
+            if report.FUSED_DRAW and not args.no_prior_variants and world == 1 and not args.array_prior:
+                def prior_variant(form):
+                    for s_ in all_steps:
+                        s_.prior = None if form == "none" else s_.prior_dense
+                        s_.run()
+                    with BatchMode(all_steps, device=dev, reserve_cus=args.mlp_reserve_cus, streams=streams) as m_:
+                        for _ in range(2 * ns):
+                            with m_.next() as s_:
+                                s_.run()
+                        torch.cuda.synchronize()
+                        return timed_loop(args.steps, sample=False, pair=m_)[0]
+                dt_noprior = prior_variant("none")
+                dt_arrayprior = prior_variant("array")
                 for s_ in all_steps:
-                    s_.prior = None if form == "none" else s_.prior_dense
-                    s_.run()
-                with BatchMode(all_steps, device=dev, reserve_cus=args.mlp_reserve_cus, streams=streams) as m_:
-                    for _ in range(2 * ns):
-                        with m_.next() as s_:
-                            s_.run()
-                    torch.cuda.synchronize()
-                    return timed_loop(args.steps, sample=False, pair=m_)[0]
-            dt_noprior = prior_variant("none")
-            dt_arrayprior = prior_variant("array")
-            for s_ in all_steps:
-                s_.prior, s_._prior_dense = s_.teacher, None
-            step.run()
-            torch.cuda.synchronize()
-            assert torch.equal(step.pipe.results, refs[0]), "records changed after the prior-variant loops"
+                    s_.prior, s_._prior_dense = s_.teacher, None
+                step.run()
+                torch.cuda.synchronize()
+                assert torch.equal(step.pipe.results, refs[0]), "records changed after the prior-variant loops"
         del others
     else:
         with tel.window("single_stream_loop"):
@@ -905,7 +921,11 @@ def main():
     step_times = sorted(ev[0][1].elapsed_time(ev[-1][1]) for ev in evs)
 
     failed = False
-    if rank == 0:
+    if rank == 0 and not args.full:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs, args.workload)
+        print(json.dumps(report.report_plain(args, step, world, backend, dt, intervals, stage_ms_2s, rank_ms, affinity)))
+    elif rank == 0:
         if args.dump_outputs:
             dump_outputs(args.dump_outputs, outputs, args.workload)
         cpu = None

@@ -1,5 +1,5 @@
-"""Hardware counters measured IN THE RUN: before bench.py touches the GPU, rank 0 of a one-rank run starts fresh child processes of
-itself under rocprofv3 (the program itself after `--`; counters in their own passes with --kernel-trace only, as
+"""Hardware counters measured IN THE RUN: before bench.py touches the GPU, rank 0 of a one-rank --full run starts fresh child processes
+of itself under rocprofv3 (the program itself after `--`; counters in their own passes with --kernel-trace only, as
 MI355X_MICROARCH.md prescribes): FETCH_SIZE, WRITE_SIZE (HBM bytes per launch = 2 x FETCH_SIZE + WRITE_SIZE KB: the guide's gfx950
 correction) and one pass of SQ counters (VALU / LDS / matrix-pipe activity per kernel).  No rocprofv3, a failed or timed-out pass or
 --no-counters: the fields are null with the reason -- never a number read from profiles/."""

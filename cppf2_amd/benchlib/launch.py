@@ -106,9 +106,15 @@ def parse(argv=None):
                     help="synthetic (default; BASELINE's workload): cppf2_amd.synth surface samples, ~90 neighbours inside the 2 cm "
                          "SHOT support; voxel2mm: the same objects sampled the way eval.py:185-201 produces its clouds (one point per "
                          "2 mm voxel of a dense depth-map-like sampling: ~250 neighbours) -- what the descriptor stage costs on real "
-                         "inputs.  The default run also times the descriptor stage on voxel2mm clouds (value_voxel_density)")
+                         "inputs.  A --full run also times the descriptor stage on voxel2mm clouds (value_voxel_density)")
     ap.add_argument("--no-voxel-density", action="store_true",
-                    help="skip the extra timed loop of the default run on voxel2mm clouds (value_voxel_density)")
+                    help="skip the extra timed loop of a --full run on voxel2mm clouds (value_voxel_density)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline loop: the rocprofv3 counter passes, the CPU baseline and the "
+                         "oracle-agreement workers, the power / clock sampler, the comparison loops (single stream, prior forms, "
+                         "scale-head order, f32-input and f16x2 arithmetic, voxel density), the per-launch power loops, the accuracy "
+                         "evidence and the records self-checks, with the roofline and per-kernel figures they feed (each leg keeps its "
+                         "own --no-* switch).  Default: a plain run -- set-up, warm-up, the timed steps, --dump-outputs, the JSON line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the scene records the headline loop's last step returned (every rank's "
                          "scenes, global scene order) as DIR/<field>.npy, float64 or float32, one file per record field")

@@ -1,5 +1,5 @@
 """What bench.py prints: the JSON line of each workload (rank 0) -- the driver's contract fields, `roofline`, `cpu_baseline`,
-`collective` -- and the arithmetic behind the roofline figures (algorithmic bytes per stage; MLP flops).
+`collective`; a plain run of the headline workload prints the contract fields alone (report_plain) -- and the arithmetic behind the roofline figures (algorithmic bytes per stage; MLP flops).
 
 `roofline` of the headline describes the dominant kernel, the tuple MLP (matrix-core bound).  Its `frac` is ALGORITHMIC work over
 time over the pipe's peak:  2 M K N float32 flops of the network as the reference writes it / launch time / the dense bf16 MFMA peak
@@ -308,6 +308,61 @@ def layer_flops(k, n, proj):
     return 2.0 * n * ((k + 15) // 16 * 16) * (2 if proj else 1) + 2.0 * n * n, 2.0 * n * k * (2 if proj else 1) + 2.0 * n * n
 
 
+def headline_fields(args, step, world, dt):
+    """The contract fields of the headline workload's line and its `config` -- what a plain run prints and a --full run
+    starts its line with.  dt = max-over-ranks seconds of the headline loop's args.steps steps."""
+    from cppf2_amd import models as _models
+    B, N, T, R = step.B, step.N, step.T, args.rots
+    total_scenes = B * world * args.steps
+    return {
+        "metric": "scenes/sec (1/2/4/8 GPU) at 4096 pts x 20k tuples; 5deg5cm match vs ref",
+        "value": total_scenes / dt, "unit": "scenes/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[1]: SHOT model, %d scenes/GPU x %d pts x %d tuples x %d rots, "
+                               "720 sphere bins, res 2 mm, bottle axes; %s clouds; random-init weights + teacher prior; scale head on %s; "
+                               "%s; MLP arithmetic: %s; tuple rows %s"
+                               % (B, N, T, R, step.cloud, "all tuples" if args.eager_scale_head else "the kept pairs only",
+                                  "every step on one HIP stream" if args.single_stream else
+                                  "consecutive steps (different scene batches) alternate between two HIP streams (double-buffered state)",
+                                  "float32 operands split exactly into 3 x bf16, 6 exact products on the bf16 matrix cores, "
+                                  "float32 accumulate (error vs float64 within 3 x a library float32 GEMM's: mlp_error_vs_f64, "
+                                  "tests/test_mlp_split.py)"
+                                  if _models.MLP_ARITH == "split" else
+                                  ("float32 operands as fp16 pairs (22-23 significant bits), 3 products on the fp16 matrix "
+                                   "cores, float32 accumulate (error vs float64 at the library float32 GEMMs' level; NOT exact "
+                                   "products)" if _models.MLP_ARITH == "split16" else "f32-input matrix cores"),
+                                  (("built and gathered inside the first ResLayer's kernel (pair features and descriptors: no per-tuple "
+                                    "array between sampler and MLP)" if ENCODE_FOLDED else
+                                    "gathered inside the first ResLayer's kernel (never written)") if GATHERED_TUPLES
+                                   else "materialised ([T, 360] float32)")
+                                  + ("; bins drawn in the epilogue of the logit head's output layer (logits never written)"
+                                     if FUSED_DRAW else "")),
+                   "scenes_per_gpu": B, "points": N, "tuples": T, "rots": R, "cloud": step.cloud,
+                   "parallelism": "scene-sharded x%d" % world},
+    }
+
+
+def report_plain(args, step, world, backend, dt, intervals, stage_ms, rank_ms=None, affinity=None):
+    """The JSON line of a plain run of the headline workload (no --full; rank 0): the contract fields and what the headline loop
+    itself leaves behind -- the records' hash, the intervals between step completions, the gather's HIP-event time, the poses
+    against the synthetic ground truth.  Nothing here runs the GPU again; the figures that take runs of their own (roofline,
+    per-kernel, CPU baseline, oracle agreement, comparison loops, power) belong to --full."""
+    all_rec = step.pipe.results_to_numpy(step.all_records)
+    sha = __import__("hashlib").sha256(all_rec.tobytes()).hexdigest()
+    line = headline_fields(args, step, world, dt)
+    line.update({
+        "full": False,
+        "step_interval_ms": intervals,
+        "records_gathered": int(all_rec.shape[0]),
+        "records_sha256": sha,
+        "host_cores_of_rank0": affinity,
+        "collective": collective_info(backend, world, step.B, all_rec.shape[0], stage_ms.get("gather", 0.0), rank_ms, sha),
+        "pose_5deg5cm_vs_gt": pose_ok_vs_gt(step.pipe.results_to_numpy(), step.scenes) / step.B,
+    })
+    return line
+
+
 def report_shot(run):
     """The JSON line of the headline workload (rank 0).  `run` = the measurements of bench.main(): args, step, world, backend, dt,
     dt_single, dt_other, dt_native, dt_f16, f16_agreement, two, intervals, intervals_single, stage_ms (kernel durations: single-stream
@@ -410,32 +465,8 @@ def report_shot(run):
     dt_other, dt_native, dt_f16 = run["dt_other"], run["dt_native"], run["dt_f16"]
     step_times = run["step_times"]
     sha = __import__("hashlib").sha256(all_rec.tobytes()).hexdigest()
-    line = {
-        "metric": "scenes/sec (1/2/4/8 GPU) at 4096 pts x 20k tuples; 5deg5cm match vs ref",
-        "value": total_scenes / dt, "unit": "scenes/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[1]: SHOT model, %d scenes/GPU x %d pts x %d tuples x %d rots, "
-                               "720 sphere bins, res 2 mm, bottle axes; %s clouds; random-init weights + teacher prior; scale head on %s; "
-                               "%s; MLP arithmetic: %s; tuple rows %s"
-                               % (B, N, T, R, step.cloud, "all tuples" if args.eager_scale_head else "the kept pairs only",
-                                  "every step on one HIP stream" if args.single_stream else
-                                  "consecutive steps (different scene batches) alternate between two HIP streams (double-buffered state)",
-                                  "float32 operands split exactly into 3 x bf16, 6 exact products on the bf16 matrix cores, "
-                                  "float32 accumulate (error vs float64 within 3 x a library float32 GEMM's: mlp_error_vs_f64, "
-                                  "tests/test_mlp_split.py)"
-                                  if _models.MLP_ARITH == "split" else
-                                  ("float32 operands as fp16 pairs (22-23 significant bits), 3 products on the fp16 matrix "
-                                   "cores, float32 accumulate (error vs float64 at the library float32 GEMMs' level; NOT exact "
-                                   "products)" if _models.MLP_ARITH == "split16" else "f32-input matrix cores"),
-                                  (("built and gathered inside the first ResLayer's kernel (pair features and descriptors: no per-tuple "
-                                    "array between sampler and MLP)" if ENCODE_FOLDED else
-                                    "gathered inside the first ResLayer's kernel (never written)") if GATHERED_TUPLES
-                                   else "materialised ([T, 360] float32)")
-                                  + ("; bins drawn in the epilogue of the logit head's output layer (logits never written)"
-                                     if FUSED_DRAW else "")),
-                   "scenes_per_gpu": B, "points": N, "tuples": T, "rots": R, "cloud": step.cloud,
-                   "parallelism": "scene-sharded x%d" % world},
+    line = headline_fields(args, step, world, dt)
+    line.update({
         # the same run with the scale head on every tuple (the reference's forward order), same loop protocol
         "value_reference_order" if not args.eager_scale_head else "value_kept_pairs_order":
             (total_scenes / dt_other) if dt_other else None,
@@ -480,7 +511,7 @@ def report_shot(run):
         "collective": collective_info(backend, world, B, all_rec.shape[0], stage_ms.get("gather", 0.0), run.get("rank_ms"), sha),
         "roofline": roofline, "cpu_baseline": cpu,
         "pose_5deg5cm_vs_gt": ok / B, "oracle_agreement": agree,
-    }
+    })
     line.update(run.get("evidence") or {})
     # self-checks of the run: a comparison loop whose records differ from the headline's is a failed run, not a footnote
     problems = []

@@ -1,6 +1,6 @@
 #!/bin/bash
 # every bench.py mode once, small: catches report / workload regressions (rc and `ok` per mode)
-S="--steps 2 --warmup 1 --scenes-per-gpu 4 --cpu-scenes 0 --no-counters"
+S="--full --steps 2 --warmup 1 --scenes-per-gpu 4 --cpu-scenes 0 --no-counters"
 i=0
 for F in "" "--single-stream" "--mlp-arith native --no-f16x2" "--mlp-arith split16" "--materialize-tuples" "--eager-scale-head" "--separate-encode" "--cloud voxel2mm" "--workload ensemble" "--workload ensemble --single-stream" "--workload dense64k" "--breakdown --no-voxel-density --no-evidence" "--cpu-scenes 1 --no-voxel-density" "--workload ensemble --cpu-scenes 1"; do
   i=$((i+1))

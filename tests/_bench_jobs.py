@@ -6,6 +6,9 @@ another job or with a test, so nothing in tests/test_multi_rank_gpu.py depends o
 and never touches the GPU itself.
 
     python tests/_bench_jobs.py <dir>      # reads <dir>/jobs.json = [{"tag", "argv", "env"}...]; writes <tag>.out/.err/.rc, then done
+
+Every job runs with --full: the tests read what only a --full run reports (roofline, counters, CPU baseline and agreement, the
+two-stream self-check, `ok`); each job's own --no-* switches still turn its other legs off.
 """
 import json
 import os
@@ -26,7 +29,7 @@ def main(d):
         t0 = time.time()
         with open(os.path.join(d, job["tag"] + ".out"), "w") as out, open(os.path.join(d, job["tag"] + ".err"), "w") as err:
             try:
-                rc = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + job["argv"], env=env, stdout=out, stderr=err,
+                rc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full"] + job["argv"], env=env, stdout=out, stderr=err,
                                     cwd=root, timeout=job.get("timeout", 240)).returncode
             except subprocess.TimeoutExpired:
                 rc = -9

@@ -58,3 +58,57 @@ def test_dump_outputs_writes_every_record_field(tmp_path):
             src = rec["pad_"][:, 0] if n == "pick" else rec[n]
             assert got.dtype in (np.float32, np.float64) and got.shape == src.shape
             assert np.array_equal(got, src) and got.dtype == (np.float32 if src.dtype == np.float32 else np.float64)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_plain_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_plain_run_switches_off_every_leg_beside_the_headline_loop():
+    """Without --full, bench.py runs the headline loop alone: every leg with a --no-* switch is off and the CPU legs take no scenes;
+    --full leaves the defaults (every leg on) as they were."""
+    from cppf2_amd.benchlib import launch
+    bench = _bench_module()
+    legs = ("no_reference_order", "no_native_arith", "no_f16x2", "no_evidence", "no_counters", "no_voxel_density", "no_prior_variants",
+            "no_launch_power")
+    full = launch.parse(["--full"])
+    assert full.full and not any(getattr(full, k) for k in legs) and full.cpu_scenes == 3
+    a = launch.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full
+    bench.plain_run(a)
+    assert all(getattr(a, k) for k in legs) and a.cpu_scenes == 0
+    # the headline loop itself is untouched: its workload, stream mode and K / W
+    assert (a.steps, a.warmup, a.scenes_per_gpu, a.single_stream, a.streams, a.workload) == (7, 2, 64, False, 2, "shot")
+
+
+def test_plain_line_holds_the_contract_fields():
+    """report.report_plain: the contract fields as the --full line states them (value = scenes of the K timed steps / their seconds,
+    ms_per_step, metric, unit, dtype), the records' hash and the poses against the ground truth -- and none of the figures that take
+    runs of their own."""
+    import hashlib
+    import types
+    import numpy as np
+    from cppf2_amd.benchlib import launch, report
+    from cppf2_amd.pipeline import RESULT_DTYPE
+    B, world, steps = 3, 1, 5
+    rec = np.zeros(B, RESULT_DTYPE)
+    rec["R"] = np.eye(3)
+    rec["t"] = [[0.0, 0.0, 0.8], [0.1, 0.0, 0.9], [0.0, 0.3, 0.7]]
+    scenes = [{"t": rec["t"][b] + (0.001 if b < 2 else 0.2), "R": np.eye(3)} for b in range(B)]     # the third one is 20 cm off
+    pipe = types.SimpleNamespace(results_to_numpy=lambda r=None: rec.copy())
+    step = types.SimpleNamespace(B=B, N=4096, T=20000, cloud="synthetic", scenes=scenes, pipe=pipe, all_records=object())
+    args = launch.parse(["--steps", str(steps), "--warmup", "0"])
+    dt = 0.125
+    line = report.report_plain(args, step, world, None, dt, {"median": 12.5}, {"gather": 0.01})
+    assert line == {**report.headline_fields(args, step, world, dt), **line}
+    assert line["metric"] == "scenes/sec (1/2/4/8 GPU) at 4096 pts x 20k tuples; 5deg5cm match vs ref"
+    assert line["value"] == B * world * steps / dt and line["ms_per_step"] == 1e3 * dt / steps
+    assert (line["unit"], line["higher_is_better"], line["dtype"], line["steps"], line["warmup"]) == ("scenes/s", True, "f32", steps, 0)
+    assert line["full"] is False and line["records_gathered"] == B and line["step_interval_ms"] == {"median": 12.5}
+    assert line["records_sha256"] == hashlib.sha256(rec.tobytes()).hexdigest() == line["collective"]["records_sha256"]
+    assert line["pose_5deg5cm_vs_gt"] == 2 / 3
+    assert not {"roofline", "cpu_baseline", "oracle_agreement", "two_streams", "value_single_stream", "ok"} & set(line)
