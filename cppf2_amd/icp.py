@@ -1,0 +1,122 @@
+"""Instance-level pose refinement against the object's mesh: point-to-plane ICP of the observed cloud against samples of the mesh
+surface (cppf_icp_refine, include/cppf_hip.h), the usual last step of instance-level pose from depth.  The reference has no such
+step; its only refinement is `opt` (eval.py:319-355), which aligns the cloud to the network's own predicted pair coordinates.
+
+    model = ModelPoints.from_mesh(render.load_mesh("obj_000015.ply", 0.001))
+    stats = refine(model, pts, pt_off, records, iters=30)          # records' R, t replaced in place
+
+Frame: the model samples are centred on the mesh's bounding-box centre, the centring render.camera_pose applies, so a rendered
+item's (rot, trans) -- pc = rot (v - centre) + trans at scale 1 -- is the record pose (R, t) under which the view and the samples
+coincide.  The defaults are chosen in DESIGN.md section 13.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, ops, shot
+from ._lib import CppfError
+
+_L = _lib.load()
+
+COUNT = 4096
+ITERS = 30
+MAX_DIST = (0.05, 0.005)         # (d0, d1) metres: inlier distance of the first and of the last iteration
+REFINED = 16                     # CppfSceneResult.flags bit4
+
+
+class ModelPoints:
+    """pts / nrm float32 [M,3] (model frame, centred on the bounding-box centre) and the centre itself (float64 [3]); device
+    copies are made once per device and kept."""
+
+    def __init__(self, pts, nrm, centre):
+        self.pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 3)
+        self.nrm = np.ascontiguousarray(nrm, dtype=np.float32).reshape(-1, 3)
+        if self.pts.shape != self.nrm.shape or not len(self.pts):
+            raise ValueError("ModelPoints: pts and nrm must be non-empty [M,3] arrays of one shape")
+        self.centre = np.asarray(centre, dtype=np.float64).reshape(3)
+        self._dev = {}
+
+    @classmethod
+    def from_mesh(cls, mesh, count=COUNT, seed=0):
+        """`count` points on the surface of a render.Mesh, area-weighted (numpy Generator(seed), float64), each with its
+        triangle's unit normal."""
+        v, f = mesh.verts, mesh.faces.astype(np.int64)
+        a, b, c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+        cr = np.cross(b - a, c - a)
+        area2 = np.linalg.norm(cr, axis=1)
+        if not area2.sum() > 0:
+            raise ValueError("ModelPoints.from_mesh: the mesh has no triangle of non-zero area")
+        rng = np.random.default_rng(seed)
+        tri = rng.choice(len(f), size=int(count), p=area2 / area2.sum())
+        r1, r2 = rng.random(int(count)), rng.random(int(count))
+        s = np.sqrt(r1)
+        p = (1.0 - s)[:, None] * a[tri] + (s * (1.0 - r2))[:, None] * b[tri] + (s * r2)[:, None] * c[tri]
+        bnd = mesh.bounds
+        centre = (bnd[0] + bnd[1]) / 2
+        return cls(p - centre, cr[tri] / area2[tri][:, None], centre)
+
+    def device(self, dev):
+        key = str(dev)
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.pts).to(dev), torch.from_numpy(self.nrm).to(dev))
+        return self._dev[key]
+
+
+_WS = {}                 # (device index, stream) -> workspace tensor
+WS_CACHE_MAX = 8
+
+
+def _workspace(B, max_n, dev):
+    key = shot._key(dev)
+    ws = _WS.pop(key, None)
+    need = _L.cppf_icp_workspace_bytes(B, max_n)
+    if need < 0:
+        raise CppfError("cppf_icp_workspace_bytes: invalid sizes B=%d max_n=%d" % (B, max_n))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _WS[key] = ws
+    while len(_WS) > WS_CACHE_MAX:
+        del _WS[next(iter(_WS))]
+    return ws
+
+
+def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST):
+    """Refines the poses of `results` in place against `model` (cppf_icp_refine) and returns the stats float32 [B,4]: inliers
+    of the last iteration, their RMS point-to-plane distance, inliers / n, iterations that changed the pose.
+
+    pts: float32 [N,3] camera-frame points of the B instances, instance b = pts[pt_off[b]:pt_off[b+1]]; pt_off: int [B+1].
+    results: the records, either a device uint8 [B,160] tensor (a VotingPipeline's results / selected; stats come back as a
+    device tensor) or a pipeline.RESULT_DTYPE array (stats come back as a NumPy array).  Records flagged empty (flags bit0)
+    are left as they are; every other one gets flags bit4."""
+    dev = ops._dev()
+    host_records = isinstance(results, np.ndarray)
+    if host_records:
+        rec = torch.from_numpy(np.frombuffer(results.tobytes(), dtype=np.uint8).reshape(-1, 160).copy()).to(dev)
+    else:
+        rec = results
+        if rec.dtype != torch.uint8 or rec.dim() != 2 or rec.shape[1] != 160 or not rec.is_contiguous() or rec.device != dev:
+            raise CppfError("icp.refine: results must be a contiguous uint8 [B,160] tensor on %s" % dev)
+    off_h = (pt_off.cpu().numpy() if torch.is_tensor(pt_off) else np.asarray(pt_off)).astype(np.int64).reshape(-1)
+    B = off_h.size - 1
+    if B != rec.shape[0]:
+        raise CppfError("icp.refine: %d records for %d instances" % (rec.shape[0], B))
+    max_n = max(int(np.diff(off_h).max()) if B > 0 else 0, 1)
+    pts = ops._t(pts, torch.float32, dev).reshape(-1, 3).contiguous()
+    if pts.shape[0] < off_h[-1]:
+        raise CppfError("icp.refine: pt_off reaches %d points, pts holds %d" % (off_h[-1], pts.shape[0]))
+    off = pt_off.to(device=dev, dtype=torch.int32).contiguous() if torch.is_tensor(pt_off) else \
+        torch.from_numpy(off_h.astype(np.int32)).to(dev)
+    mp, mn = model.device(dev)
+    stats = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    ws = _workspace(B, max_n, dev)
+    d0, d1 = (float(x) for x in max_dist)
+    _lib.check(_L.cppf_icp_refine(B, ops._p(pts), ops._p(off), max_n, ops._p(mp), ops._p(mn), mp.shape[0], int(iters),
+                                  C.c_float(d0), C.c_float(d1), ops._p(rec), ops._p(stats), ops._p(ws), ws.numel(),
+                                  ops._stream()), "cppf_icp_refine")
+    if host_records:
+        results[...] = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=results.dtype).reshape(results.shape)
+        return stats.cpu().numpy()
+    return stats

@@ -19,6 +19,9 @@ What the image cannot provide is stated, not faked:
   * the Adam/lietorch refinement (eval.py:319-355, `opt`) runs as one HIP kernel per batch
     (cppf_refine_pose); lietorch is absent, so its semantics are restated from the published algorithm and pinned
     only by the oracle (parity unpinned).
+  * `--data=depth --mesh=<ply|obj> [--mesh_scale=1.0] --icp_iters=N` (N > 0) refines the selected pose of the instance by N
+    point-to-plane ICP iterations against samples of the object's mesh (cppf2_amd.icp, cppf_icp_refine; not in the
+    reference), after the ensemble selection and `opt`; the report gains the ICP stats.  --icp_iters=0 (default): off.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import json
@@ -480,8 +483,15 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          use_grounded_sam=False, geo_branch=True, visual_branch=True, data="synthetic", num_scenes=8, num_points=4096,
          category=None, categories=None, seed=0, ckpt_dir=None, ckpt_shot=None, ckpt_dino=None, depth=None, mask=None,
          intrinsics=None, depth_scale=1000.0, out=None, out_pkl=None, log_dir=None, data_root="NOCS/real_test", out_dir=None,
-         desc_npz=None, batch_instances=16, max_images=None):
+         desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0):
     custom = False
+    icp_iters = int(icp_iters)
+    if icp_iters > 0 and (data != "depth" or not mesh):
+        raise ValueError("--icp_iters > 0 refines against the object's mesh: it needs --data=depth and --mesh")
+    icp_model = None
+    if icp_iters > 0:
+        from cppf2_amd import icp, render
+        icp_model = icp.ModelPoints.from_mesh(render.load_mesh(mesh, mesh_scale))
     if categories is None:
         if category:
             categories = [category]
@@ -547,11 +557,16 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                          num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
                          up_sym, priors, scale_priors=scale_priors)
         cls_id = category2id.get(cat, 0)
+        icp_stats = None
+        if icp_model is not None:
+            # after the ensemble selection (and `opt`): the selected record of each instance against the mesh
+            icp_stats = icp.refine(icp_model, r["pts"], np.cumsum([0] + [s["pc"].shape[0] for s in scenes]), r["selected"],
+                                   iters=icp_iters)
         for b in range(B):
             RT, sc = np.eye(4), np.ones(3)                                      # eval.py:143-144 defaults
             item = dict(scene=scene_ids[b], category=cat, model=None)
             if r["pick"][b] >= 0:                                               # eval.py:367-372
-                rec = r["records"][r["pick"][b]][b]
+                rec = r["records"][r["pick"][b]][b] if icp_stats is None else r["selected"][b]
                 RT[:3, :3] = rec["R"] * r["scale_norm"][b]
                 RT[:3, 3] = rec["t"]
                 if r["scale_norm"][b] > 0:
@@ -559,6 +574,9 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                 item.update(model=["dino", "shot"][r["pick"][b]], loss=float(r["best"][b]),
                             losses=[float(r["losses"][0][b]), float(r["losses"][1][b])], pred_RT=RT.tolist(),
                             pred_scale=sc.tolist())
+                if icp_stats is not None:
+                    st = icp_stats[b]
+                    item["icp"] = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
                 if scenes[b]["R"] is not None:
                     item["tr_err_cm"] = float(np.linalg.norm(rec["t"] - scenes[b]["t"]) * 100)
                     item["rot_err_deg"] = geometry.rot_err_deg(rec["R"], scenes[b]["R"], up_sym)
@@ -575,6 +593,9 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
 
     report = dict(categories=categories, instances=len(summary),
                   opt_refinement="100 Adam steps (cppf_refine_pose)" if opt else "off", results=summary)
+    if icp_model is not None:
+        report["icp_refinement"] = "%d point-to-plane ICP iterations against %s (cppf_icp_refine)" % (icp_iters, os.path.basename(mesh))
+        report["icp"] = [s_["icp"] for s_ in summary if "icp" in s_]
     if len(categories) == 1:
         report["category"] = categories[0]
     scored = [s for s in summary if "rot_err_deg" in s]

@@ -344,6 +344,25 @@ int cppf_render_depth(int B, const float* verts, int64_t num_verts, const int32_
                       float* depth, int32_t* tri_id, int64_t* status, void* workspace, int64_t workspace_bytes,
                       int64_t list_capacity, void* stream);
 
+/* ---- instance-level refinement against the object's mesh (after 8f-1; the reference has no such step) ---------------
+ * Point-to-plane ICP of B observed clouds against one model, all iterations enqueued by one call (2 launches per iteration,
+ * no host synchronisation).  pts float32[pt_off[B],3] (camera frame, as cppf_backproject writes them), pt_off int32[B+1];
+ * max_n >= every instance's point count (points past it are not read).  model_pts / model_nrm float32[M,3]: samples of the
+ * model's surface and their unit normals, in the frame where  p = R m + t.  results: the pose (R row-major, t) comes in and
+ * goes out in place, float64; flags bit4 is set on every refined record; records with flags bit0 (empty scene) are left as
+ * they are; scale is not read or changed.  Per iteration k: each point q = R^T (p - t) (float32) is paired with its nearest
+ * model sample (lowest index on ties), an inlier when |q - m| <= d_k = d0 (d1/d0)^(k/(iters-1)) (d0 when iters = 1), and the
+ * 6x6 normal equations of e = n.(q - m), J = [q x n, n] are solved by Cholesky (float64): R <- R Rodrigues(w)^T,
+ * t <- t - R v.  Fewer than 6 inliers or a pivot <= 0: that iteration leaves the pose.  The exact order of the float32
+ * operations is stated in cppf2_amd/csrc/cppf_icp.hip.  No atomics: the result of an instance does not depend on the batch.
+ * stats float32[B,4]: inliers of the last iteration, their RMS of e, inliers / n, iterations that changed the pose.
+ * workspace: cppf_icp_workspace_bytes(B, max_n) bytes (< 0 for invalid sizes; CPPF_ECAPACITY when too small).
+ * B <= 65535, M > 0, iters > 0, 0 < d1 <= d0. */
+int64_t cppf_icp_workspace_bytes(int B, int max_n);
+int cppf_icp_refine(int B, const float* pts, const int32_t* pt_off, int max_n, const float* model_pts, const float* model_nrm,
+                    int M, int iters, float d0, float d1, CppfSceneResult* results, float* stats, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* DINO-branch feature plumbing: replaces interpolate_features (dataset.py:40-59) = grid_sample
  * (bilinear, zeros padding, align_corners=False) of the patch-token map desc at the pixel centres of pts float32[n,2]
  * (x, y), then L2 normalisation over the C channels.  desc is addressed as desc[c*stride_c + y*stride_y + x*stride_x]
