@@ -6,32 +6,52 @@
 //              CppfSceneResult) is cast to float32 once; the point goes into the model frame, the nearest model sample is found
 //              by brute force over the M samples (positions streamed through LDS in tiles of ICP_TILE; the winner's normal is
 //              read from global memory after the search, it is the only one needed), and an inlier adds its point-to-plane
-//              terms (float64) to 29 block sums: the 21 upper-triangle terms of J^T J (row-major), the 6 of J^T e, the inlier
-//              count and sum e^2.  Wavefront sums on the DPP path (a fixed butterfly), then the 4 wavefronts' sums added in
+//              terms (float64) to 30 block sums: the 21 upper-triangle terms of J^T J (row-major), the 6 of J^T e, the inlier
+//              count, sum e^2 and sum |q|^2.  Wavefront sums on the DPP path (a fixed butterfly), then the 4 wavefronts' sums added in
 //              wavefront order; each block writes its own workspace slot -- no atomics, so nothing depends on scheduling.
-//   icp_solve  one wavefront per instance: the block slots summed in block order, A x = -b solved by Cholesky (float64), the
-//              pose updated in place:  dR = Rodrigues(w), R <- R dR^T, t <- t - R v  (x = [w, v], the new R in the second).
-//              Fewer than 6 inliers or a pivot <= 0 (or NaN): the pose does not change in that iteration.
+//   icp_solve  one wavefront per instance: the block slots summed in block order, then the minimum-norm Gauss-Newton step of
+//              A x = -b (float64, lane 0, matrices in LDS): the unknowns scaled to one unit, S = diag(1/L, 1/L, 1/L, 1, 1, 1) with
+//              L^2 = sum |q|^2 / inliers (a rotation times the RMS lever arm is a length), the eigen-decomposition of S A S by
+//              cyclic Jacobi, and the pseudo-inverse over the eigenvalues above ICP_TAU * lambda_max; x = S y.  Then the pose is
+//              updated in place:  dR = Rodrigues(w), R <- R dR^T, t <- t - R v  (x = [w, v], the new R in the second).
+//              Fewer than 6 inliers, no eigenvalue kept (rank 0) or a zero or non-finite step: the pose does not change.
 //
+// ICP_TAU = 1e-9.  Measured spectra of S A S (eigenvalue / lambda_max, float64): directions that only
+// rounding constrains -- a plate's in-plane translation and spin, a smooth cylinder's spin and slide, a smooth sphere's
+// rotation -- sit at <= 1.2e-13 (exactly 0 where the normals are exactly axis-aligned); the weakest genuine constraints are a
+// faceted sphere cap's rotation (1.1e-6 to 4.7e-5 over poses, 192 segments), a 128-facet cylinder's spin (1.8e-4) and the
+// fixture's views (>= 0.12): tau is three orders below the weakest and four above the rounding level.
+// A rank-deficient system therefore corrects what it observes and leaves the other directions exactly where they were (the
+// step has no component along them), instead of dividing by a rounding-level pivot.
 // Arithmetic (tests/icp_ref.py restates it in NumPy; the build's -ffp-contract=off keeps every operation where it is written):
 //   float32:  Rf = (float)R, tf = (float)t, d = p - tf,
 //             q.x = (Rf00*d.x + Rf10*d.y) + Rf20*d.z,  q.y = (Rf01*d.x + Rf11*d.y) + Rf21*d.z,  q.z = (Rf02*d.x + Rf12*d.y) + Rf22*d.z
 //             d2(j) = ((q.x - m.x)^2 + (q.y - m.y)^2) + (q.z - m.z)^2;  nearest = the lowest j of the smallest d2 (strict '<' in
 //             index order; a NaN d2 never wins); inlier <=> d2 <= dk * dk  (dk = (float)d_k, the product in float32)
 //   float64:  r = q - m,  e = (n.x*r.x + n.y*r.y) + n.z*r.z,  J = [q x n, n],  (q x n) = (q.y*n.z - q.z*n.y, q.z*n.x - q.x*n.z,
-//             q.x*n.y - q.y*n.x) -- q, m, n widened from float32
+//             q.x*n.y - q.y*n.x), |q|^2 = (q.x*q.x + q.y*q.y) + q.z*q.z -- q, m, n widened from float32
 //   schedule: d_k = d0 * (d1 / d0)^(k / (iters - 1)) in float64 on the host (d_k = d0 when iters = 1)
 //   Rodrigues: th2 = (w0^2 + w1^2) + w2^2; a = sin(th)/th, c = (1 - cos(th))/th2 (a = 1 - th2/6, c = 0.5 - th2/24 when th2 < 1e-8);
 //             dR_ij = (delta_ij * (1 - c*th2) + a*K_ij) + (c*w_i)*w_j,  K = [w]x
+//   solve:    L2 = sum|q|^2 / cnt, r = L2 > 0 ? 1 / sqrt(L2) : 0, s = (r, r, r, 1, 1, 1), As_ij = (s_i * A_ij) * s_j, V = I;
+//             sweeps (at most ICP_SWEEPS, until one rotates nothing) over (p, q) = (0,1), (0,2), .. (4,5): skip when a_pq == 0
+//             or |a_pq| <= ICP_JEPS * (|a_pp| + |a_qq|) (a_pq, a_qp set to 0); else th = (a_qq - a_pp) / (2 a_pq),
+//             t = sgn(th) / (|th| + sqrt(th*th + 1)) (sgn(0) = 1), c = 1 / sqrt(t*t + 1), s = t * c, a_pp -= t a_pq, a_qq += t a_pq,
+//             a_pq = a_qp = 0, for k != p, q: a_kp = a_pk = c a_kp - s a_kq, a_kq = a_qk = s a_kp + c a_kq (old values), and for
+//             every k: V_kp = c V_kp - s V_kq, V_kq = s V_kp + c V_kq.  lmax = the largest a_ii; i in ascending order with
+//             a_ii > ICP_TAU * lmax: g = sum_j V_ji (s_j b_j) (j ascending, from 0), y_j += (-g / a_ii) V_ji; x_j = s_j y_j.
 // Stats per instance (float32, written every iteration, final after the last): [0] inliers of the last match, [1] sqrt(sum e^2 /
-// inliers) of that match (0 without inliers), [2] inliers / n, [3] iterations that changed the pose.
+// inliers) of that match (0 without inliers), [2] inliers / n, [3] iterations with a non-zero step (those that moved the pose).
 #include "cppf_common.h"
 
 #define ICP_THREADS 256
 #define ICP_TILE 1024          // model samples per LDS tile (16 KiB of float4)
-#define ICP_TERMS 29           // 21 (J^T J upper) + 6 (J^T e) + count + sum e^2
+#define ICP_TERMS 30           // 21 (J^T J upper) + 6 (J^T e) + count + sum e^2 + sum |q|^2
 #define ICP_SLOT 32            // doubles per block slot
 #define ICP_REFINED 16         // CppfSceneResult.flags bit4: pose refined by ICP
+#define ICP_TAU 1e-9           // eigenvalues of S A S at or below ICP_TAU * lambda_max are dropped (unobservable directions)
+#define ICP_JEPS 1e-17         // Jacobi: an off-diagonal entry this small next to its two diagonal entries counts as 0
+#define ICP_SWEEPS 16          // Jacobi sweeps at most (measured: 3-8, the last of them rotating nothing)
 
 __global__ __launch_bounds__(ICP_THREADS) void icp_match_kernel(const float* __restrict__ pts, const int32_t* __restrict__ pt_off,
                                                                 int max_n, int nblk, const float* __restrict__ model_pts,
@@ -105,6 +125,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_match_kernel(const float* __r
     for (int a = 0; a < 6; ++a) v[21 + a] = J[a] * e;
     v[27] = 1.0;
     v[28] = e * e;
+    v[29] = (Qx * Qx + Qy * Qy) + Qz * Qz;
   }
   const int w = threadIdx.x / CPPF_WAVE;
 #pragma unroll
@@ -127,7 +148,7 @@ __global__ __launch_bounds__(CPPF_WAVE) void icp_solve_kernel(const int32_t* __r
                                                               const double* __restrict__ part, int k, int iters,
                                                               CppfSceneResult* __restrict__ results, float* __restrict__ stats) {
   __shared__ double s_t[ICP_SLOT];
-  __shared__ double s_A[36], s_L[36], s_y[6], s_x[6], s_K[9], s_R[9], s_dR[9], s_Rn[9];
+  __shared__ double s_A[36], s_V[36], s_s[6], s_y[6], s_x[6], s_K[9], s_R[9], s_dR[9], s_Rn[9];
   const int b = blockIdx.x;
   CppfSceneResult& rec = results[b];
   float* st = stats + 4 * (int64_t)b;
@@ -148,40 +169,77 @@ __global__ __launch_bounds__(CPPF_WAVE) void icp_solve_kernel(const int32_t* __r
   const double cnt = s_t[27], sse = s_t[28];
   bool ok = cnt >= 6.0;
   if (ok) {
+    const double L2 = s_t[29] / cnt;
+    const double r = L2 > 0.0 ? 1.0 / sqrt(L2) : 0.0;
+    for (int j = 0; j < 6; ++j) s_s[j] = j < 3 ? r : 1.0;
     int o = 0;
     for (int a = 0; a < 6; ++a)
       for (int c = a; c < 6; ++c) {
-        s_A[a * 6 + c] = s_t[o];
-        s_A[c * 6 + a] = s_t[o];
+        const double v = (s_s[a] * s_t[o]) * s_s[c];
+        s_A[a * 6 + c] = v;
+        s_A[c * 6 + a] = v;
+        s_V[a * 6 + c] = a == c ? 1.0 : 0.0;
+        s_V[c * 6 + a] = a == c ? 1.0 : 0.0;
         ++o;
       }
-    for (int j = 0; j < 6 && ok; ++j) {              // A = L L^T
-      double s = s_A[j * 6 + j];
-      for (int c = 0; c < j; ++c) s -= s_L[j * 6 + c] * s_L[j * 6 + c];
-      if (!(s > 0.0)) {
-        ok = false;
-        break;
-      }
-      const double d = sqrt(s);
-      s_L[j * 6 + j] = d;
-      for (int r = j + 1; r < 6; ++r) {
-        double u = s_A[r * 6 + j];
-        for (int c = 0; c < j; ++c) u -= s_L[r * 6 + c] * s_L[j * 6 + c];
-        s_L[r * 6 + j] = u / d;
-      }
+    for (int sweep = 0; sweep < ICP_SWEEPS; ++sweep) {       // cyclic Jacobi: S A S = V diag(a_ii) V^T
+      bool rotated = false;
+      for (int p = 0; p < 5; ++p)
+        for (int q = p + 1; q < 6; ++q) {
+          const double apq = s_A[p * 6 + q], app = s_A[p * 7], aqq = s_A[q * 7];
+          if (apq == 0.0) continue;
+          if (fabs(apq) <= ICP_JEPS * (fabs(app) + fabs(aqq))) {
+            s_A[p * 6 + q] = 0.0;
+            s_A[q * 6 + p] = 0.0;
+            continue;
+          }
+          const double th = (aqq - app) / (2.0 * apq);
+          const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
+          const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+          s_A[p * 7] = app - t * apq;
+          s_A[q * 7] = aqq + t * apq;
+          s_A[p * 6 + q] = 0.0;
+          s_A[q * 6 + p] = 0.0;
+          for (int k = 0; k < 6; ++k) {
+            if (k != p && k != q) {
+              const double akp = s_A[k * 6 + p], akq = s_A[k * 6 + q];
+              const double np_ = c * akp - sn * akq, nq = sn * akp + c * akq;
+              s_A[k * 6 + p] = np_;
+              s_A[p * 6 + k] = np_;
+              s_A[k * 6 + q] = nq;
+              s_A[q * 6 + k] = nq;
+            }
+            const double vkp = s_V[k * 6 + p], vkq = s_V[k * 6 + q];
+            s_V[k * 6 + p] = c * vkp - sn * vkq;
+            s_V[k * 6 + q] = sn * vkp + c * vkq;
+          }
+          rotated = true;
+        }
+      if (!rotated) break;
     }
+    double lmax = 0.0;
+    for (int i = 0; i < 6; ++i)
+      if (s_A[i * 7] > lmax) lmax = s_A[i * 7];
+    for (int j = 0; j < 6; ++j) s_y[j] = 0.0;
+    int rank = 0;
+    for (int i = 0; i < 6; ++i) {                            // y = -sum_kept V_i (V_i . S b) / lambda_i
+      const double lam = s_A[i * 7];
+      if (!(lam > ICP_TAU * lmax)) continue;
+      double g = 0.0;
+      for (int j = 0; j < 6; ++j) g += s_V[j * 6 + i] * (s_s[j] * s_t[21 + j]);
+      const double f = -g / lam;
+      for (int j = 0; j < 6; ++j) s_y[j] += f * s_V[j * 6 + i];
+      ++rank;
+    }
+    bool nonzero = false, finite = true;
+    for (int j = 0; j < 6; ++j) {
+      s_x[j] = s_s[j] * s_y[j];
+      nonzero = nonzero || s_x[j] != 0.0;
+      finite = finite && fabs(s_x[j]) < __builtin_inf();
+    }
+    ok = rank > 0 && nonzero && finite;
   }
   if (ok) {
-    for (int r = 0; r < 6; ++r) {                    // L y = -b
-      double u = -s_t[21 + r];
-      for (int c = 0; c < r; ++c) u -= s_L[r * 6 + c] * s_y[c];
-      s_y[r] = u / s_L[r * 6 + r];
-    }
-    for (int r = 5; r >= 0; --r) {                   // L^T x = y
-      double u = s_y[r];
-      for (int c = r + 1; c < 6; ++c) u -= s_L[c * 6 + r] * s_x[c];
-      s_x[r] = u / s_L[r * 6 + r];
-    }
     const double w0 = s_x[0], w1 = s_x[1], w2 = s_x[2];
     const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
     double a, c;

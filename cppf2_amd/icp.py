@@ -90,7 +90,8 @@ def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST):
     pts: float32 [N,3] camera-frame points of the B instances, instance b = pts[pt_off[b]:pt_off[b+1]]; pt_off: int [B+1].
     results: the records, either a device uint8 [B,160] tensor (a VotingPipeline's results / selected; stats come back as a
     device tensor) or a pipeline.RESULT_DTYPE array (stats come back as a NumPy array).  Records flagged empty (flags bit0)
-    are left as they are; every other one gets flags bit4."""
+    are left as they are; every other one gets flags bit4.  B = 0 (pt_off of one entry) is an empty batch: nothing is launched
+    and the stats are an empty [0,4] array (device tensor or NumPy, as above)."""
     dev = ops._dev()
     host_records = isinstance(results, np.ndarray)
     if host_records:
@@ -103,7 +104,9 @@ def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST):
     B = off_h.size - 1
     if B != rec.shape[0]:
         raise CppfError("icp.refine: %d records for %d instances" % (rec.shape[0], B))
-    max_n = max(int(np.diff(off_h).max()) if B > 0 else 0, 1)
+    if B == 0:
+        return np.zeros((0, 4), dtype=np.float32) if host_records else torch.zeros((0, 4), dtype=torch.float32, device=dev)
+    max_n = max(int(np.diff(off_h).max()), 1)
     pts = ops._t(pts, torch.float32, dev).reshape(-1, 3).contiguous()
     if pts.shape[0] < off_h[-1]:
         raise CppfError("icp.refine: pt_off reaches %d points, pts holds %d" % (off_h[-1], pts.shape[0]))

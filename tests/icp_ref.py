@@ -1,6 +1,9 @@
 """NumPy restatement of cppf_icp_refine (cppf2_amd/csrc/cppf_icp.hip): the float32 transform and distances element by element in
-the kernel's order, the nearest sample by the lowest index, the normal equations, Cholesky solve and pose update in float64.
+the kernel's order, the nearest sample by the lowest index, the normal equations, the rank-aware solve (cyclic Jacobi, minimum-norm
+step) and the pose update in float64.
 One instance per call.  Test infrastructure only."""
+import math
+
 import numpy as np
 
 F32 = np.float32
@@ -45,35 +48,65 @@ def nearest(q, mp):
     return idx, d2
 
 
-def _cholesky_solve(A, b):
-    """x of A x = -b (6x6, the kernel's loops); None when a pivot is <= 0 or NaN."""
-    L = np.zeros((6, 6))
-    for j in range(6):
-        s = A[j, j]
-        for c in range(j):
-            s -= L[j, c] * L[j, c]
-        if not s > 0.0:
-            return None
-        d = np.sqrt(s)
-        L[j, j] = d
-        for r in range(j + 1, 6):
-            u = A[r, j]
-            for c in range(j):
-                u -= L[r, c] * L[j, c]
-            L[r, j] = u / d
-    y = np.zeros(6)
-    for r in range(6):
-        u = -b[r]
-        for c in range(r):
-            u -= L[r, c] * y[c]
-        y[r] = u / L[r, r]
-    x = np.zeros(6)
-    for r in range(5, -1, -1):
-        u = y[r]
-        for c in range(r + 1, 6):
-            u -= L[c, r] * x[c]
-        x[r] = u / L[r, r]
-    return x
+TAU = 1e-9          # ICP_TAU
+JEPS = 1e-17        # ICP_JEPS
+SWEEPS = 16         # ICP_SWEEPS
+
+
+def _min_norm_solve(A, b, qq, cnt):
+    """x of A x = -b (6x6) by the kernel's loops: the scale s = (r, r, r, 1, 1, 1), r = 1 / RMS |q| of the inliers, cyclic Jacobi
+    of S A S, the pseudo-inverse over the eigenvalues above TAU * lambda_max.  Returns (x, rank)."""
+    L2 = qq / cnt
+    r = 1.0 / math.sqrt(L2) if L2 > 0.0 else 0.0
+    s = [r, r, r, 1.0, 1.0, 1.0]
+    a = [[(s[i] * float(A[i, j])) * s[j] for j in range(6)] for i in range(6)]
+    V = [[1.0 if i == j else 0.0 for j in range(6)] for i in range(6)]
+    for _ in range(SWEEPS):
+        rotated = False
+        for p in range(5):
+            for q in range(p + 1, 6):
+                apq, app, aqq = a[p][q], a[p][p], a[q][q]
+                if apq == 0.0:
+                    continue
+                if abs(apq) <= JEPS * (abs(app) + abs(aqq)):
+                    a[p][q] = a[q][p] = 0.0
+                    continue
+                th = (aqq - app) / (2.0 * apq)
+                t = (1.0 if th >= 0.0 else -1.0) / (abs(th) + math.sqrt(th * th + 1.0))
+                c = 1.0 / math.sqrt(t * t + 1.0)
+                sn = t * c
+                a[p][p] = app - t * apq
+                a[q][q] = aqq + t * apq
+                a[p][q] = a[q][p] = 0.0
+                for k in range(6):
+                    if k != p and k != q:
+                        akp, akq = a[k][p], a[k][q]
+                        a[k][p] = a[p][k] = c * akp - sn * akq
+                        a[k][q] = a[q][k] = sn * akp + c * akq
+                    vkp, vkq = V[k][p], V[k][q]
+                    V[k][p] = c * vkp - sn * vkq
+                    V[k][q] = sn * vkp + c * vkq
+                rotated = True
+        if not rotated:
+            break
+    lmax = 0.0
+    for i in range(6):
+        if a[i][i] > lmax:
+            lmax = a[i][i]
+    y = [0.0] * 6
+    rank = 0
+    for i in range(6):
+        lam = a[i][i]
+        if not lam > TAU * lmax:
+            continue
+        g = 0.0
+        for j in range(6):
+            g += V[j][i] * (s[j] * float(b[j]))
+        f = -g / lam
+        for j in range(6):
+            y[j] += f * V[j][i]
+        rank += 1
+    return np.array([s[j] * y[j] for j in range(6)]), rank
 
 
 def rodrigues(w):
@@ -94,7 +127,8 @@ def rodrigues(w):
 
 
 def step(pts, R, t, mp, mn, dk):
-    """One iteration at inlier distance dk (float32).  Returns (R, t, inliers, rms, updated)."""
+    """One iteration at inlier distance dk (float32).  Returns (R, t, inliers, rms, updated): updated when the step is non-zero
+    (and finite), which is when the kernel counts the iteration in stats[3]."""
     R = np.asarray(R, dtype=np.float64).reshape(3, 3)
     t = np.asarray(t, dtype=np.float64).reshape(3)
     q = model_frame(pts, R, t)
@@ -111,8 +145,11 @@ def step(pts, R, t, mp, mn, dk):
     cnt = int(inl.sum())
     sse = float(np.sum(e * e))
     rms = float(F32(np.sqrt(sse / cnt))) if cnt else 0.0
-    x = _cholesky_solve(J.T @ J, J.T @ e) if cnt >= 6 else None
-    if x is None:
+    if cnt < 6:
+        return R, t, cnt, rms, False
+    qq = float(np.sum((Q[:, 0] * Q[:, 0] + Q[:, 1] * Q[:, 1]) + Q[:, 2] * Q[:, 2]))
+    x, rank = _min_norm_solve(J.T @ J, J.T @ e, qq, float(cnt))
+    if rank == 0 or not np.any(x != 0.0) or not np.all(np.isfinite(x)):
         return R, t, cnt, rms, False
     dR = rodrigues(x[:3])
     Rn = np.empty((3, 3))
