@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import os
 from itertools import combinations
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -129,12 +130,36 @@ def pack_linear(w, k_in, arith="bf16x3", scale=1.0):
     return s.reshape(pc, n // 256, 8, 32, ks1, 2, 8).permute(1, 4, 2, 0, 5, 3, 6).reshape(-1).contiguous()   # [grp, s, u, slice, g, i, j]
 
 
+def _stamp(params):
+    """Weight versions of `params`: changes when any of them is updated in place (version counter) or moved (data pointer)."""
+    return tuple((p.data_ptr(), p._version) for p in params)
+
+
+def _cached(owner, key, stamp, build):
+    """build(), cached on `owner` under `key` and rebuilt when `stamp` (the _stamp of every parameter build() reads) changes: the one
+    weight-version cache of this module (folded biases, launch plans with their packed streams, folds, Linear streams)."""
+    cache = owner.__dict__.setdefault("_weight_cache", {})
+    hit = cache.get(key)
+    if hit is None or hit[0] != stamp:
+        hit = cache[key] = (stamp, build())
+    return hit[1]
+
+
+def _linear_stream(w, k_in, arith):
+    """(cppf_linear_split stream of w, weight scale or None) in `arith`."""
+    if arith == "split16":
+        sc = f16_scale(w)
+        return pack_linear(w, k_in, arith="f16x2", scale=sc), sc
+    return pack_linear(w, k_in), None
+
+
 class _FoldedFirstLayer:
     """A tuple encoder's first ResLayer (a projection layer) on rows [heads | s] with s linear in per-point vectors p of the tuple's
     points, s = s0 + sum_i E_i p[idx_i]: the per-point parts of x W1^T and x W0^T are moved into per-point slot tables
         tables[n, i] = [A_i p_n | C_i p_n],   A_i = W1[:, s-columns] E_i,   C_i = W0[:, s-columns] E_i      (128 + 128 floats)
     (ops.linear_split with `wq_tab`), the constant parts into the biases, and the layer's own products shrink to the head columns
-    (w1_heads / w0_heads).  Algebraically the same layer; the products are folded in float64 and rounded to float32 once."""
+    (w1_heads / w0_heads).  Algebraically the same layer; the products are folded in float64 and rounded to float32 once.
+    stamp: the weight versions it was folded from (part of the stamp of every launch plan it feeds)."""
 
     def __init__(self, stamp, a_list, c_list, w1_heads, w0_heads, b1_add=None, b0_add=None):
         self.stamp = stamp
@@ -143,17 +168,10 @@ class _FoldedFirstLayer:
         self.tab_w = torch.cat([torch.cat([a, c]) for a, c in zip(a_list, c_list)]).float().contiguous()     # [slots * 256, dp]
         self.w1_heads, self.w0_heads = w1_heads.float().contiguous(), w0_heads.float().contiguous()       # [128, head columns]
         self.b1_add, self.b0_add = b1_add, b0_add
-        self._wq = {}
 
     def table_stream(self):
         """(packed stream of the table weights, weight scale or None) in the current arithmetic."""
-        if MLP_ARITH not in self._wq:
-            if MLP_ARITH == "split16":
-                sc = f16_scale(self.tab_w)
-                self._wq[MLP_ARITH] = (pack_linear(self.tab_w, self.dp, arith="f16x2", scale=sc), sc)
-            else:
-                self._wq[MLP_ARITH] = (pack_linear(self.tab_w, self.dp), None)
-        return self._wq[MLP_ARITH]
+        return _cached(self, ("table_stream", MLP_ARITH), self.stamp, lambda: _linear_stream(self.tab_w, self.dp, MLP_ARITH))
 
     def tables(self, p):
         """[points, slots * 256] from the per-point vectors p [points, dp] (float32, device)."""
@@ -162,70 +180,191 @@ class _FoldedFirstLayer:
 
 
 def _fused_plan(seq):
-    """Per-layer (W1^T, b1', W0^T | None, b0', W2^T) with the pending-offset algebra of fused_stack applied once; cached
-    on the module and rebuilt when any parameter changed (version counters) or moved."""
-    stamp = tuple((p.data_ptr(), p._version) for p in seq.parameters())
-    cached = getattr(seq, "_fused_plan_cache", None)
-    if cached is not None and cached[0] == stamp:
-        return cached[1]
-    plan, c = [], None
-    with torch.no_grad():
-        for layer in seq:
-            w1, b1, w2, b2 = layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias
-            if c is not None:
-                b1 = torch.addmv(b1, w1, c)
-            if layer.fc0 is not None:
-                b0 = layer.fc0.bias + b2
+    """(layers, c): per layer (W1^T, b1', W0^T | None, b0', W2^T) with the pending-offset algebra of fused_stack applied once, and
+    the offset c still pending behind the last layer (None when it is a projection layer); rebuilt when a parameter changes."""
+    def build():
+        layers, c = [], None
+        with torch.no_grad():
+            for layer in seq:
+                w1, b1, w2, b2 = layer.fc1.weight, layer.fc1.bias, layer.fc2.weight, layer.fc2.bias
                 if c is not None:
-                    b0 = torch.addmv(b0, layer.fc0.weight, c)
-                plan.append([w1.t(), b1.clone(), layer.fc0.weight.t(), b0, w2.t(), None])
-                c = None
-            else:
-                plan.append([w1.t(), b1.clone(), None, None, w2.t(), None])
-                c = b2.clone() if c is None else c + b2
-    seq._fused_plan_cache = (stamp, (plan, c))
-    return plan, c
+                    b1 = torch.addmv(b1, w1, c)
+                if layer.fc0 is not None:
+                    b0 = layer.fc0.bias + b2
+                    if c is not None:
+                        b0 = torch.addmv(b0, layer.fc0.weight, c)
+                    layers.append((w1.t(), b1.clone(), layer.fc0.weight.t(), b0, w2.t()))
+                    c = None
+                else:
+                    layers.append((w1.t(), b1.clone(), None, None, w2.t()))
+                    c = b2.clone() if c is None else c + b2
+        return layers, c
+    return _cached(seq, "fused_plan", _stamp(seq.parameters()), build)
 
 
-def _entry_cache(entry):
-    """Per-layer cache of packed weight streams and chain lengths, one slot per launch shape (input width, chain | "decode"):
-    alternating callers (with / without the fused bin draw, different input widths) do not evict each other's streams."""
-    if entry[5] is None:
-        entry[5] = {}
-    return entry[5]
+def _decode_fits(layers, c):
+    """The fused bin draw's condition on a stack: a 192-wide projection layer (6 x 32 bins) with a multiple of 8 inputs last,
+    nothing pending behind it."""
+    w1t, _, w0t, _, _ = layers[-1]
+    return w0t is not None and w1t.shape[1] == 192 and w1t.shape[0] % 8 == 0 and c is None
 
 
-def _packed(cache, key, w1t, w0t, w2t, k_in, rest, b1, b0, stamp=None, add=None):
-    """(weight stream, first biases of the launch's layers, skip bias, weight scale) of one launch in the current arithmetic,
-    cached per launch shape: bf16 triples (scale 1) or fp16 pairs of scale x the weights with the biases scaled alike.
-    stamp: weight versions of a SECOND stack the launch runs into (cross-stack launches); it is stored inside the slot and the
-    slot is rebuilt when it changes, so that re-trained weights of the second stack replace their stream instead of adding one."""
-    key = key + (MLP_ARITH,)
-    hit = cache.get(key)
-    if hit is None or hit[0] != stamp:
-        if add is not None:                      # constant terms folded into the first layer's biases (_FoldedFirstLayer)
-            b1 = b1 if add[0] is None else b1 + add[0]
-            b0 = b0 if add[1] is None else b0 + add[1]
-        chain = [(e[0].t(), e[4].t()) for e in rest]
+def _tail_fits(k_in, n_out, proj):
+    """A layer cppf_reslayer_tail evaluates: at most 8 outputs, a multiple of 4 inputs, a projection or an equal-width skip."""
+    return n_out <= 8 and k_in % 4 == 0 and (proj or k_in == n_out)
+
+
+class MlpCall(NamedTuple):
+    """What the launches of fused_stack depend on besides the weights and the arithmetic (the key of its plan cache)."""
+    width: int = 0              # columns of x (0: gathered first layer)
+    aligned: bool = True        # x float32, unit column stride, row stride a multiple of 4, 16-byte aligned: the split kernels read it
+    contiguous: bool = True     # x float32 and contiguous: cppf_reslayer128 reads it
+    gather: str | None = None   # first layer's input: "gather" | "encode" | "sumgather" | "sumencode" (ops.reslayer_split_<form>)
+    heads: int = 0              # head columns of the gathered rows
+    slots: int = 0              # gathered points per row
+    table: int = 0              # columns of the gathered table
+    decode: bool = False
+    tail: bool = False
+    keep_input: bool = False
+
+
+class Launch(NamedTuple):
+    """One launch of a plan."""
+    op: str           # the ops function it calls; "gemm": the library-GEMM triple of a native layer
+    first: int        # its first layer, counted over both stacks
+    chain: int        # identity layers chained behind it in the same launch
+    n_out: int
+    weights: tuple    # split launches: (stream, first biases of its layers, skip bias, weight scale | None);
+                      # reslayer128_: (W1, b1, W2); reslayer_tail: (W1, b1, W0 | None, b0, W2); gemm: (W1^T, b1, W0^T | None, b0, W2^T)
+    out: str          # "inplace" | "new" (buffer) | "tap" (new buffer + the first layer's own) | "caller" (decode's bins, tail's out)
+    tapped: bool      # it produces the tapped activation (its tap buffer when out == "tap", else its output)
+
+
+class LaunchPlan(NamedTuple):
+    launches: tuple
+    offset: torch.Tensor | None     # pending bias offset added to the result at the end
+    tap: int | None                 # tapped layer (the first stack's last one)
+
+
+_ENCODE_OPS = ("reslayer_split_encode", "reslayer_split_sumencode")
+
+
+def _chain_length(layers, li, tap, k_in=None, proj=False):
+    """Identity layers of layer li's width that one launch chains behind it: at most 15, each accepted by
+    ops.reslayer_split_supported(k_in, width, proj, chain) (k_in None: not asked), cut at the tapped layer unless it starts there."""
+    n = layers[li][0].shape[1]
+    chain = 0
+    while (li + 1 + chain < len(layers) and chain < 15 and layers[li + 1 + chain][2] is None
+           and layers[li + 1 + chain][0].shape == (n, n)
+           and (k_in is None or ops.reslayer_split_supported(k_in, n, proj, chain + 1))):
+        chain += 1
+    if tap is not None and li < tap <= li + chain:
+        return tap - li
+    return chain
+
+
+def plan_launches(seq, call, arith, fold=None):
+    """The ordered launches of fused_stack(seq, ...) for the call `call` (MlpCall) in arithmetic `arith` -- every launch decision
+    of the executor, with the packed weight streams.  seq: a stack or (stack_a, stack_b) (tapped at stack_a's last layer); fold:
+    the _FoldedFirstLayer of a table-fed first layer.  Pure: reads the weights and the library's kernel coverage only."""
+    kernel = arith in ("split", "split16")
+    if isinstance(seq, (tuple, list)):
+        layers_a, c_a = _fused_plan(seq[0])
+        assert c_a is None, "the first stack must end in a projection layer"
+        layers_b, c = _fused_plan(seq[1])
+        layers, tap = layers_a + layers_b, len(layers_a) - 1
+    else:
+        (layers, c), tap = _fused_plan(seq), None
+    last = len(layers) - 1
+
+    def split(op, li, chain, k_in, n_out, out, first=None, add=(None, None)):
+        """A split-arithmetic launch of layers li .. li + chain reading k_in columns (first / add: a folded first layer)."""
+        w1t, b1, w0t, b0, w2t = layers[li] if first is None else first
+        b1 = b1 if add[0] is None else b1 + add[0]
+        b0 = b0 if add[1] is None else b0 + add[1]
+        rest = layers[li + 1:li + 1 + chain]
+        pairs = [(e[0].t(), e[4].t()) for e in rest]
         biases = torch.cat([b1] + [e[1] for e in rest])
-        if MLP_ARITH == "split16":
-            sc = f16_scale(w1t, w0t, w2t, *[w for pair in chain for w in pair])
-            wq = pack_split(w1t.t(), None if w0t is None else w0t.t(), w2t.t(), k_in, chain=chain, arith="f16x2", scale=sc)
-            hit = (stamp, (wq, (biases * sc).contiguous(), None if b0 is None else (b0 * sc).contiguous(), sc))
+        if arith == "split16":
+            sc = f16_scale(w1t, w0t, w2t, *[w for pair in pairs for w in pair])
+            wq = pack_split(w1t.t(), None if w0t is None else w0t.t(), w2t.t(), k_in, chain=pairs, arith="f16x2", scale=sc)
+            weights = (wq, (biases * sc).contiguous(), None if b0 is None else (b0 * sc).contiguous(), sc)
         else:
-            wq = pack_split(w1t.t(), None if w0t is None else w0t.t(), w2t.t(), k_in, chain=chain)
-            hit = (stamp, (wq, biases.contiguous(), b0, 1.0))
-        cache[key] = hit
-    return hit[1]
+            weights = (pack_split(w1t.t(), None if w0t is None else w0t.t(), w2t.t(), k_in, chain=pairs), biases.contiguous(), b0, None)
+        return Launch(op, li, chain, n_out, weights, out, tap is not None and li <= tap <= li + chain)
+
+    launches = []
+    li, width, aligned, contiguous = 0, call.width, call.aligned, call.contiguous
+    if call.gather is not None:
+        # the first layer reads its rows itself: [heads | table[gidx_0] | ...] or, table-fed, heads plus the slot tables' rows
+        form = call.gather
+        if form in ("encode", "sumencode") and not (arith == "split" and ops.reslayer_split_encode_supported(call.slots, 128)):
+            form = form.replace("encode", "gather")            # the head columns come from an array (TupleSource.heads)
+        w1t, b1, w0t, b0, w2t = layers[0]
+        first, add = None, (None, None)
+        if fold is not None:
+            k_in = call.heads
+            assert kernel and w0t is not None and w1t.shape[1] == 128 and k_in % 8 == 0, "table-fed first layer: see sum_supported"
+            first, add = (fold.w1_heads.t(), b1, fold.w0_heads.t(), b0, w2t), (fold.b1_add, fold.b0_add)
+        else:
+            k_in = call.heads + call.slots * call.table
+            assert kernel and w0t is not None and w1t.shape == (k_in, 128), "gathered first layer: see gather_supported"
+        op = "reslayer_split16" if (form == "gather" and arith == "split16") else "reslayer_split_" + form
+        chain = 0 if tap == 0 else _chain_length(layers, 0, tap)          # (the gathering launch has no second output)
+        launches.append(split(op, 0, chain, k_in, 128, "new", first, add))
+        li, width, aligned, contiguous = 1 + chain, 128, True, True
+    while li < len(layers):
+        w1t, b1, w0t, b0, w2t = layers[li]
+        n_out, proj = w1t.shape[1], w0t is not None
+        prev = launches[-1] if launches else None
+        # an identity layer must not overwrite the caller's x (keep_input) or the tapped activation
+        keep = (li == 0 and call.keep_input) or (prev is not None and prev.tapped and prev.out != "tap")
+        if call.decode and li == last:
+            assert kernel and _decode_fits(layers, c), "fused bin draw: see decode_supported"
+            launches.append(split("reslayer_split16" if arith == "split16" else "reslayer_split_decode", li, 0, width, n_out, "caller"))
+            return LaunchPlan(tuple(launches), None, tap)
+        if kernel and aligned and width >= w1t.shape[0] and ops.reslayer_split_supported(width, n_out, proj):
+            # the layer and the identity layers of its width behind it, while they fit one kernel: the activation stays in registers
+            chain = _chain_length(layers, li, tap, width, proj)
+            out = "tap" if (tap == li and chain > 0) else "inplace" if not (proj or keep) else "new"
+            launch = split("reslayer_split16" if arith == "split16" else "reslayer_split", li, chain, width, n_out, out)
+        elif (kernel and aligned and width >= w1t.shape[0] and _tail_fits(w1t.shape[0], n_out, proj)
+              and (call.tail or c is None or li < last)):
+            # a layer too narrow for a matrix-core tile (the scale head's 64 -> 3): cppf_reslayer_tail, which also scatters its rows
+            scatter = call.tail and li == last
+            assert not scatter or c is None
+            launch = Launch("reslayer_tail", li, 0, n_out, (w1t.t(), b1, None if w0t is None else w0t.t(), b0, w2t.t()),
+                            "caller" if scatter else "new", tap == li)
+        elif not proj and w1t.shape == (128, 128) and width == 128 and contiguous and not (li == 0 and call.keep_input):
+            # 128-wide identity layer: both products, the bias, the ReLU and the residual add in one kernel (cppf_reslayer128)
+            launch = Launch("reslayer128_", li, 0, n_out, (w1t.t(), b1, w2t.t()), "new" if keep else "inplace", tap == li)
+        else:
+            launch = Launch("gemm", li, 0, n_out, (w1t, b1, w0t, b0, w2t), "inplace" if not (proj or keep) else "new", tap == li)
+        launches.append(launch)
+        if launch.out != "inplace":
+            aligned = contiguous = True
+        elif width > w1t.shape[0]:
+            contiguous = False                       # (a column slice of the input, updated in place)
+        li, width = li + 1 + launch.chain, n_out
+    return LaunchPlan(tuple(launches), c, tap)
 
 
-def _chain_len(cache, key, stamp, compute):
-    """Chain length of a launch shape, cached like _packed (one slot per shape, the second stack's stamp inside it)."""
-    hit = cache.get(key)
-    if hit is None or hit[0] != stamp:
-        hit = (stamp, compute())
-        cache[key] = hit
-    return hit[1]
+def _describe(x, gather, decode, tail, keep_input):
+    """The MlpCall of a fused_stack call."""
+    flags = dict(decode=decode is not None, tail=tail is not None, keep_input=bool(keep_input))
+    if gather is None:
+        f32 = x.dtype == torch.float32
+        return MlpCall(width=x.shape[1], aligned=f32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0,
+                       contiguous=f32 and x.is_contiguous(), **flags)
+    heads, gidx, table = gather[:3]
+    source = isinstance(heads, ops.TupleSource)
+    # the head columns are built inside the first launch where that kernel exists (cppf_reslayer_split_encode: the SHOT model's pair
+    # features; cppf_reslayer_split_sumencode: the DINO model's coordinate block in front of its slot tables)
+    if len(gather) > 3:
+        form = "sumencode" if source and heads.nrm is None else "sumgather"
+    else:
+        form = "encode" if source and heads.nrm is not None else "gather"
+    return MlpCall(gather=form, heads=heads.shape[1], slots=heads.k if source else gidx.shape[1], table=table.shape[1], **flags)
 
 
 def fused_stack(seq, x, keep_input=False, gather=None, decode=None, tail=None):
@@ -242,10 +381,15 @@ def fused_stack(seq, x, keep_input=False, gather=None, decode=None, tail=None):
     In both modes an identity layer's output bias b2 is not added to the activation but carried as a pending per-channel
     offset c (true activation = x + c) and folded into the biases of the next layer (b1 + W1 c, b0 + W0 c), which is
     algebraically the same network; every stack of the reference's models ends in a projection layer, which absorbs the
-    pending offset.  The folded biases (and the packed weight streams of the split kernels) depend on the weights only and
-    are computed once per weight version (_fused_plan).  An identity first layer overwrites `x` unless keep_input is set.
+    pending offset.  An identity first layer overwrites `x` unless keep_input is set.
+    Plan and executor: plan_launches decides every launch of a call -- which ops function, which layers it chains, where the
+    tap lands, which buffer it writes -- with the packed weight streams; the plan is cached per call description (MlpCall) and
+    arithmetic on the first stack under one weight stamp of every parameter it reads (both stacks, the fold's weights), so any
+    in-place update or move of a weight re-plans.  This function looks the plan up and runs it.
     gather = (heads [T, H], gidx int32 [T, k], table [points, F]) instead of x: the rows [heads | table[gidx[:, 0]] | ...] are
-    read by the first layer's kernel itself (ops.reslayer_split_gather; split arithmetic, 128-wide projection first layer).
+    read by the first layer's kernel itself (ops.reslayer_split_gather; split arithmetic, 128-wide projection first layer);
+    heads may be an ops.TupleSource (the head columns built by the first launch, ops.reslayer_split_encode).  gather = (heads,
+    gidx, tables, fold): the per-point parts of the first products come from slot tables (fold: _FoldedFirstLayer).
     decode = (uniforms [T, 6], prior [T, 6, 32] | None, bins int32 [T, 6] | None): the stack's last layer (the logit head's
     192-wide projection layer) draws the bins in its epilogue instead of writing its logits (ops.reslayer_split_decode); the
     return value is then the bins.  Use decode_supported(seq, x) first.
@@ -256,215 +400,77 @@ def fused_stack(seq, x, keep_input=False, gather=None, decode=None, tail=None):
     tail = (rows int32 [n], counts int32 [n / per_group], per_group, out [T, n_out]): the stack's last layer, when it is a narrow
     one (n_out <= 8: ops.reslayer_tail), writes row i of its result to out[rows[i]], skipping the padded entries of each
     group (VotingPipeline.kept_rows32 / kept_count / max_kept); returns `out`.  Use tail_supported(seq) first."""
-    tap_at, cross = None, None
-    if isinstance(seq, (tuple, list)):
-        # two stacks run as one: the first one's output is tapped (returned as well) while the identity layers that open the
-        # second continue in the same kernel.  The first stack must end in a projection layer (nothing pending).
-        seq_a, seq_b = seq
-        plan_a, c_a = _fused_plan(seq_a)
-        assert c_a is None, "the first stack must end in a projection layer"
-        plan_b, c = _fused_plan(seq_b)
-        plan = plan_a + plan_b
-        tap_at = len(plan_a) - 1
-        cross = seq_b._fused_plan_cache[0]          # weight versions of the second stack: stored inside every cross-stack cache slot
-        seq = seq_b
-    else:
-        plan, c = _fused_plan(seq)
-    tapped = None
-
-    def cut(li_, chain_):
-        """chain length of a launch starting at layer li_ so that it does not run past the tapped layer unless it starts there"""
-        if tap_at is not None and li_ < tap_at <= li_ + chain_:
-            return tap_at - li_
-        return chain_
-    li = 0
+    fold = gather[3] if gather is not None and len(gather) > 3 else None
+    call = _describe(x, gather, decode, tail, keep_input)
+    stacks = tuple(seq) if isinstance(seq, (tuple, list)) else (seq,)
+    stamp = (_stamp(p for s in stacks for p in s.parameters()), None if fold is None else fold.stamp)
+    plan = _cached(stacks[0], ("launch_plan", len(stacks), call, MLP_ARITH), stamp, lambda: plan_launches(seq, call, MLP_ARITH, fold))
     if gather is not None:
-        # gather = (heads, gidx, table): x-tile gather of [heads | table[gidx_0] | ...]; gather = (heads, gidx, tables, fold): the
-        # per-point parts of the first products come from slot tables (fold: _FoldedFirstLayer) and are summed into the accumulators
-        fold = gather[3] if len(gather) > 3 else None
         heads, gidx, table = gather[:3]
-        source = None
-        if isinstance(heads, ops.TupleSource):
-            # the head columns are built inside the first launch (cppf_reslayer_split_encode: the SHOT model's 40 pair features;
-            # cppf_reslayer_split_sumencode: the DINO model's coordinate block in front of its slot tables) where that kernel
-            # exists; the other launch forms read them from the array the separate kernel writes
-            if (MLP_ARITH == "split" and ops.reslayer_split_encode_supported(heads.k, 128)
-                    and (fold is None) == (heads.nrm is not None)):
-                source = heads
+        if isinstance(heads, ops.TupleSource) and plan.launches[0].op not in _ENCODE_OPS:
+            heads, gidx = heads.heads()                 # this launch form reads the head columns from an array
+    tapped = None
+    for e in plan.launches:
+        fn = getattr(ops, e.op, None)                   # (looked up per call: bench evidence swaps the ops functions for recorders)
+        w = e.weights
+        tap = None
+        if e.first == 0 and gather is not None:
+            if e.op in _ENCODE_OPS:
+                x = fn(heads, table, *w[:3], 128, chain=e.chain)
+            elif e.op == "reslayer_split16":
+                x = fn(heads, *w[:3], 128, w[3], chain=e.chain, gather=(gidx, table))
+            elif e.op == "reslayer_split_sumgather":
+                x = fn(heads, gidx, table, *w[:3], 128, chain=e.chain, scale=w[3])
             else:
-                heads, gidx = heads.heads()
-        entry = plan[0]
-        w1t, b1, w0t, b0, w2t = entry[:5]
-        if fold is not None:
-            k_in = heads.shape[1]
-            assert _kernel_arith() and w0t is not None and w1t.shape[1] == 128 and k_in % 8 == 0, "table-fed first layer: see sum_supported"
-            w1t, w0t = fold.w1_heads.t(), fold.w0_heads.t()
-        else:
-            k_in = heads.shape[1] + (source.k if source is not None else gidx.shape[1]) * table.shape[1]
-            assert _kernel_arith() and w0t is not None and w1t.shape == (k_in, 128), "gathered first layer: see gather_supported"
-        cache = _entry_cache(entry)
-
-        def gather_chain():
-            n = 0
-            while (1 + n < len(plan) and plan[1 + n][2] is None and n < 15 and plan[1 + n][0].shape == (128, 128)):
-                n += 1
-            n = cut(0, n)
-            return 0 if tap_at == 0 else n      # (the gathering launch has no second output)
-        chain = _chain_len(cache, ("gather-chain", k_in, tap_at), cross, gather_chain)
-        crossing = tap_at is not None and chain > tap_at
-        stamp = (cross if crossing else None, None if fold is None else fold.stamp)
-        wq, bb1, bb0, sc = _packed(cache, (k_in, chain, crossing, fold is not None), w1t, w0t, w2t, k_in, plan[1:1 + chain], b1, b0,
-                                   stamp=stamp, add=None if fold is None else (fold.b1_add, fold.b0_add))
-        if fold is not None and source is not None:
-            x = ops.reslayer_split_sumencode(source, table, wq, bb1, bb0, 128, chain=chain)
-        elif fold is not None:
-            x = ops.reslayer_split_sumgather(heads, gidx, table, wq, bb1, bb0, 128, chain=chain,
-                                             scale=sc if MLP_ARITH == "split16" else None)
-        elif MLP_ARITH == "split16":
-            x = ops.reslayer_split16(heads, wq, bb1, bb0, 128, sc, chain=chain, gather=(gidx, table))
-        elif source is not None:
-            x = ops.reslayer_split_encode(source, table, wq, bb1, bb0, 128, chain=chain)
-        else:
-            x = ops.reslayer_split_gather(heads, gidx, table, wq, bb1, bb0, 128, chain=chain)
-        li = 1 + chain
-        if tap_at is not None and li - 1 == tap_at:
-            tapped = x
-    while li < len(plan):
-        entry = plan[li]
-        w1t, b1, w0t, b0, w2t = entry[:5]
-        n_out = w1t.shape[1]
-        if (decode is not None and li == len(plan) - 1):
-            assert c is None and decode_supported(seq, x), "fused bin draw: see decode_supported"
-            cache = _entry_cache(entry)
-            wq, bb1, bb0, sc = _packed(cache, (x.shape[1], "decode"), w1t, w0t, w2t, x.shape[1], [], b1, b0)
-            if MLP_ARITH == "split16":
-                bins = ops.reslayer_split16(x, wq, bb1, bb0, 192, sc, decode=decode)
+                x = fn(heads, gidx, table, *w[:3], 128, chain=e.chain)
+        elif e.op == "reslayer_split_decode":
+            x = fn(x, *w[:3], decode[0], prior=decode[1], bins=decode[2])
+        elif e.out == "caller" and e.op == "reslayer_split16":
+            x = fn(x, *w[:3], 192, w[3], decode=decode)
+        elif e.op in ("reslayer_split", "reslayer_split16"):
+            out = None if e.out == "inplace" else torch.empty((x.shape[0], e.n_out), dtype=torch.float32, device=x.device)
+            if e.out == "tap":
+                tap = torch.empty((x.shape[0], e.n_out), dtype=torch.float32, device=x.device)
+            if e.op == "reslayer_split16":
+                x = fn(x, *w[:3], e.n_out, w[3], out=out, chain=e.chain, tap=tap)
             else:
-                bins = ops.reslayer_split_decode(x, wq, bb1, bb0, decode[0], prior=decode[1], bins=decode[2])
-            return bins if tap_at is None else (bins, tapped)
-        if (_kernel_arith() and x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0
-                and x.data_ptr() % 16 == 0 and x.shape[1] >= w1t.shape[0]
-                and ops.reslayer_split_supported(x.shape[1], n_out, w0t is not None)):
-            # the whole layer -- and the identity layers of the same width behind it, while they fit one kernel -- on the
-            # bf16 matrix cores in split-float32 arithmetic; the activation stays in registers across the chain
-            cache = _entry_cache(entry)
-            ahead = tap_at is not None and tap_at >= li
-
-            def plain_chain(li=li, n_out=n_out, w0t=w0t):  # (one library call per candidate layer: looked up once per shape)
-                n = 0
-                while (li + 1 + n < len(plan) and plan[li + 1 + n][2] is None and n < 15
-                       and plan[li + 1 + n][0].shape == (n_out, n_out)
-                       and ops.reslayer_split_supported(x.shape[1], n_out, w0t is not None, n + 1)):
-                    n += 1
-                return cut(li, n)
-            chain = _chain_len(cache, ("chain", x.shape[1], tap_at if ahead else None), cross if ahead else None, plain_chain)
-            crossing = tap_at is not None and li <= tap_at < li + chain           # the launch runs from one stack into the other
-            wq, bb1, bb0, sc = _packed(cache, (x.shape[1], chain, crossing), w1t, w0t, w2t, x.shape[1],
-                                       plan[li + 1:li + 1 + chain], b1, b0, stamp=cross if crossing else None)
-            out = None
-            if w0t is None and li == 0 and keep_input:
-                out = torch.empty_like(x)
-            if w0t is None and out is None and tapped is not None and x.data_ptr() == tapped.data_ptr():
-                out = torch.empty_like(x)                 # an in-place identity layer must not overwrite the tapped activation
-            tap_buf = None
-            if tap_at == li and chain > 0:
-                # the tapped layer opens this launch: its output goes to a buffer of its own, the chain's to another
-                tap_buf = torch.empty((x.shape[0], n_out), dtype=torch.float32, device=x.device)
-                if w0t is None and out is None:
-                    out = torch.empty_like(x)
-            if MLP_ARITH == "split16":
-                x = ops.reslayer_split16(x, wq, bb1, bb0, n_out, sc, out=out, chain=chain, tap=tap_buf)
+                x = fn(x, *w[:3], e.n_out, out=out, chain=e.chain, tap=tap)
+        elif e.op == "reslayer_tail":
+            t = tail if e.out == "caller" else None
+            x = fn(x, *w, out=None if t is None else t[3], scatter_rows=None if t is None else t[0],
+                   valid_count=None if t is None else t[1], per_group=0 if t is None else t[2])
+        elif e.op == "reslayer128_":
+            x = fn(x.clone() if e.out == "new" else x, *w)
+        else:                                           # gemm
+            w1t, b1, w0t, b0, w2t = w
+            if x.shape[1] > w1t.shape[0]:               # zero-padded input columns (see BeyondCPPFDino.prepare_tuple_inputs)
+                x = x[:, :w1t.shape[0]]
+            h = torch._addmm_activation(b1, x, w1t)
+            if w0t is not None:
+                x = torch.addmm(b0, x, w0t).addmm_(h, w2t)
+            elif e.out == "new":
+                x = torch.addmm(x, h, w2t)              # same GEMM, written to a new tensor: the input survives
             else:
-                x = ops.reslayer_split(x, wq, bb1, bb0, n_out, out=out, chain=chain, tap=tap_buf)
-            if tap_at is not None and li <= tap_at <= li + chain:
-                tapped = tap_buf if tap_buf is not None else x
-            li += 1 + chain
-            continue
-        if (_kernel_arith() and n_out <= 8 and x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0
-                and x.data_ptr() % 16 == 0 and w1t.shape[0] % 4 == 0 and x.shape[1] >= w1t.shape[0]
-                and (w0t is not None or w1t.shape[0] == n_out) and (tail is not None or c is None or li + 1 < len(plan))):
-            # a layer too narrow for a matrix-core tile (the scale head's 64 -> 3): plain float32, one thread per row, in the
-            # library (cppf_reslayer_tail); tail = (rows, counts, per_group, out): its rows are scattered into `out` on the way
-            last = li == len(plan) - 1
-            t_ = tail if (tail is not None and last) else None
-            x = ops.reslayer_tail(x, w1t.t(), b1, None if w0t is None else w0t.t(), b0, w2t.t(),
-                                  out=None if t_ is None else t_[3], scatter_rows=None if t_ is None else t_[0],
-                                  valid_count=None if t_ is None else t_[1], per_group=0 if t_ is None else t_[2])
-            li += 1
-            if t_ is not None:
-                assert c is None
-                return x
-            continue
-        li += 1
-        if tap_at is not None and li - 2 == tap_at and tapped is None:
-            tapped = x                                     # (library-GEMM path: layer by layer; the next layer must not overwrite it)
-            x = x.clone() if plan[li - 1][2] is None else x
-        if (w0t is None and w1t.shape == (128, 128) and x.shape[1] == 128 and x.dtype == torch.float32 and x.is_contiguous()
-                and not (li == 1 and keep_input)):
-            # 128-wide identity-skip layer: both GEMMs, the bias, the ReLU and the residual add in one matrix-core kernel
-            # that reads and writes the activation once (cppf_reslayer128); w1t / w2t are transposed views of the weights
-            x = ops.reslayer128_(x, w1t.t(), b1, w2t.t())
-            continue
-        if x.shape[1] > w1t.shape[0]:               # zero-padded input columns (see BeyondCPPFDino.prepare_tuple_inputs)
-            x = x[:, :w1t.shape[0]]
-        h = torch._addmm_activation(b1, x, w1t)
-        if w0t is not None:
-            x = torch.addmm(b0, x, w0t)
-        elif li == 1 and keep_input:
-            x = torch.addmm(x, h, w2t)              # same GEMM, written to a new tensor: the caller's x survives
-            continue
-        x = x.addmm_(h, w2t)
-    if c is not None:
-        x = x.add_(c)
-    return x if tap_at is None else (x, tapped)
+                x = x.addmm_(h, w2t)
+        if e.tapped:
+            tapped = tap if tap is not None else x
+    if plan.offset is not None:
+        x = x.add_(plan.offset)
+    return x if plan.tap is None else (x, tapped)
 
 
 def tail_supported(seq):
     """True when fused_stack(seq, ..., tail=...) can scatter the last layer's rows itself: split arithmetic, inference, a
     projection layer with at most 8 outputs and a multiple of 4 inputs last."""
     last = seq[len(seq) - 1]
-    return (_kernel_arith() and not torch.is_grad_enabled() and last.fc0 is not None and last.fc1.out_features <= 8
-            and last.fc1.in_features % 4 == 0)
+    return (_kernel_arith() and not torch.is_grad_enabled() and last.fc0 is not None
+            and _tail_fits(last.fc1.in_features, last.fc1.out_features, True))
 
 
 def decode_supported(seq, x):
     """True when fused_stack(seq, x, decode=...) can draw the bins inside the stack's last layer: split arithmetic, inference,
     a 192-wide projection layer (6 x 32 bins) last, preceded by a projection or nothing pending (no carried bias offset)."""
-    last = seq[len(seq) - 1]
-    plan, c = _fused_plan(seq)
-    return (_kernel_arith() and not torch.is_grad_enabled() and x.is_cuda and last.fc0 is not None
-            and last.fc1.out_features == 192 and last.fc1.in_features % 8 == 0 and c is None)
-
-
-def _scale_head_rows(model, feat, rows, scatter=None):
-    """model.scale_head(feat[rows]) without materialising feat[rows]: the scale head's first layer (a 128-wide projection
-    layer) reads the selected rows of `feat` through the gathering x-tile fetch of cppf_reslayer_split_gather (a table
-    gather with no pair-feature block).  rows: int32 (or int64) [n] tuple rows.
-    scatter = (counts int32 [n / per_group], per_group, out [T, 3]): the result rows are written to out[rows[i]] by the
-    head's last kernel (padded entries of each group skipped) and `out` is returned -- no index_put, no torch kernel."""
-    first = model.scale_encoder[0]
-    f = feat.shape[1]
-    if not (_kernel_arith() and not torch.is_grad_enabled() and feat.is_cuda and feat.is_contiguous()
-            and first.fc0 is not None and first.fc1.out_features == 128 and first.fc1.in_features == f
-            and f >= 8 and f & (f - 1) == 0 and feat.shape[0] < 2 ** 31):
-        vals = model.scale_head(feat[rows.long()])
-        if scatter is None:
-            return vals
-        counts, per_group, out = scatter
-        keep = (torch.arange(rows.numel(), device=rows.device) % per_group) < counts.repeat_interleave(per_group)
-        out[rows.long()[keep]] = vals[keep]
-        return out
-    gidx = (rows if rows.dtype == torch.int32 else rows.to(torch.int32)).reshape(-1, 1)
-    tail = None
-    if scatter is not None and tail_supported(model.scale_encoder):
-        tail = (gidx.reshape(-1), scatter[0], scatter[1], scatter[2])
-    vals = fused_stack(model.scale_encoder, None, gather=(feat[:, :0], gidx, feat), tail=tail)
-    if scatter is not None and tail is None:
-        counts, per_group, out = scatter
-        keep = (torch.arange(rows.numel(), device=rows.device) % per_group) < counts.repeat_interleave(per_group)
-        out[rows.long()[keep]] = vals[keep]
-        return out
-    return vals
+    return _kernel_arith() and not torch.is_grad_enabled() and x.is_cuda and _decode_fits(*_fused_plan(seq))
 
 
 class _EncodeShot(torch.autograd.Function):
@@ -490,7 +496,71 @@ class _EncodeShot(torch.autograd.Function):
         return None, None, gf, None
 
 
-class BeyondCPPFShot(nn.Module):
+class _TupleHeads(nn.Module):
+    """The heads both models put behind their tuple encoder (tuple_encoder -> logit_encoder / scale_encoder, train_shot.py:112-114,
+    train_dino.py:130-132) and their inference on the library's kernels."""
+
+    def heads(self, inputs, decode=None, lazy_scale=False):
+        """(preds_cls [T,6,32], preds_scale [T,3]) from the tuple inputs; inference on the GPU runs the tuple encoder and the logit
+        head as one chain of launches (fused_stack) with the tuple features tapped for the scale head.  decode: see
+        BeyondCPPFShot.heads_from_tuples (None is returned in place of the logits when the bins were drawn).  lazy_scale=True
+        (inference) returns (preds_cls, feat) instead: the scale head's output is only ever read for the pairs that survive the
+        back-vote filter (eval.py:272, ~10 % of the tuples), so a caller can run scale_head() on just those rows of `feat` later --
+        same rows through the same layers."""
+        if not torch.is_grad_enabled() and inputs.is_cuda:
+            return self._tuple_mlp(inputs, None, decode, lazy_scale)
+        feat = self.tuple_encoder(inputs)
+        preds_scale = self.scale_encoder(feat)
+        preds_cls = self.logit_encoder(feat).reshape(feat.shape[0], 6, -1)
+        return preds_cls, preds_scale
+
+    def _tuple_mlp(self, x, gather, decode, lazy_scale):
+        """fused_stack((tuple_encoder, logit_encoder), x, gather=gather) with the bins drawn by the last launch when
+        decode_supported, then the scale head on the tapped tuple features unless lazy_scale: (logits | None, scales | features)."""
+        probe = x if gather is None else gather[2]
+        draw = decode if (decode is not None and decode_supported(self.logit_encoder, probe)) else None
+        preds_cls, feat = fused_stack((self.tuple_encoder, self.logit_encoder), x, gather=gather, decode=draw)
+        second = feat if lazy_scale else fused_stack(self.scale_encoder, feat)      # first layer projects: feat is left intact
+        if draw is not None:
+            return None, second
+        return preds_cls.reshape(feat.shape[0], 6, -1), second
+
+    def scale_head(self, feat_rows):
+        """scale_encoder on a subset of tuple features (rows of the `feat` heads(lazy_scale=True) returned)."""
+        if not torch.is_grad_enabled() and feat_rows.is_cuda:
+            return fused_stack(self.scale_encoder, feat_rows)
+        return self.scale_encoder(feat_rows)
+
+    def scale_head_rows(self, feat, rows, scatter=None):
+        """scale_head(feat[rows]) on the kept pairs only (eval.py:272 reads nothing else; it is the DINO model's scale that the
+        reference keeps, eval.py:308-310), without materialising feat[rows]: the scale head's first layer (a 128-wide projection
+        layer) reads the selected rows of `feat` through the gathering x-tile fetch of cppf_reslayer_split_gather (a table gather
+        with no pair-feature block).  rows: int32 (or int64) [n] tuple rows.
+        scatter = (counts int32 [n / per_group], per_group, out [T, 3]): the result rows are written to out[rows[i]] (padded entries
+        of each group skipped) and `out` is returned -- by the head's last kernel where tail_supported: no index_put, no torch kernel."""
+        first = self.scale_encoder[0]
+        f = feat.shape[1]
+        if (_kernel_arith() and not torch.is_grad_enabled() and feat.is_cuda and feat.is_contiguous()
+                and first.fc0 is not None and first.fc1.out_features == 128 and first.fc1.in_features == f
+                and f >= 8 and f & (f - 1) == 0 and feat.shape[0] < 2 ** 31):
+            gidx = (rows if rows.dtype == torch.int32 else rows.to(torch.int32)).reshape(-1, 1)
+            tail = None
+            if scatter is not None and tail_supported(self.scale_encoder):
+                tail = (gidx.reshape(-1), scatter[0], scatter[1], scatter[2])
+            vals = fused_stack(self.scale_encoder, None, gather=(feat[:, :0], gidx, feat), tail=tail)
+            if tail is not None:
+                return vals
+        else:
+            vals = self.scale_head(feat[rows.long()])
+        if scatter is None:
+            return vals
+        counts, per_group, out = scatter
+        keep = (torch.arange(rows.numel(), device=rows.device) % per_group) < counts.repeat_interleave(per_group)
+        out[rows.long()[keep]] = vals[keep]
+        return out
+
+
+class BeyondCPPFShot(_TupleHeads):
     """train_shot.py:48-122.  forward(points, point_idxs_all, shot_feat, normal) -> (preds_cls [T,6,32], preds_scale [T,3])."""
 
     def __init__(self, cfg):
@@ -508,22 +578,6 @@ class BeyondCPPFShot(nn.Module):
         if shot_feat.requires_grad:
             return _EncodeShot.apply(points, idx, shot_feat, normal)
         return ops.encode_tuples_shot(points, idx, shot_feat, normal)
-
-    def heads(self, inputs, lazy_scale=False):
-        """(preds_cls, preds_scale).  lazy_scale=True (inference) returns (preds_cls, feat) instead: the scale head's
-        output is only ever read for the pairs that survive the back-vote filter (eval.py:272, ~10 % of the tuples), so a
-        caller can run scale_head() on just those rows of `feat` later -- same rows through the same layers."""
-        if not torch.is_grad_enabled() and inputs.is_cuda:
-            # tuple encoder and logit head as one chain of launches; `feat` (the tuple encoder's output) is tapped for the scale head
-            preds_cls, feat = fused_stack((self.tuple_encoder, self.logit_encoder), inputs)
-            if lazy_scale:
-                return preds_cls.reshape(feat.shape[0], 6, -1), feat
-            preds_scale = fused_stack(self.scale_encoder, feat)      # first layer projects: feat is left intact
-            return preds_cls.reshape(feat.shape[0], 6, -1), preds_scale
-        feat = self.tuple_encoder(inputs)
-        preds_scale = self.scale_encoder(feat)
-        preds_cls = self.logit_encoder(feat).reshape(feat.shape[0], 6, -1)
-        return preds_cls, preds_scale
 
     def gather_supported(self, feat_dim, k):
         """True when heads_from_tuples can feed the tuple encoder without materialising its input rows."""
@@ -544,16 +598,15 @@ class BeyondCPPFShot(nn.Module):
         (train_shot.py:75-83): slot i's table weights are the columns of fc1 / fc0 that multiply feat[idx_i] (no product to
         fold: the same multiplications as the row form, summed per slot first)."""
         first = self.tuple_encoder[0]
-        stamp = tuple((q.data_ptr(), q._version) for q in first.parameters()) + (feat_dim, k)
-        cached = getattr(self, "_fold_cache", None)
-        if cached is None or cached.stamp != stamp:
+        stamp = _stamp(first.parameters())
+
+        def build():
             head = k * (k - 1) // 2 * 4
             w1, w0 = first.fc1.weight.detach(), first.fc0.weight.detach()
-            cached = _FoldedFirstLayer(stamp, [w1[:, head + i * feat_dim: head + (i + 1) * feat_dim] for i in range(k)],
-                                       [w0[:, head + i * feat_dim: head + (i + 1) * feat_dim] for i in range(k)],
-                                       w1[:, :head], w0[:, :head])
-            self._fold_cache = cached
-        return cached
+            return _FoldedFirstLayer(stamp, [w1[:, head + i * feat_dim: head + (i + 1) * feat_dim] for i in range(k)],
+                                     [w0[:, head + i * feat_dim: head + (i + 1) * feat_dim] for i in range(k)],
+                                     w1[:, :head], w0[:, :head])
+        return _cached(self, ("first_layer_fold", feat_dim, k), stamp, build)
 
     def heads_from_tuples(self, points, point_idxs_all, feat, normal, pt_off=None, tup_off=None, lazy_scale=False, decode=None,
                           sum_tables=False):
@@ -571,7 +624,6 @@ class BeyondCPPFShot(nn.Module):
         if not (points.is_cuda and self.gather_supported(feat.shape[1], idx.shape[1])):
             return self.heads(ops.encode_tuples_shot(points, idx, feat, normal, pt_off, tup_off), lazy_scale=lazy_scale)
         tuples = ops.TupleSource(points, idx, normal, pt_off, tup_off)
-        draw = decode if (decode is not None and decode_supported(self.logit_encoder, feat)) else None
         if sum_tables and self.sum_supported(feat.shape[1], idx.shape[1]):
             # the descriptor columns' share of the first products, once per point and slot instead of once per tuple
             fold = self.first_layer_fold(feat.shape[1], idx.shape[1])
@@ -580,21 +632,7 @@ class BeyondCPPFShot(nn.Module):
         else:
             # (round 5: the pair features are built by the first launch itself -- no per-tuple array between sampler and encoder)
             src = (tuples, None, feat.contiguous())
-        preds_cls, feat = fused_stack((self.tuple_encoder, self.logit_encoder), None, gather=src, decode=draw)
-        second = feat if lazy_scale else fused_stack(self.scale_encoder, feat)
-        if draw is not None:
-            return None, second
-        return preds_cls.reshape(feat.shape[0], 6, -1), second
-
-    def scale_head(self, feat_rows):
-        """scale_encoder on a subset of tuple features (rows of the `feat` heads(lazy_scale=True) returned)."""
-        if not torch.is_grad_enabled() and feat_rows.is_cuda:
-            return fused_stack(self.scale_encoder, feat_rows)
-        return self.scale_encoder(feat_rows)
-
-    def scale_head_rows(self, feat, rows, scatter=None):
-        """scale_head(feat[rows]) on the kept pairs only: see _scale_head_rows."""
-        return _scale_head_rows(self, feat, rows, scatter)
+        return self._tuple_mlp(None, src, decode, lazy_scale)
 
     def encode_points(self, shot_feat):
         """shot_encoder over the per-point descriptors (train_shot.py:118)."""
@@ -607,7 +645,7 @@ class BeyondCPPFShot(nn.Module):
         return self.heads(inputs)
 
 
-class BeyondCPPFDino(nn.Module):
+class BeyondCPPFDino(_TupleHeads):
     """train_dino.py:58-133.  forward(points, point_descs, point_idxs_all).
     desc_transform is applied per point BEFORE the gather: same Linear on the same rows,
     1/5 of the FLOPs at T >> N and no [T,5,1024] temporary."""
@@ -648,23 +686,6 @@ class BeyondCPPFDino(nn.Module):
         coord = ops.encode_tuples_coord(points, idx)
         return torch.cat([coord, desc_part], -1)
 
-    def heads(self, inputs, decode=None, lazy_scale=False):
-        """(preds_cls [T,6,32], preds_scale [T,3]) from the tuple inputs (train_dino.py:130-132); inference on the GPU
-        runs the stacks as matrix-core kernels (fused_stack), like the SHOT model.  decode: see
-        BeyondCPPFShot.heads_from_tuples (None is returned in place of the logits when the bins were drawn);
-        lazy_scale=True returns the tuple features in place of the scale head's output (see BeyondCPPFShot.heads)."""
-        if not torch.is_grad_enabled() and inputs.is_cuda:
-            draw = decode if (decode is not None and decode_supported(self.logit_encoder, inputs)) else None
-            preds_cls, feat = fused_stack((self.tuple_encoder, self.logit_encoder), inputs, decode=draw)
-            second = feat if lazy_scale else fused_stack(self.scale_encoder, feat)      # first layer projects: feat is left intact
-            if draw is not None:
-                return None, second
-            return preds_cls.reshape(feat.shape[0], 6, -1), second
-        feat = self.tuple_encoder(inputs)
-        preds_scale = self.scale_encoder(feat)
-        preds_cls = self.logit_encoder(feat).reshape(feat.shape[0], 6, -1)
-        return preds_cls, preds_scale
-
     def sum_supported(self, k):
         """True when heads_from_tuples can run: every Linear of prepare_tuple_inputs on the library's matrix-core kernels and the
         tuple rows never formed (split arithmetic, inference, the reference's layer widths)."""
@@ -682,33 +703,27 @@ class BeyondCPPFDino(nn.Module):
         fc0[:, desc columns] W_i (folded in float64, rounded to float32 once), desc_pair_transform's bias goes through the same
         columns into the layer's biases, and the layer's own products keep the 30 coordinate columns only."""
         first = self.tuple_encoder[0]
-        params = list(first.parameters()) + list(self.desc_pair_transform.parameters())
-        stamp = tuple((q.data_ptr(), q._version) for q in params) + (k,)
-        cached = getattr(self, "_fold_cache", None)
-        if cached is None or cached.stamp != stamp:
+        stamp = _stamp(list(first.parameters()) + list(self.desc_pair_transform.parameters()))
+
+        def build():
             nc, d = self.ncoord, self.desc_transform.out_features
             w1, w0 = first.fc1.weight.detach().double(), first.fc0.weight.detach().double()
             wp, bp = self.desc_pair_transform.weight.detach().double(), self.desc_pair_transform.bias.detach().double()
-            cached = _FoldedFirstLayer(stamp, [w1[:, nc:] @ wp[:, i * d:(i + 1) * d] for i in range(k)],
-                                       [w0[:, nc:] @ wp[:, i * d:(i + 1) * d] for i in range(k)], w1[:, :nc], w0[:, :nc],
-                                       b1_add=(w1[:, nc:] @ bp).float(), b0_add=(w0[:, nc:] @ bp).float())
-            self._fold_cache = cached
-        return cached
+            return _FoldedFirstLayer(stamp, [w1[:, nc:] @ wp[:, i * d:(i + 1) * d] for i in range(k)],
+                                     [w0[:, nc:] @ wp[:, i * d:(i + 1) * d] for i in range(k)], w1[:, :nc], w0[:, :nc],
+                                     b1_add=(w1[:, nc:] @ bp).float(), b0_add=(w0[:, nc:] @ bp).float())
+        return _cached(self, ("first_layer_fold", k), stamp, build)
 
     def transform_points(self, point_descs):
         """desc_transform over the per-point descriptors (train_dino.py:95; applied per point, before the gather) on the library's
         matrix-core Linear kernel: [N, 1024] -> [N, 256]."""
         lin = self.desc_transform
-        stamp = (lin.weight.data_ptr(), lin.weight._version, lin.bias.data_ptr(), lin.bias._version, MLP_ARITH)
-        cached = getattr(self, "_desc_cache", None)
-        if cached is None or cached[0] != stamp:
-            if MLP_ARITH == "split16":
-                sc = f16_scale(lin.weight)
-                cached = (stamp, pack_linear(lin.weight, lin.in_features, arith="f16x2", scale=sc), (lin.bias.detach() * sc).contiguous(), sc)
-            else:
-                cached = (stamp, pack_linear(lin.weight, lin.in_features), lin.bias.detach().contiguous(), None)
-            self._desc_cache = cached
-        return ops.linear_split(point_descs, cached[1], cached[2], lin.out_features, scale=cached[3])
+
+        def build():
+            wq, sc = _linear_stream(lin.weight, lin.in_features, MLP_ARITH)
+            return wq, (lin.bias.detach() if sc is None else lin.bias.detach() * sc).contiguous(), sc
+        wq, bias, sc = _cached(self, ("transform_points", MLP_ARITH), _stamp(lin.parameters()), build)
+        return ops.linear_split(point_descs, wq, bias, lin.out_features, scale=sc)
 
     def point_tables(self, point_descs, k):
         """Per-point slot tables [N, k * 256] of the folded first layer from the raw descriptors [N, 1024]: two library launches
@@ -735,23 +750,7 @@ class BeyondCPPFDino(nn.Module):
             tables = fold.tables(self.transform_points(point_descs.contiguous()))
         # (round 5: the coordinate columns are built by the first launch itself -- no per-tuple array between sampler and encoder)
         tuples = ops.TupleSource(points, idx, None, pt_off, tup_off)
-        draw = decode if (decode is not None and decode_supported(self.logit_encoder, tables)) else None
-        preds_cls, feat = fused_stack((self.tuple_encoder, self.logit_encoder), None, gather=(tuples, None, tables, fold), decode=draw)
-        second = feat if lazy_scale else fused_stack(self.scale_encoder, feat)
-        if draw is not None:
-            return None, second
-        return preds_cls.reshape(feat.shape[0], 6, -1), second
-
-    def scale_head(self, feat_rows):
-        """scale_encoder on a subset of tuple features (rows of the `feat` heads(lazy_scale=True) returned)."""
-        if not torch.is_grad_enabled() and feat_rows.is_cuda:
-            return fused_stack(self.scale_encoder, feat_rows)
-        return self.scale_encoder(feat_rows)
-
-    def scale_head_rows(self, feat, rows, scatter=None):
-        """scale_head(feat[rows]) on the kept pairs only (eval.py:272 reads nothing else; it is THIS model's scale that the
-        reference keeps, eval.py:308-310): see _scale_head_rows."""
-        return _scale_head_rows(self, feat, rows, scatter)
+        return self._tuple_mlp(None, (tuples, None, tables, fold), decode, lazy_scale)
 
     def forward(self, points, point_descs, point_idxs_all):
         return self.heads(self.prepare_tuple_inputs(points, point_descs, point_idxs_all))

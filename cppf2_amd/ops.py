@@ -328,6 +328,17 @@ def cast_f16(x, out=None):
     return out
 
 
+def _split_args(wq, b1, b0, *mid, count=None):
+    """The trailing arguments of a cppf_reslayer_split* entry point: the weight stream and its byte count, the biases made
+    contiguous (b1 holds `count` values when given: the first biases of the launch's layers), `mid` (the chain length, or the
+    bin draw's arguments), the row-block counters and the stream."""
+    b1 = b1.contiguous()
+    if count is not None:
+        assert b1.numel() == count
+    b0 = None if b0 is None else b0.contiguous()
+    return (_p(wq), wq.numel() * wq.element_size(), _p(b1), _p(b0)) + mid + (_sched(), _stream())
+
+
 def reslayer_split_supported(k_in, n_out, proj, chain=0):
     """True when cppf_reslayer_split has a kernel for a ResLayer of these dims (k_in = columns of x it reads) followed by
     `chain` identity layers of the same width."""
@@ -346,18 +357,13 @@ def reslayer_split(x, wq, b1, b0, n_out, out=None, chain=0, tap=None):
     if out is None:
         out = x if b0 is None else torch.empty((rows, n_out), dtype=torch.float32, device=x.device)
     assert out.dtype == torch.float32 and out.shape == (rows, n_out) and out.stride(1) == 1
-    b1 = b1.contiguous()
-    assert b1.numel() == (1 + chain) * n_out
-    b0 = None if b0 is None else b0.contiguous()
+    args = _split_args(wq, b1, b0, int(chain), count=(1 + chain) * n_out)
     if tap is not None:
         assert tap.dtype == torch.float32 and tap.shape == (rows, n_out) and tap.stride(1) == 1
         _lib.check(_L.cppf_reslayer_split_tap(_p(x), x.stride(0), k_in, _p(tap), tap.stride(0), _p(out), out.stride(0), n_out,
-                                              rows, _p(wq), wq.numel() * wq.element_size(), _p(b1), _p(b0), int(chain), _sched(), _stream()),
-                   "cppf_reslayer_split_tap")
+                                              rows, *args), "cppf_reslayer_split_tap")
         return out
-    _lib.check(_L.cppf_reslayer_split(_p(x), x.stride(0), k_in, _p(out), out.stride(0), n_out, rows, _p(wq),
-                                      wq.numel() * wq.element_size(), _p(b1), _p(b0), int(chain), _sched(), _stream()),
-               "cppf_reslayer_split")
+    _lib.check(_L.cppf_reslayer_split(_p(x), x.stride(0), k_in, _p(out), out.stride(0), n_out, rows, *args), "cppf_reslayer_split")
     return out
 
 
@@ -456,13 +462,11 @@ def reslayer_split_decode(x, wq, b1, b0, uniforms, prior=None, bins=None):
         bins = torch.empty((rows, 6), dtype=torch.int32, device=x.device)
     assert bins.dtype == torch.int32 and bins.is_contiguous() and bins.numel() == rows * 6
     if prior is None and ppos is None:       # the reference's draw (eval.py:225-229): the stable entry point
-        _lib.check(_L.cppf_reslayer_split_decode(_p(x), x.stride(0), x.shape[1], rows, _p(wq), wq.numel() * wq.element_size(),
-                                                 _p(b1.contiguous()), _p(b0.contiguous()), _p(u), _p(bins), _sched(), _stream()),
+        _lib.check(_L.cppf_reslayer_split_decode(_p(x), x.stride(0), x.shape[1], rows, *_split_args(wq, b1, b0, _p(u), _p(bins))),
                    "cppf_reslayer_split_decode")
         return bins
-    _lib.check(_L.cppf_reslayer_split_decode_prior(_p(x), x.stride(0), x.shape[1], rows, _p(wq), wq.numel() * wq.element_size(),
-                                                   _p(b1.contiguous()), _p(b0.contiguous()), _p(prior), _p(ppos), C.c_float(pis), _p(u),
-                                                   _p(bins), _sched(), _stream()),
+    _lib.check(_L.cppf_reslayer_split_decode_prior(_p(x), x.stride(0), x.shape[1], rows,
+                                                   *_split_args(wq, b1, b0, _p(prior), _p(ppos), C.c_float(pis), _p(u), _p(bins))),
                "cppf_reslayer_split_decode_prior")
     return bins
 
@@ -495,13 +499,10 @@ def reslayer_split_gather(heads, gidx, table, wq, b1, b0, n_out, chain=0):
     assert gidx.dtype == torch.int32 and gidx.is_contiguous() and table.dtype == torch.float32 and table.is_contiguous()
     rows = gidx.shape[0]
     out = torch.empty((rows, n_out), dtype=torch.float32, device=heads.device)
-    b1 = b1.contiguous()
-    b0 = b0.contiguous()
-    assert b1.numel() == (1 + chain) * n_out
     ld_heads = heads.stride(0) if heads.shape[1] else 0
     _lib.check(_L.cppf_reslayer_split_gather(_p(heads if heads.shape[1] else table), ld_heads, heads.shape[1], _p(gidx), gidx.shape[1], _p(table),
-                                             table.shape[1], _p(out), out.stride(0), n_out, rows, _p(wq),
-                                             wq.numel() * wq.element_size(), _p(b1), _p(b0), int(chain), _sched(), _stream()),
+                                             table.shape[1], _p(out), out.stride(0), n_out, rows,
+                                             *_split_args(wq, b1, b0, int(chain), count=(1 + chain) * n_out)),
                "cppf_reslayer_split_gather")
     return out
 
@@ -579,12 +580,9 @@ def reslayer_split_encode(src, table, wq, b1, b0, n_out, chain=0):
     assert isinstance(src, TupleSource) and table.dtype == torch.float32 and table.is_contiguous() and table.is_cuda
     rows = src.idx.shape[0]
     out = torch.empty((rows, n_out), dtype=torch.float32, device=table.device)
-    b1 = b1.contiguous()
-    b0 = b0.contiguous()
-    assert b1.numel() == (1 + chain) * n_out
     _lib.check(_L.cppf_reslayer_split_encode(src.B, _p(src.pts), _p(src.nrm), _p(src.idx), src.k, _p(src.pt_off), _p(src.tup_off),
-                                             _p(table), table.shape[1], _p(out), out.stride(0), n_out, rows, _p(wq),
-                                             wq.numel() * wq.element_size(), _p(b1), _p(b0), int(chain), _sched(), _stream()),
+                                             _p(table), table.shape[1], _p(out), out.stride(0), n_out, rows,
+                                             *_split_args(wq, b1, b0, int(chain), count=(1 + chain) * n_out)),
                "cppf_reslayer_split_encode")
     return out
 
@@ -596,12 +594,9 @@ def reslayer_split_sumencode(src, tables, wq, b1, b0, n_out, chain=0):
     rows = src.idx.shape[0]
     assert tables.shape[1] == src.k * 256
     out = torch.empty((rows, n_out), dtype=torch.float32, device=tables.device)
-    b1 = b1.contiguous()
-    b0 = b0.contiguous()
-    assert b1.numel() == (1 + chain) * n_out
     _lib.check(_L.cppf_reslayer_split_sumencode(src.B, _p(src.pts), _p(src.idx), src.k, _p(src.pt_off), _p(src.tup_off), _p(tables),
-                                                tables.stride(0), _p(out), out.stride(0), n_out, rows, _p(wq),
-                                                wq.numel() * wq.element_size(), _p(b1), _p(b0), int(chain), _sched(), _stream()),
+                                                tables.stride(0), _p(out), out.stride(0), n_out, rows,
+                                                *_split_args(wq, b1, b0, int(chain), count=(1 + chain) * n_out)),
                "cppf_reslayer_split_sumencode")
     return out
 
@@ -660,18 +655,18 @@ def reslayer_split_sumgather(heads, gidx, tables, wq, b1, b0, n_out, chain=0, sc
     rows, slots = gidx.shape
     assert tables.shape[1] == slots * 256
     out = torch.empty((rows, n_out), dtype=torch.float32, device=heads.device)
-    b1 = b1.contiguous()
-    b0 = b0.contiguous()
-    assert b1.numel() == (1 + chain) * n_out
     if scale is not None:
+        b1 = b1.contiguous()
+        b0 = b0.contiguous()
+        assert b1.numel() == (1 + chain) * n_out
         _split16("cppf_reslayer_split16(sumgather)", wq, scale, mode=2, x=heads.data_ptr(), ldx=heads.stride(0), k_in=heads.shape[1],
                  out=out.data_ptr(), ldo=out.stride(0), n_out=int(n_out), rows=int(rows), chain=int(chain), b1=b1.data_ptr(),
                  b0=b0.data_ptr(), gidx=gidx.data_ptr(), slots=int(slots), table=tables.data_ptr(), ld_table=tables.stride(0),
                  sched=_sched().value)
         return out
     _lib.check(_L.cppf_reslayer_split_sumgather(_p(heads), heads.stride(0), heads.shape[1], _p(gidx), slots, _p(tables),
-                                                tables.stride(0), _p(out), out.stride(0), n_out, rows, _p(wq),
-                                                wq.numel() * wq.element_size(), _p(b1), _p(b0), int(chain), _sched(), _stream()),
+                                                tables.stride(0), _p(out), out.stride(0), n_out, rows,
+                                                *_split_args(wq, b1, b0, int(chain), count=(1 + chain) * n_out)),
                "cppf_reslayer_split_sumgather")
     return out
 
