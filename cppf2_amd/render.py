@@ -45,11 +45,13 @@ SUBSAMPLE_STREAM = 1 << 30       # third seed word of the exported 100-point sub
 # mesh loaders
 # ----------------------------------------------------------------------------------------------
 class Mesh:
-    """verts float64 [V,3] (already multiplied by the load scale), faces int32 [F,3]; device copies made on first use."""
+    """verts float64 [V,3] (already multiplied by the load scale), faces int32 [F,3]; device copies made on first use.  scale:
+    the factor that took the file's units to these vertices' (load_mesh's `scale`)."""
 
-    def __init__(self, verts, faces):
+    def __init__(self, verts, faces, scale=1.0):
         self.verts = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
         self.faces = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+        self.scale = float(scale)
         if self.faces.size and (self.faces.min() < 0 or self.faces.max() >= len(self.verts)):
             raise ValueError("mesh face indices outside [0, %d)" % len(self.verts))
         self._dev = {}
@@ -180,7 +182,7 @@ def load_mesh(path, scale=1.0):
             v, f = load_obj(path)
         else:
             raise ValueError("%s: only .ply and .obj meshes are read" % path)
-        m = _MESHES[key] = Mesh(v * float(scale), f)
+        m = _MESHES[key] = Mesh(v * float(scale), f, scale)
     return m
 
 

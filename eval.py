@@ -22,6 +22,10 @@ What the image cannot provide is stated, not faked:
   * `--data=depth --mesh=<ply|obj> [--mesh_scale=1.0] --icp_iters=N` (N > 0) refines the selected pose of the instance by N
     point-to-plane ICP iterations against samples of the object's mesh (cppf2_amd.icp, cppf_icp_refine; not in the
     reference), after the ensemble selection and `opt`; the report gains the ICP stats.  --icp_iters=0 (default): off.
+  * `--data=depth --mesh=<ply|obj> --gt_pose=<.npy|.txt> [--models_info=<json>]` scores the reported pose against the true one
+    (a 3x4 or 4x4 model -> OpenCV camera matrix in the record convention, metres) with the BOP metrics VSD, MSSD and MSPD
+    (cppf2_amd.bop; --models_info: the object's BOP models_info entry, for its symmetries and diameter): each result gains
+    `bop` (and `bop_before_icp` with --icp_iters > 0), the report their average recall.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import json
@@ -483,15 +487,28 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          use_grounded_sam=False, geo_branch=True, visual_branch=True, data="synthetic", num_scenes=8, num_points=4096,
          category=None, categories=None, seed=0, ckpt_dir=None, ckpt_shot=None, ckpt_dino=None, depth=None, mask=None,
          intrinsics=None, depth_scale=1000.0, out=None, out_pkl=None, log_dir=None, data_root="NOCS/real_test", out_dir=None,
-         desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0):
+         desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
+         models_info=None):
     custom = False
     icp_iters = int(icp_iters)
     if icp_iters > 0 and (data != "depth" or not mesh):
         raise ValueError("--icp_iters > 0 refines against the object's mesh: it needs --data=depth and --mesh")
+    if gt_pose is not None and (data != "depth" or not mesh):
+        raise ValueError("--gt_pose scores the pose against the object's mesh (BOP metrics): it needs --data=depth and --mesh")
     icp_model = None
     if icp_iters > 0:
         from cppf2_amd import icp, render
         icp_model = icp.ModelPoints.from_mesh(render.load_mesh(mesh, mesh_scale))
+    bop_obj = None
+    if gt_pose is not None:
+        from cppf2_amd import bop, render
+        info = None
+        if models_info:
+            with open(models_info) as f:
+                info = json.load(f)
+        bop_obj = bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale), models_info=info, mesh_scale=mesh_scale)
+        gt_R, gt_t = bop.load_pose(gt_pose)
+        bop_reported, bop_width = [], None
     if categories is None:
         if category:
             categories = [category]
@@ -589,6 +606,27 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                 gt[:3, :3], gt[:3, 3] = scenes[b]["R"] * scenes[b]["diag"], scenes[b]["t"]
                 all_gt.append(gt)
                 all_gt_scale.append(scenes[b]["extent"] / scenes[b]["diag"])
+        if bop_obj is not None:
+            # the BOP errors of each instance's reported pose (and of its pose before ICP) against --gt_pose, on the depth
+            # image and K loaded above; an instance without an estimate scores +inf
+            nan = (np.full((3, 3), np.nan), np.full(3, np.nan))
+            reported = [(r["records"][r["pick"][b]][b] if icp_stats is None else r["selected"][b]) if r["pick"][b] >= 0 else None
+                        for b in range(B)]
+            poses = [(p_["R"], p_["t"]) if p_ is not None else nan for p_ in reported]
+            if icp_stats is not None:
+                poses += [(r["records"][r["pick"][b]][b]["R"], r["records"][r["pick"][b]][b]["t"]) if r["pick"][b] >= 0 else nan
+                          for b in range(B)]
+            err = bop.pose_errors(bop_obj, d, np.zeros(len(poses), dtype=np.int64), [p_[0] for p_ in poses],
+                                  [p_[1] for p_ in poses], [gt_R] * len(poses), [gt_t] * len(poses), K)
+
+            def block(j):
+                return dict(vsd=[float(x) for x in err["vsd"][j]], mssd=float(err["mssd"][j]), mspd=float(err["mspd"][j]))
+            for b, item in enumerate(summary[len(summary) - B:]):
+                item["bop"] = block(b)
+                if icp_stats is not None:
+                    item["bop_before_icp"] = block(B + b)
+            bop_reported.append({k_: v_[:B] for k_, v_ in err.items()})
+            bop_width = d.shape[1]
         inst += made
 
     report = dict(categories=categories, instances=len(summary),
@@ -596,6 +634,9 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
     if icp_model is not None:
         report["icp_refinement"] = "%d point-to-plane ICP iterations against %s (cppf_icp_refine)" % (icp_iters, os.path.basename(mesh))
         report["icp"] = [s_["icp"] for s_ in summary if "icp" in s_]
+    if bop_obj is not None and bop_reported:
+        errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
+        report["bop"] = dict(bop.average_recall(errs, bop_obj.diameter, bop_width), delta=bop.DELTA, taus=list(bop.TAUS))
     if len(categories) == 1:
         report["category"] = categories[0]
     scored = [s for s in summary if "rot_err_deg" in s]

@@ -363,6 +363,33 @@ int cppf_icp_refine(int B, const float* pts, const int32_t* pt_off, int max_n, c
                     int M, int iters, float d0, float d1, CppfSceneResult* results, float* stats, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* ---- instance-level pose errors: the BOP metrics VSD, MSSD, MSPD (Hodan et al.; BOP'19; the reference has no scorer) ----
+ * Both calls take P (estimate, ground truth) pairs, P <= 65535; P = 0 launches nothing.  h_K = (fx, fy, cx, cy), host doubles,
+ * one K for every pair.  Neither needs a workspace.  Integer atomics only: the results do not depend on the batch or the order.
+ * The exact order of the operations is stated in cppf2_amd/csrc/cppf_bop.hip.
+ *
+ * cppf_vsd_counts: Visible Surface Discrepancy as integer pixel counts.  depth_test float32[I,H,W] (metres, 0 = no reading),
+ * test_idx int32[P] (the test image of each pair; outside [0, I): the pair's row stays 0), depth_est / depth_gt float32[P,H,W]
+ * (the renders of the estimated and the true pose, cppf_render_depth's output; 0 = nothing drawn), diameter float32[P],
+ * taus float32[n_taus] (fractions of the diameter, 1 <= n_taus <= 32), H, W <= 8192.  Per pixel (r, c), in float64,
+ * dist(d) = d * sqrt(((c - cx)/fx)^2 + ((r - cy)/fy)^2 + 1) (the pixel's integer coordinates), and the BOP'19 visibility:
+ * vis_gt = d_gt > 0 && (dist_gt - dist_test <= delta || d_test == 0), vis_est = (d_est > 0 && (dist_est - dist_test <= delta ||
+ * d_test == 0)) || (vis_gt && d_est > 0).  counts int64[P, 2 + n_taus] = (union of the visible masks, their intersection,
+ * cost_k = intersection pixels with |dist_gt - dist_est| >= taus[k] * diameter).  The error at taus[k] is
+ * (cost_k + union - inter) / union, 1 when union = 0 (the "step" cost; cppf2_amd/bop.py forms it in float64).
+ *
+ * cppf_mssd_mspd: verts float32[V,3] (model frame), syms float64[S,12] (row-major 3x4 model -> model maps x -> R_s x + t_s; the
+ * identity among them), pose_est / pose_gt float64[P,12] (row-major 3x4 model -> OpenCV camera).  Out, float32[P]:
+ * mssd = min_s max_v |(R_e v + t_e) - (R_g (R_s v + t_s) + t_g)| (model units), mspd = the same with both points projected,
+ * pi(p) = (fx p_x / p_z + cx, fy p_y / p_z + cy) (pixels), +inf for an s at which some vertex has p_z <= 0 in either pose.  The
+ * per-(pair, symmetry) maps are formed in float64 and rounded to float32 once; the vertices go through them in float32.
+ * V >= 1, 1 <= S <= 2^24. */
+int cppf_vsd_counts(int P, int I, int H, int W, const float* depth_test, const int32_t* test_idx, const float* depth_est,
+                    const float* depth_gt, const double* h_K, double delta, const float* diameter, const float* taus, int n_taus,
+                    int64_t* counts, void* stream);
+int cppf_mssd_mspd(int P, const float* verts, int V, const double* syms, int S, const double* pose_est, const double* pose_gt,
+                   const double* h_K, float* mssd, float* mspd, void* stream);
+
 /* DINO-branch feature plumbing: replaces interpolate_features (dataset.py:40-59) = grid_sample
  * (bilinear, zeros padding, align_corners=False) of the patch-token map desc at the pixel centres of pts float32[n,2]
  * (x, y), then L2 normalisation over the C channels.  desc is addressed as desc[c*stride_c + y*stride_y + x*stride_x]
