@@ -305,3 +305,28 @@ __device__ __forceinline__ void wave_argmax(uint32_t& v, int64_t& i) {
     argmax_combine(v, i, ov, oi);
   }
 }
+
+// eval.py:295-313: the rotation of a record from an (up, right) pair of sphere bins.  float32 Gram-Schmidt of the right vote
+// against the up vote, the third column their cross product in float64.  R: row-major double[9].  One definition for
+// assemble_pose_kernel and pose_hypotheses_kernel, so that the hypotheses of the arg-max pair are the pass' own record.
+__device__ __forceinline__ void pose_from_bins(const float* __restrict__ sphere, int up_idx, int right_idx, int up_axis,
+                                               int right_axis, double* __restrict__ Rout) {
+  const float ux = sphere[3 * up_idx], uy = sphere[3 * up_idx + 1], uz = sphere[3 * up_idx + 2];
+  float rx = sphere[3 * right_idx], ry = sphere[3 * right_idx + 1], rz = sphere[3 * right_idx + 2];
+  const float d = (ux * rx + uy * ry) + uz * rz;
+  rx = rx - d * ux; ry = ry - d * uy; rz = rz - d * uz;
+  const float n = __builtin_sqrtf((rx * rx + ry * ry) + rz * rz) + 1e-9f;
+  rx = rx / n; ry = ry / n; rz = rz / n;
+  // column up_axis = u, column right_axis = r, the third = (column o+1) x (column o+2) in float64; written with selects, not
+  // a register array indexed by the axes (that would live in scratch memory)
+  const int o = 3 - up_axis - right_axis;
+  const bool u_first = (o + 1) % 3 == up_axis;
+  const double a0 = u_first ? ux : rx, a1 = u_first ? uy : ry, a2 = u_first ? uz : rz;
+  const double b0 = u_first ? rx : ux, b1 = u_first ? ry : uy, b2 = u_first ? rz : uz;
+  const double w[3] = {a1 * b2 - a2 * b1, a2 * b0 - a0 * b2, a0 * b1 - a1 * b0};
+  const float uu[3] = {ux, uy, uz}, rr[3] = {rx, ry, rz};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rout[3 * i + j] = j == up_axis ? (double)uu[i] : (j == right_axis ? (double)rr[i] : w[i]);
+}

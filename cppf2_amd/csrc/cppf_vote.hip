@@ -1844,23 +1844,7 @@ __global__ __launch_bounds__(256) void assemble_pose_kernel(
   r.ncell = grids ? grids[b].ncell : 0;
   r.pad_[0] = r.pad_[1] = r.pad_[2] = 0;
   r.scale[0] = s_med[0]; r.scale[1] = s_med[1]; r.scale[2] = s_med[2];
-  // eval.py:295-296: float32 Gram-Schmidt of the right vote against the up vote
-  const float ux = sphere[3 * r.up_idx], uy = sphere[3 * r.up_idx + 1], uz = sphere[3 * r.up_idx + 2];
-  float rx = sphere[3 * r.right_idx], ry = sphere[3 * r.right_idx + 1], rz = sphere[3 * r.right_idx + 2];
-  const float d = (ux * rx + uy * ry) + uz * rz;
-  rx = rx - d * ux; ry = ry - d * uy; rz = rz - d * uz;
-  const float n = __builtin_sqrtf((rx * rx + ry * ry) + rz * rz) + 1e-9f;
-  rx = rx / n; ry = ry / n; rz = rz / n;
-  double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-  R[0][up_axis] = ux; R[1][up_axis] = uy; R[2][up_axis] = uz;
-  R[0][right_axis] = rx; R[1][right_axis] = ry; R[2][right_axis] = rz;
-  const int o = 3 - up_axis - right_axis;
-  const int c1 = (o + 1) % 3, c2 = (o + 2) % 3;
-  R[0][o] = R[1][c1] * R[2][c2] - R[2][c1] * R[1][c2];
-  R[1][o] = R[2][c1] * R[0][c2] - R[0][c1] * R[2][c2];
-  R[2][o] = R[0][c1] * R[1][c2] - R[1][c1] * R[0][c2];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) r.R[3 * i + j] = R[i][j];
+  pose_from_bins(sphere, r.up_idx, r.right_idx, up_axis, right_axis, r.R);   // eval.py:295-313
   out[b] = r;
 }
 

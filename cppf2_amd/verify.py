@@ -1,0 +1,202 @@
+"""Instance-level pose-hypothesis verification by render and compare: several well-separated peaks of each rotation-bin vote
+become pose hypotheses (cppf_pose_hypotheses), each is refined against the object's mesh (cppf_icp_refine, optional), rendered
+(cppf_render_depth) and counted against the observed depth (cppf_depth_fit_counts), and the hypothesis that explains the most of
+the instance without hiding what the camera saw is kept.  The reference reports one rotation per pass, from the arg-max of each
+vote; it has no such step.
+
+    recs = hypotheses(pipe.counts[0], pipe.counts[1], pipe.sphere, pipe.results, H=8, up_axis=1, right_axis=0)
+    out = select(obj, depth, mask, K, recs, pts=pts, pt_off=pt_off, icp_model=model, icp_iters=30)
+    out["records"][b]                          # the chosen record of instance b: flags bit5, its hypothesis index in pad_[1]
+
+Frame: the record convention of icp.py and bop.py -- the model centred on its bounding-box centre, metres, p = R m + t.
+DESIGN.md section 15 states the arithmetic and how the defaults were chosen.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _lib, bop, icp, ops, render
+from ._lib import CppfError
+from .pipeline import RESULT_DTYPE
+
+_L = _lib.load()
+
+PEAKS = 4                                   # peaks per vote
+COS_SEP = float(np.cos(np.deg2rad(20.0)))   # a bin within 20 degrees of an earlier peak is no new peak
+COS_PERP = float(np.cos(np.deg2rad(45.0)))  # (up, right) pairs more than 45 degrees from perpendicular are dropped
+TAU = 0.02                                  # metres: a drawn pixel fits the observation within TAU
+EMPTY = 1                                   # CppfSceneResult.flags bit0: no hypothesis in this slot
+CHOSEN = 32                                 # CppfSceneResult.flags bit5: the record verification chose (index in pad_[1])
+RENDER_CHUNK = 64                           # hypotheses rendered and counted per call
+N_COUNTS = 4                                # drawn, observed, violations, unexplained; then fit_k per tau
+
+
+def hypotheses(counts_up, counts_right, sphere, base, H, up_axis, right_axis, K=PEAKS, cos_sep=COS_SEP, cos_perp=COS_PERP,
+               y_only=False, with_peaks=False):
+    """cppf_pose_hypotheses on the current stream: device uint8 [B,H,160] records (slot 0 = the base record; empty slots carry
+    flags bit0), and with with_peaks also (peak_idx int32 [B,2,K], peak_count float32 [B,2,K]).  counts_up / counts_right
+    float32 [B,S] (a VotingPipeline's counts[0] / counts[1]), sphere float32 [S,3], base: device uint8 [B,160] records (a
+    pipeline's results) or a RESULT_DTYPE array."""
+    dev = ops._dev()
+    cu = ops._t(counts_up, torch.float32, dev)
+    cr = ops._t(counts_right, torch.float32, dev)
+    sph = ops._t(sphere, torch.float32, dev).reshape(-1, 3)
+    if isinstance(base, np.ndarray):
+        base = torch.from_numpy(np.frombuffer(np.ascontiguousarray(base).tobytes(), dtype=np.uint8).reshape(-1, 160).copy()).to(dev)
+    if base.dtype != torch.uint8 or base.dim() != 2 or base.shape[1] != 160 or not base.is_contiguous():
+        raise CppfError("verify.hypotheses: base must be contiguous uint8 [B,160] records")
+    B, S = base.shape[0], sph.shape[0]
+    if cu.shape != (B, S) or cr.shape != (B, S):
+        raise CppfError("verify.hypotheses: counts must be [%d,%d], not %s and %s" % (B, S, tuple(cu.shape), tuple(cr.shape)))
+    out = torch.empty((B, int(H), 160), dtype=torch.uint8, device=dev)
+    pi = torch.empty((B, 2, int(K)), dtype=torch.int32, device=dev) if with_peaks else None
+    pc = torch.empty((B, 2, int(K)), dtype=torch.float32, device=dev) if with_peaks else None
+    _lib.check(_L.cppf_pose_hypotheses(B, S, ops._p(cu), ops._p(cr), ops._p(sph), int(K), C.c_float(cos_sep),
+                                       C.c_float(cos_perp), int(up_axis), int(right_axis), int(bool(y_only)), ops._p(base),
+                                       int(H), ops._p(out), ops._p(pi), ops._p(pc), ops._stream()), "cppf_pose_hypotheses")
+    return (out, pi, pc) if with_peaks else out
+
+
+def _images(x, dtype, dev):
+    t = ops._t(x, dtype, dev)
+    return t[None] if t.dim() == 2 else t
+
+
+def fit_counts(depth, mask, hyp_off, renders, taus=(TAU,)):
+    """cppf_depth_fit_counts: int64 [P, 4 + n_taus] device tensor (drawn, observed, violations, unexplained, fit_1 .. fit_n).
+    depth float32 [I,H,W] or [H,W] (metres, 0 = no reading), mask [I,H,W] or [H,W] (non-zero: the instance), hyp_off int
+    [I+1] (host: renders hyp_off[i] .. hyp_off[i+1]-1 are hypotheses of image i), renders float32 [P,H,W] (0 = nothing
+    drawn), taus: metres, at most 32 (taus[0] is also the violation margin)."""
+    dev = ops._dev()
+    d = _images(depth, torch.float32, dev)
+    I, H, W = d.shape
+    m = _images(torch.as_tensor(mask) != 0 if torch.is_tensor(mask) else np.asarray(mask) != 0, torch.uint8, dev)
+    if m.shape != d.shape:
+        raise CppfError("verify.fit_counts: mask %s for depth %s" % (tuple(m.shape), tuple(d.shape)))
+    off = np.ascontiguousarray((hyp_off.cpu().numpy() if torch.is_tensor(hyp_off) else np.asarray(hyp_off)).reshape(-1),
+                               dtype=np.int32)
+    if off.size != I + 1:
+        raise CppfError("verify.fit_counts: hyp_off of %d entries for %d images" % (off.size, I))
+    r = ops._t(renders, torch.float32, dev).reshape(-1, H, W)
+    P = r.shape[0]
+    tau = ops._t(np.asarray(taus, dtype=np.float32).reshape(-1), torch.float32, dev)
+    counts = torch.zeros((P, N_COUNTS + tau.numel()), dtype=torch.int64, device=dev)
+    _lib.check(_L.cppf_depth_fit_counts(I, H, W, ops._p(d), ops._p(m), off.ctypes.data_as(C.c_void_p), P, ops._p(r), ops._p(tau),
+                                        tau.numel(), ops._p(counts), ops._stream()), "cppf_depth_fit_counts")
+    return counts
+
+
+def score(counts):
+    """float64 [P]: fit_0 / (observed + violations) -- the share of the observed instance the render explains within taus[0],
+    with every pixel the render would hide counted against it; 0 where the denominator is 0."""
+    c = (counts.cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)).astype(np.int64)
+    c = c.reshape(len(c), -1)
+    den = c[:, 1] + c[:, 2]
+    return np.where(den > 0, c[:, N_COUNTS].astype(np.float64) / np.maximum(den, 1).astype(np.float64), 0.0)
+
+
+def choose(scores, empty=None):
+    """int64 [B]: per row of scores [B,H] the index of the highest score, the lower index on ties (hypothesis 0 wins unless
+    something beats it); entries flagged in empty [B,H] never win (-1 when every entry of a row is)."""
+    s = np.asarray(scores, dtype=np.float64)
+    s = s.reshape(len(s), -1).copy()
+    if empty is not None:
+        s[np.asarray(empty, dtype=bool).reshape(s.shape)] = -np.inf
+    s[np.isnan(s)] = -np.inf
+    pick = np.argmax(s, axis=1).astype(np.int64)           # the first maximum
+    pick[~np.isfinite(s.max(axis=1, initial=-np.inf))] = -1
+    return pick
+
+
+def _as_records(records):
+    """(RESULT_DTYPE [B,H] host copy, device uint8 [B*H,160])."""
+    dev = ops._dev()
+    if torch.is_tensor(records):
+        rec = records.reshape(records.shape[0], -1, 160)
+        host = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=RESULT_DTYPE).reshape(rec.shape[:2]).copy()
+    else:
+        host = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
+        host = host.reshape(len(host), -1).copy()
+    raw = np.frombuffer(host.tobytes(), dtype=np.uint8).reshape(-1, 160).copy()
+    return host, torch.from_numpy(raw).to(dev)
+
+
+def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_model=None, icp_iters=0, tau=TAU,
+           chunk=RENDER_CHUNK):
+    """Verifies H pose hypotheses of each of B instances and keeps one per instance.
+
+    obj_or_mesh: a bop.ObjectInfo or a render.Mesh (metres); depth [B,H_img,W_img] or [H_img,W_img] (metres, 0 = no reading) and
+    mask (non-zero: the instance) of the same shape: instance b is seen in image b; K: the camera's 3x3 intrinsics; records
+    [B,H] (RESULT_DTYPE, or a device uint8 [B,H,160] tensor such as hypotheses() returns).  With icp_iters > 0, every
+    non-empty hypothesis is first refined by icp.refine against icp_model (an icp.ModelPoints) from the instance's points pts
+    float32 [N,3] (camera frame), pt_off int [B+1].  Each hypothesis is then rendered (back faces culled); one that is not
+    finite, or puts a vertex nearer than render.ZNEAR (the renderer does not clip), is not drawn and scores 0.  score() of its
+    fit_counts at (tau,) ranks it, and choose() picks.
+
+    Returns dict(records RESULT_DTYPE [B] (the chosen records, flags bit5, the hypothesis index in pad_[1]; an instance whose
+    hypotheses are all empty keeps records[b, 0] unmarked), chosen int64 [B] (-1: none), scores float64 [B,H] (NaN for empty
+    slots), counts int64 [B,H,5], hypotheses RESULT_DTYPE [B,H] (after ICP), icp float32 [B,H,4] or None)."""
+    obj = obj_or_mesh if isinstance(obj_or_mesh, bop.ObjectInfo) else bop.ObjectInfo.from_mesh(obj_or_mesh)
+    dev = ops._dev()
+    host, rec = _as_records(records)
+    B, Hh = host.shape
+    d = _images(depth, torch.float32, dev)
+    m = _images(torch.as_tensor(mask) != 0 if torch.is_tensor(mask) else np.asarray(mask) != 0, torch.uint8, dev)
+    if d.shape[0] != B or m.shape != d.shape:
+        raise CppfError("verify.select: %d instances, depth %s, mask %s" % (B, tuple(d.shape), tuple(m.shape)))
+    _, Hi, Wi = d.shape
+    empty = (host["flags"] & EMPTY) != 0
+    stats = None
+    if int(icp_iters) > 0 and B:
+        if icp_model is None or pts is None or pt_off is None:
+            raise ValueError("verify.select: icp_iters > 0 needs icp_model, pts and pt_off")
+        off = (pt_off.cpu().numpy() if torch.is_tensor(pt_off) else np.asarray(pt_off)).astype(np.int64).reshape(-1)
+        if off.size != B + 1:
+            raise CppfError("verify.select: pt_off of %d entries for %d instances" % (off.size, B))
+        p = ops._t(pts, torch.float32, dev).reshape(-1, 3)
+        # each instance's points once per hypothesis: the B*H records refine in one batch
+        sel = torch.from_numpy(np.concatenate([np.arange(off[b], off[b + 1]) for b in range(B) for _ in range(Hh)])).to(dev)
+        rep_off = np.concatenate([[0], np.cumsum(np.repeat(np.diff(off), Hh))])
+        stats = icp.refine(icp_model, p[sel].contiguous(), rep_off, rec, iters=int(icp_iters))
+        stats = stats.cpu().numpy().reshape(B, Hh, 4)
+        host = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=RESULT_DTYPE).reshape(B, Hh).copy()
+    # poses of the records (float64), drawable ones
+    R = host["R"].reshape(-1, 3, 3)
+    t = host["t"].reshape(-1, 3)
+    P = B * Hh
+    flat_empty = empty.reshape(-1)
+    finite = np.isfinite(R).all((1, 2)) & np.isfinite(t).all(1)
+    z = np.full(P, -np.inf)
+    ok = finite & ~flat_empty
+    if ok.any():
+        z[ok] = np.einsum("pj,vj->pv", R[ok, 2, :], obj.verts).min(1) + t[ok, 2]
+    draw = ok & (z >= render.ZNEAR * (1 + 1e-5))
+    counts = np.zeros((P, N_COUNTS + 1), dtype=np.int64)
+    verts, faces, _ = obj.device(dev)
+    F = faces.shape[0]
+    img_of = np.repeat(np.arange(B), Hh)
+    for a in range(0, P, int(chunk)):
+        idx = np.arange(a, min(P, a + int(chunk)))
+        dr = idx[draw[idx]]
+        ren = torch.zeros((idx.size, Hi, Wi), dtype=torch.float32, device=dev)
+        if dr.size:
+            poses = torch.from_numpy(np.concatenate([R[dr], t[dr, :, None]], 2).reshape(-1, 12).astype(np.float32)).to(dev)
+            ren[torch.from_numpy(dr - a).to(dev)] = render.render_depth(verts, faces.repeat(dr.size, 1),
+                                                                        ops._offsets([F] * dr.size, dev), poses, K, Hi, Wi,
+                                                                        cull=True)
+        # the chunk's hypotheses lie on consecutive images: offsets over all B images, zero-length outside the chunk
+        hyp_off = np.searchsorted(img_of[idx], np.arange(B + 1), side="left").astype(np.int32)
+        counts[idx] = fit_counts(d, m, hyp_off, ren, (tau,)).cpu().numpy()
+    sc = score(counts)
+    sc[~draw] = 0.0
+    sc = sc.reshape(B, Hh)
+    pick = choose(sc, empty)
+    sc[empty] = np.nan
+    out = host[np.arange(B), np.maximum(pick, 0)].copy()
+    hit = pick >= 0
+    out["flags"][hit] |= CHOSEN
+    out["pad_"][hit, 1] = pick[hit]
+    return dict(records=out, chosen=pick, scores=sc, counts=counts.reshape(B, Hh, -1), hypotheses=host, icp=stats)

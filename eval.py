@@ -26,6 +26,12 @@ What the image cannot provide is stated, not faked:
     (a 3x4 or 4x4 model -> OpenCV camera matrix in the record convention, metres) with the BOP metrics VSD, MSSD and MSPD
     (cppf2_amd.bop; --models_info: the object's BOP models_info entry, for its symmetries and diameter): each result gains
     `bop` (and `bop_before_icp` with --icp_iters > 0), the report their average recall.
+  * `--data=depth --mesh=<ply|obj> --hypotheses=H [--verify_tau=0.01]` (H > 1) verifies H pose hypotheses of the instance
+    against the depth image (cppf2_amd.verify, cppf_pose_hypotheses + cppf_depth_fit_counts; not in the reference): the
+    selected pose first, then the other peak combinations of both votes of the picked pass and of the other enabled pass;
+    each is refined by --icp_iters, rendered, and the one whose render explains the most of the observed instance is
+    reported.  Each result gains `verify`, and with --gt_pose `bop_first` (the errors of the selected pose: what H = 1
+    reports).  --hypotheses=1 (default): off.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import json
@@ -149,7 +155,7 @@ def _pipelines(dev, Ns, num_pairs, k, cfg, num_rots, angle_tol, backproj_ratio, 
 @torch.no_grad()
 def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_pairs, num_rots, angle_tol=1.,
                  imp_wt_margin=0.01, backproj_ratio=.1, opt=False, geo_branch=True, visual_branch=True, up_sym=False,
-                 priors=None, keep=False, scale_priors=None, two_streams=True):
+                 priors=None, keep=False, scale_priors=None, two_streams=True, hypotheses=None):
     """eval.py:207-372 for a batch of instances of one category.  pcs: list of float32 [N_b,3]; descs: list of float32
     [N_b,1024] arrays or (device) tensors (DINOv2 features at the points: inputs to the path); priors: optional callable(idx_global, base) -> logit
     prior [T,6,nb] added to both models' logits; scale_priors: optional float32 [B,3] teacher box extents that stand in for
@@ -158,7 +164,10 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
     two_streams (default): the DINO pass and the SHOT pass (descriptors included) run on two HIP streams at once, each with
     working buffers of its own (VotingPipeline.twin) -- one pass' voting and descriptor kernels beside the other's wide
     matrix-core kernels; the only cross-stream dependency is the DINO pass' scale, which scores the SHOT pass too
-    (eval.py:308-310).  Same records as the one-stream order (keep=True, which hands out intermediates, uses that order)."""
+    (eval.py:308-310).  Same records as the one-stream order (keep=True, which hands out intermediates, uses that order).
+    hypotheses: None (default) or H >= 1: each pass also forms H pose hypotheses from the peaks of its two votes
+    (verify.hypotheses, right after its vote and before `opt`; slot 0 is the pass' assembled record), returned as
+    out["hypotheses"] = [2 x RESULT_DTYPE [B,H]] (model 0, model 1)."""
     dev = ops._dev()
     B = len(pcs)
     Ns = [int(p.shape[0]) for p in pcs]
@@ -192,6 +201,12 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
         st_.wait_stream(main)
     kept = []
     extra = {}
+    hyps = [None, None]
+    if hypotheses is not None:
+        from cppf2_amd import verify
+        hypotheses = int(hypotheses)
+        if hypotheses < 1:
+            raise ValueError("hypotheses must be >= 1, not %d" % hypotheses)
     dino_scored = torch.cuda.Event() if two else None
 
     def one_pass(model_idx):
@@ -227,6 +242,10 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
             return (scale_prior + 1e-3 * s_).contiguous() if scale_prior is not None else s_.contiguous()
         pred_scales = scales() if keep else scales
         pp.vote(pts, idx, None if pred_cls is None else pred_cls.contiguous(), u, pred_scales)
+        if hypotheses is not None:
+            # here, on this pass' stream: the one-stream order reuses pp.counts for the next pass, and `opt` rewrites the records
+            hyps[model_idx] = verify.hypotheses(pp.counts[0], pp.counts[1], pp.sphere, pp.results, hypotheses, pp.up_axis,
+                                                pp.right_axis, y_only=up_sym)
         if opt:
             pp.refine(pts, idx, up_sym)                                                    # eval.py:319-355
         if two and model_idx == 0:
@@ -265,6 +284,8 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
     scale_norm = np.array([np.linalg.norm(s_) for s_ in scale], dtype=np.float32)          # np.linalg.norm per instance
     out = dict(records=records, selected=chosen, losses=losses, pick=pick, best=best, scale=scale.astype(np.float64),
                scale_norm=scale_norm.astype(np.float64), idx=idx, pipe=pipe, pts=pts)
+    if hypotheses is not None:
+        out["hypotheses"] = [pipe.results_to_numpy(h_.reshape(-1, 160)).reshape(B, hypotheses) for h_ in hyps]
     if keep:
         out["kept"] = kept
         out["shot_feat"], out["normal"] = extra["shot_feat"].cpu().numpy(), extra["normal"].cpu().numpy()
@@ -472,6 +493,33 @@ def main_nocs(setups, log_dir, data_root="NOCS/real_test", out_dir=None, desc_np
 
 
 
+def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, icp_iters, tau):
+    """The hypotheses of each instance, in order: its selected record (after `opt`: what H = 1 reports), the other peak
+    combinations of the picked pass, then those of the other pass if it is enabled; cut at H (empty slots past the end).  An
+    instance without a pick gets only empty slots.  Then verify.select (ICP first when icp_iters > 0) on the instance's image."""
+    from cppf2_amd import verify
+    from cppf2_amd.pipeline import RESULT_DTYPE
+    recs = np.zeros((B, H), dtype=RESULT_DTYPE)
+    for b in range(B):
+        p_ = int(r["pick"][b])
+        if p_ < 0:
+            lst = []
+        else:
+            lst = [r["selected"][b]] + list(r["hypotheses"][p_][b][1:])
+            if enabled[1 - p_]:
+                lst += list(r["hypotheses"][1 - p_][b])
+            lst = [h_ for h_ in lst if not h_["flags"] & verify.EMPTY][:H]
+        for h in range(H):
+            if h < len(lst):
+                recs[b, h] = lst[h]
+            else:
+                recs[b, h] = r["selected"][b]
+                recs["flags"][b, h] |= verify.EMPTY
+    img = np.broadcast_to(np.asarray(depth, dtype=np.float32), (B,) + np.shape(depth))
+    msk = np.broadcast_to(np.asarray(mask, dtype=bool), (B,) + np.shape(mask))
+    return verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=icp_iters, tau=tau)
+
+
 def _teacher_prior(canon, dev):
     canon = torch.from_numpy(canon).to(dev)
     kb = torch.arange(32, device=dev, dtype=torch.float32)
@@ -488,9 +536,14 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          category=None, categories=None, seed=0, ckpt_dir=None, ckpt_shot=None, ckpt_dino=None, depth=None, mask=None,
          intrinsics=None, depth_scale=1000.0, out=None, out_pkl=None, log_dir=None, data_root="NOCS/real_test", out_dir=None,
          desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
-         models_info=None):
+         models_info=None, hypotheses=1, verify_tau=None):
     custom = False
     icp_iters = int(icp_iters)
+    hypotheses = int(hypotheses)
+    if hypotheses < 1:
+        raise ValueError("--hypotheses must be >= 1, not %d" % hypotheses)
+    if hypotheses > 1 and (data != "depth" or not mesh):
+        raise ValueError("--hypotheses > 1 verifies poses against the object's mesh: it needs --data=depth and --mesh")
     if icp_iters > 0 and (data != "depth" or not mesh):
         raise ValueError("--icp_iters > 0 refines against the object's mesh: it needs --data=depth and --mesh")
     if gt_pose is not None and (data != "depth" or not mesh):
@@ -509,6 +562,11 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         bop_obj = bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale), models_info=info, mesh_scale=mesh_scale)
         gt_R, gt_t = bop.load_pose(gt_pose)
         bop_reported, bop_width = [], None
+    verify_obj = None
+    if hypotheses > 1:
+        from cppf2_amd import bop, render, verify
+        verify_tau = verify.TAU if verify_tau is None else float(verify_tau)
+        verify_obj = bop_obj if bop_obj is not None else bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale))
     if categories is None:
         if category:
             categories = [category]
@@ -572,10 +630,16 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
             scale_priors = np.stack([s["extent"] for s in scenes])
         r = run_ensemble(cfg, dino_model, shot_model, [s["pc"] for s in scenes], descs, seed, scene_ids, num_pairs,
                          num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
-                         up_sym, priors, scale_priors=scale_priors)
+                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if verify_obj is not None else None)
         cls_id = category2id.get(cat, 0)
         icp_stats = None
-        if icp_model is not None:
+        ver = None
+        if verify_obj is not None:
+            ver = _verify_instances(r, B, hypotheses, (geo_branch, visual_branch), verify_obj, d, m, K,
+                                    np.cumsum([0] + [s["pc"].shape[0] for s in scenes]), icp_model, icp_iters, verify_tau)
+            if icp_model is not None:
+                icp_stats = ver["icp"][np.arange(B), np.maximum(ver["chosen"], 0)]
+        elif icp_model is not None:
             # after the ensemble selection (and `opt`): the selected record of each instance against the mesh
             icp_stats = icp.refine(icp_model, r["pts"], np.cumsum([0] + [s["pc"].shape[0] for s in scenes]), r["selected"],
                                    iters=icp_iters)
@@ -584,6 +648,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
             item = dict(scene=scene_ids[b], category=cat, model=None)
             if r["pick"][b] >= 0:                                               # eval.py:367-372
                 rec = r["records"][r["pick"][b]][b] if icp_stats is None else r["selected"][b]
+                if ver is not None:
+                    rec = ver["records"][b]
                 RT[:3, :3] = rec["R"] * r["scale_norm"][b]
                 RT[:3, 3] = rec["t"]
                 if r["scale_norm"][b] > 0:
@@ -594,6 +660,10 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                 if icp_stats is not None:
                     st = icp_stats[b]
                     item["icp"] = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
+                if ver is not None:
+                    c_ = int(ver["chosen"][b])
+                    item["verify"] = dict(hypotheses=int(np.count_nonzero((ver["hypotheses"][b]["flags"] & verify.EMPTY) == 0)),
+                                          chosen=c_, score=float(ver["scores"][b, c_]), score_first=float(ver["scores"][b, 0]))
                 if scenes[b]["R"] is not None:
                     item["tr_err_cm"] = float(np.linalg.norm(rec["t"] - scenes[b]["t"]) * 100)
                     item["rot_err_deg"] = geometry.rot_err_deg(rec["R"], scenes[b]["R"], up_sym)
@@ -612,7 +682,12 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
             nan = (np.full((3, 3), np.nan), np.full(3, np.nan))
             reported = [(r["records"][r["pick"][b]][b] if icp_stats is None else r["selected"][b]) if r["pick"][b] >= 0 else None
                         for b in range(B)]
+            if ver is not None:
+                first = [ver["hypotheses"][b, 0] if r["pick"][b] >= 0 else None for b in range(B)]
+                reported = [ver["records"][b] if r["pick"][b] >= 0 else None for b in range(B)]
             poses = [(p_["R"], p_["t"]) if p_ is not None else nan for p_ in reported]
+            if ver is not None:
+                poses += [(p_["R"], p_["t"]) if p_ is not None else nan for p_ in first]
             if icp_stats is not None:
                 poses += [(r["records"][r["pick"][b]][b]["R"], r["records"][r["pick"][b]][b]["t"]) if r["pick"][b] >= 0 else nan
                           for b in range(B)]
@@ -621,10 +696,13 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
 
             def block(j):
                 return dict(vsd=[float(x) for x in err["vsd"][j]], mssd=float(err["mssd"][j]), mspd=float(err["mspd"][j]))
+            nv = B if ver is not None else 0
             for b, item in enumerate(summary[len(summary) - B:]):
                 item["bop"] = block(b)
+                if ver is not None:
+                    item["bop_first"] = block(B + b)
                 if icp_stats is not None:
-                    item["bop_before_icp"] = block(B + b)
+                    item["bop_before_icp"] = block(B + nv + b)
             bop_reported.append({k_: v_[:B] for k_, v_ in err.items()})
             bop_width = d.shape[1]
         inst += made
@@ -634,6 +712,9 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
     if icp_model is not None:
         report["icp_refinement"] = "%d point-to-plane ICP iterations against %s (cppf_icp_refine)" % (icp_iters, os.path.basename(mesh))
         report["icp"] = [s_["icp"] for s_ in summary if "icp" in s_]
+    if verify_obj is not None:
+        report["verification"] = ("%d pose hypotheses per instance from %d peaks per vote, rendered and compared with the depth "
+                                  "at tau = %g m (cppf_pose_hypotheses, cppf_depth_fit_counts)" % (hypotheses, verify.PEAKS, verify_tau))
     if bop_obj is not None and bop_reported:
         errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
         report["bop"] = dict(bop.average_recall(errs, bop_obj.diameter, bop_width), delta=bop.DELTA, taus=list(bop.TAUS))

@@ -69,7 +69,9 @@ typedef struct CppfSceneResult {
   int32_t  kept;         /* pairs surviving the back-vote filter, eval.py:258 */
   float    up_count;     /* counts[up_idx] */
   float    right_count;  /* counts[right_idx] */
-  int32_t  flags;        /* CppfSceneGrid.flags | (bit2: grid larger than cells_cap) */
+  int32_t  flags;        /* CppfSceneGrid.flags | (bit2: grid larger than cells_cap); bit3: refined by cppf_refine_pose;
+                            bit4: refined by cppf_icp_refine; bit5: the hypothesis verification chose this record, its
+                            hypothesis index in pad_[1] (cppf2_amd/verify.py) */
   int32_t  ncell;        /* cells of the scene's vote grid */
   int32_t  pad_[3];
 } CppfSceneResult;
@@ -389,6 +391,36 @@ int cppf_vsd_counts(int P, int I, int H, int W, const float* depth_test, const i
                     int64_t* counts, void* stream);
 int cppf_mssd_mspd(int P, const float* verts, int V, const double* syms, int S, const double* pose_est, const double* pose_gt,
                    const double* h_K, float* mssd, float* mspd, void* stream);
+
+/* ---- instance-level hypothesis verification: render and compare (not in the reference) -------------------------------
+ * Several peaks of each rotation-bin vote become pose hypotheses; each hypothesis' render (cppf_render_depth) is counted
+ * against the observed depth, and cppf2_amd/verify.py keeps the one that explains most of it.  The exact order of the
+ * operations is stated in cppf2_amd/csrc/cppf_verify.hip.  Neither call needs a workspace; a count of 0 launches nothing.
+ *
+ * cppf_pose_hypotheses: counts_up / counts_right float32[B,S] (one pass' per-bin counts of the two votes, cppf_rot_bins2's
+ * counts[0] / counts[1]), sphere float32[S,3], base CppfSceneResult[B] (the pass' records, cppf_assemble_pose's output).
+ * Per scene and vote, up to K peaks (1 <= K <= 32): peak 0 = the first maximum (rot_bins_final's rule: top_idx); peak k = the
+ * first maximum over the bins with a count > 0 that are no earlier peak and have a dot product < cos_sep (float32,
+ * -1 <= cos_sep <= 1) with every earlier peak (antipodes are different peaks).  y_only (up-symmetric category): the right
+ * vote keeps peak 0 only.  Combinations (up peak i, right peak j): (0, 0), then every other one with |u.r| <= cos_perp
+ * (0 <= cos_perp <= 1) by descending up_count[i] * right_count[j] (float64), ties by (i, j); the first H (1 <= H <= 1024) go
+ * to out CppfSceneResult[B,H]: the base record with up_idx, right_idx, up_count, right_count of the combination and R by
+ * cppf_assemble_pose's Gram-Schmidt -- slot 0 is the base record itself --; slots without a combination: the base record with
+ * flags bit0 (empty), up_idx = right_idx = -1 and zero counts.  Optional (NULL: not written): peak_idx int32[B,2,K] and
+ * peak_count float32[B,2,K] (vote-major; -1 and 0 past a vote's last peak).  up_axis != right_axis in [0, 3).
+ *
+ * cppf_depth_fit_counts: I observed images depth float32[I,H,W] (metres, 0 = no reading) with their instance masks uint8[I,H,W]
+ * (!= 0: the instance), P renders float32[P,H,W] (0 = nothing drawn), h_hyp_off int32[I+1] on the HOST (renders
+ * h_hyp_off[i] .. h_hyp_off[i+1]-1 are hypotheses of image i; 0 = h_hyp_off[0] <= ... <= h_hyp_off[I] = P <= 2^24), taus
+ * float32[n_taus] (metres, 1 <= n_taus <= 32), H, W <= 8192.  counts int64[P, 4 + n_taus], per pixel with d_o - d_h formed in
+ * float64: drawn (d_h > 0), observed (mask && d_o > 0), violations (d_h > 0 && d_o > 0 && d_o - d_h > taus[0], any pixel: the
+ * model would hide a surface the camera saw), unexplained (mask && d_o > 0 && d_h == 0), fit_k (mask && d_o > 0 && d_h > 0 &&
+ * |d_h - d_o| <= taus[k]).  Integer atomics only: the counts of a hypothesis do not depend on the batch or the order. */
+int cppf_pose_hypotheses(int B, int S, const float* counts_up, const float* counts_right, const float* sphere, int K,
+                         float cos_sep, float cos_perp, int up_axis, int right_axis, int y_only, const CppfSceneResult* base,
+                         int H, CppfSceneResult* out, int32_t* peak_idx, float* peak_count, void* stream);
+int cppf_depth_fit_counts(int I, int H, int W, const float* depth, const uint8_t* mask, const int32_t* h_hyp_off, int P,
+                          const float* renders, const float* taus, int n_taus, int64_t* counts, void* stream);
 
 /* DINO-branch feature plumbing: replaces interpolate_features (dataset.py:40-59) = grid_sample
  * (bilinear, zeros padding, align_corners=False) of the patch-token map desc at the pixel centres of pts float32[n,2]
