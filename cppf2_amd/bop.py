@@ -1,6 +1,7 @@
 """Instance-level pose errors on the GPU: the BOP metrics (Hodan et al., "On Evaluation of 6D Object Pose Estimation", ECCVW 2016;
 the BOP'19 challenge's variants) -- VSD (Visible Surface Discrepancy, cppf_vsd_counts), MSSD and MSPD (Maximum Symmetry-aware
-Surface / Projection Distance, cppf_mssd_mspd) -- and their average recall.  The reference has no such scorer.
+Surface / Projection Distance, cppf_mssd_mspd) -- and their average recall; and the visibility of ground-truth instances in their
+test images (cppf_gt_visibility: BOP's scene_gt_info counts and boxes, mask_visib).  The reference has no such scorer.
 
     mesh = render.load_mesh("obj_000015.ply", 0.001)
     obj = ObjectInfo.from_mesh(mesh, models_info=info)              # info: the object's entry of a BOP models_info.json
@@ -134,6 +135,17 @@ def pose_from_bop(R, t, mesh_scale, centre):
     return (R[0], tp[0]) if single else (R, tp)
 
 
+def pose_to_bop(R, t, mesh_scale, centre):
+    """The inverse of pose_from_bop: record-convention poses (centred model, metres) -> BOP's (R, (t - R centre) / mesh_scale),
+    x_cam = R x + t on the uncentred model in the model file's units.  R [3,3] or [N,3,3], t [3] or [N,3]."""
+    R = np.asarray(R, dtype=np.float64)
+    single = R.ndim == 2
+    R = R.reshape(-1, 3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(-1, 3)
+    tb = (t - np.einsum("pij,j->pi", R, np.asarray(centre, dtype=np.float64).reshape(3))) / float(mesh_scale)
+    return (R[0], tb[0]) if single else (R, tb)
+
+
 def load_pose(path):
     """(R [3,3], t [3]) from a .npy or whitespace text file holding a 3x4 or 4x4 model -> camera matrix."""
     M = np.load(path) if str(path).endswith(".npy") else np.loadtxt(path)
@@ -204,6 +216,76 @@ def mssd_mspd(verts, syms, pose_est, pose_gt, K):
         _lib.check(_L.cppf_mssd_mspd(n, ops._p(v), v.shape[0], ops._p(S_), S_.shape[0], ops._p(pe[a:]), ops._p(pg[a:]), _hK(K),
                                      ops._p(mssd[a:]), ops._p(mspd[a:]), ops._stream()), "cppf_mssd_mspd")
     return mssd, mspd
+
+
+def gt_visibility_counts(depth_test, img_idx, renders, K, delta=DELTA, masks=False):
+    """cppf_gt_visibility: (counts int64 [G,3] = (#all, #valid, #visib), bbox int32 [G,8] = (x, y, w, h) of all, then of visib,
+    mask uint8 [G,H,W] (255 = visible) or None) device tensors.  depth_test [I,H,W] or [H,W] (metres, 0 = no reading), img_idx
+    int [G] (or one for all), renders [G,H,W] (each instance rendered alone, 0 = nothing drawn)."""
+    dev = ops._dev()
+    dt = _depth3(depth_test, dev)
+    I, H, W = dt.shape
+    rn = ops._t(renders, torch.float32, dev).reshape(-1, H, W)
+    G = rn.shape[0]
+    ii = ops._t(np.broadcast_to(np.asarray(img_idx, dtype=np.int32), (G,)) if not torch.is_tensor(img_idx) else img_idx,
+                torch.int32, dev).reshape(-1)
+    if ii.numel() != G:
+        raise CppfError("bop.gt_visibility_counts: %d renders, %d image indices" % (G, ii.numel()))
+    counts = torch.empty((G, 3), dtype=torch.int64, device=dev)
+    bbox = torch.empty((G, 8), dtype=torch.int32, device=dev)
+    mask = torch.empty((G, H, W), dtype=torch.uint8, device=dev) if masks else None
+    for a in range(0, max(G, 1), MAX_PAIRS):
+        n = min(MAX_PAIRS, G - a)
+        _lib.check(_L.cppf_gt_visibility(n, I, H, W, ops._p(dt), ops._p(ii[a:]), ops._p(rn[a:]), _hK(K), C.c_double(float(delta)),
+                                         ops._p(counts[a:]), ops._p(bbox[a:]), ops._p(mask[a:]) if masks else None,
+                                         ops._stream()), "cppf_gt_visibility")
+    return counts, bbox, mask
+
+
+def gt_visibility(obj_or_objs, depth_test, img_idx, R, t, K, delta=DELTA, masks=False, chunk=2 * RENDER_CHUNK):
+    """What the test images show of G ground-truth instances (BOP's scene_gt_info entries and mask_visib): each instance is
+    rendered alone (render.render_depth, back faces culled, `chunk` instances per call) and compared with its image by
+    cppf_gt_visibility.  obj_or_objs: one ObjectInfo for all instances or one per instance; depth_test [I,H,W] or [H,W]
+    (metres, 0 = no reading), img_idx int [G] (or one for all), R [G,3,3], t [G,3]: poses in the record convention (every
+    instance beyond render.ZNEAR: the renderer does not clip).  Returns dict(px_count_all, px_count_valid, px_count_visib
+    int64 [G], visib_fract float64 [G] (#visib / #all, 0 when nothing is drawn), bbox_obj, bbox_visib int32 [G,4] (x, y, w, h;
+    -1 when empty; bbox_obj is the in-image part's box), mask_visib uint8 [G,H,W] host array (255 = visible) or None)."""
+    dev = ops._dev()
+    P = _poses(R, t)
+    G = len(P)
+    objs = list(obj_or_objs) if isinstance(obj_or_objs, (list, tuple)) else [obj_or_objs] * G
+    if len(objs) != G:
+        raise ValueError("bop.gt_visibility: %d objects for %d poses" % (len(objs), G))
+    dt = _depth3(depth_test, dev)
+    _, H, W = dt.shape
+    ii = np.broadcast_to(np.asarray(img_idx, dtype=np.int32).reshape(-1), (G,))
+    uniq, first = [], {}
+    for o in objs:
+        if id(o) not in first:
+            first[id(o)] = len(uniq)
+            uniq.append(o)
+    counts = np.zeros((G, 3), dtype=np.int64)
+    bbox = np.full((G, 8), -1, dtype=np.int32)
+    mask = np.zeros((G, H, W), dtype=np.uint8) if masks else None
+    if G:
+        # several objects per call: their vertices one after another, each instance's triangles shifted to its object's
+        vbase = np.cumsum([0] + [o.verts.shape[0] for o in uniq])
+        verts = torch.cat([o.device(dev)[0] for o in uniq], 0)
+    for a in range(0, G, int(chunk)):
+        sel = range(a, min(G, a + int(chunk)))
+        tris = torch.cat([objs[g].device(dev)[1] + int(vbase[first[id(objs[g])]]) for g in sel], 0)
+        tri_off = ops._offsets([objs[g].faces.shape[0] for g in sel], dev)
+        poses = torch.from_numpy(P[a:a + len(sel)].reshape(-1, 12).astype(np.float32)).to(dev)
+        ren = render.render_depth(verts, tris, tri_off, poses, K, H, W, cull=True)
+        c, b, m = gt_visibility_counts(dt, ii[a:a + len(sel)].copy(), ren, K, delta, masks)
+        counts[a:a + len(sel)] = c.cpu().numpy()
+        bbox[a:a + len(sel)] = b.cpu().numpy()
+        if masks:
+            mask[a:a + len(sel)] = m.cpu().numpy()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fract = np.where(counts[:, 0] > 0, counts[:, 2].astype(np.float64) / np.maximum(counts[:, 0], 1).astype(np.float64), 0.0)
+    return dict(px_count_all=counts[:, 0].copy(), px_count_valid=counts[:, 1].copy(), px_count_visib=counts[:, 2].copy(),
+                visib_fract=fract, bbox_obj=bbox[:, :4].copy(), bbox_visib=bbox[:, 4:].copy(), mask_visib=mask)
 
 
 def _poses(R, t):

@@ -32,6 +32,15 @@ What the image cannot provide is stated, not faked:
     each is refined by --icp_iters, rendered, and the one whose render explains the most of the observed instance is
     reported.  Each result gains `verify`, and with --gt_pose `bop_first` (the errors of the selected pose: what H = 1
     reports).  --hypotheses=1 (default): off.
+  * `--data=bop --bop_root=<dir> --split=<name> [--targets=<json>] --out_csv=<file> [--model_scale=0.001]` runs the instance-level
+    path over a BOP-format dataset (cppf2_amd.bop_data; not in the reference): per target the instances' masks come from
+    mask_visib/ (computed by cppf_gt_visibility when the folder is missing: the "ground-truth masks" protocol), each is
+    back-projected and down-sampled as in the depth mode, instances of one object are batched across images through
+    run_ensemble (config/custom.yaml, --ckpt_shot / --ckpt_dino), --icp_iters / --hypotheses / --verify_tau apply per
+    instance against the object's model, and the reported poses go to a BOP results CSV (score: the verification score, else
+    the negated alignment loss; time: the image's share of its batches' wall time), which bop_data.score then scores.
+    `--teacher_prior` (this mode only) builds the logit prior and the scale from each instance's ground-truth pose, the same
+    stand-in the synthetic mode uses: trained checkpoints are absent from this tree, and without it untrained weights vote noise.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import json
@@ -515,9 +524,147 @@ def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, 
             else:
                 recs[b, h] = r["selected"][b]
                 recs["flags"][b, h] |= verify.EMPTY
-    img = np.broadcast_to(np.asarray(depth, dtype=np.float32), (B,) + np.shape(depth))
-    msk = np.broadcast_to(np.asarray(mask, dtype=bool), (B,) + np.shape(mask))
+    if np.ndim(depth) == 3:                        # one image and mask per instance (main_bop)
+        img, msk = np.asarray(depth, dtype=np.float32), np.asarray(mask, dtype=bool)
+    else:
+        img = np.broadcast_to(np.asarray(depth, dtype=np.float32), (B,) + np.shape(depth))
+        msk = np.broadcast_to(np.asarray(mask, dtype=bool), (B,) + np.shape(mask))
     return verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=icp_iters, tau=tau)
+
+
+def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1,
+             num_pairs=50000, num_rots=180, opt=True, geo_branch=True, visual_branch=True, seed=0, batch_instances=16,
+             icp_iters=0, hypotheses=1, verify_tau=None, teacher_prior=False, visib_gt_min=None, debug=False, out=None):
+    """The instance-level path over one split of a BOP-format dataset (cppf2_amd.bop_data.Dataset): one estimate per valid
+    ground-truth instance of every target, from its visible mask; poses written to `out_csv` in BOP's frame and scored with
+    bop_data.score.  Instances of one object (and one K and image size) are evaluated in batches of `batch_instances` across
+    images.  Returns the report (report["bop"] = bop_data.score's)."""
+    import time
+    from cppf2_amd import bop, bop_data, icp, verify
+    dev = ops._dev()
+    cfg, dino_model, shot_model = setup
+    up_sym = bool(cfg.get("up_sym", False))
+    vmin = bop_data.VISIB_GT_MIN if visib_gt_min is None else float(visib_gt_min)
+    ds = bop_data.Dataset(bop_root, split, mesh_scale)
+    tlist = ds.targets(targets, vmin)
+    verify_tau = verify.TAU if verify_tau is None else float(verify_tau)
+    icp_models, pending, rows, summary = {}, {}, [], []
+    im_time = {}
+    skipped = dict(too_few_points=0, too_large=0, no_pick=0)
+    gid = [0]
+
+    def flush(key):
+        chunk, pending[key] = pending.get(key, []), []
+        if not chunk:
+            return
+        t0 = time.perf_counter()
+        o = key[0]
+        obj = ds.object(o)
+        B = len(chunk)
+        descs = []
+        for c_ in chunk:                            # DINOv2 features are inputs to the path (weights absent): seeded unit vectors
+            gen = torch.Generator(device="cpu").manual_seed(seed * 7919 + c_["gid"] + 1)
+            descs.append(torch.nn.functional.normalize(torch.randn((c_["pc"].shape[0], 1024), generator=gen), dim=-1).numpy())
+        priors = scale_priors = None
+        if teacher_prior:
+            # the synthetic mode's stand-in (synth.make_scene): canonical coordinates (pc - t) @ R / diag from the true pose
+            ext = obj.verts.max(0) - obj.verts.min(0)
+            diag = float(np.linalg.norm(ext))
+            canon = [((c_["pc"].astype(np.float64) - c_["gt"]["t"]) @ c_["gt"]["R"] / diag).astype(np.float32) for c_ in chunk]
+            priors = _teacher_prior(np.concatenate(canon), dev)
+            scale_priors = np.stack([ext] * B)
+        r = run_ensemble(cfg, dino_model, shot_model, [c_["pc"] for c_ in chunk], descs, seed, [c_["gid"] for c_ in chunk],
+                         num_pairs, num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
+                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if hypotheses > 1 else None)
+        pt_off = np.cumsum([0] + [c_["pc"].shape[0] for c_ in chunk])
+        ver = icp_stats = None
+        if icp_iters > 0 and o not in icp_models:
+            icp_models[o] = icp.ModelPoints.from_mesh(ds.mesh(o))
+        if hypotheses > 1:
+            ver = _verify_instances(r, B, hypotheses, (geo_branch, visual_branch), obj, np.stack([c_["depth"] for c_ in chunk]),
+                                    np.stack([c_["mask"] for c_ in chunk]), chunk[0]["K"], pt_off, icp_models.get(o), icp_iters,
+                                    verify_tau)
+            if icp_iters > 0:
+                icp_stats = ver["icp"][np.arange(B), np.maximum(ver["chosen"], 0)]
+        elif icp_iters > 0:
+            icp_stats = icp.refine(icp_models[o], r["pts"], pt_off, r["selected"], iters=icp_iters)
+        dt = (time.perf_counter() - t0) / B
+        for b, c_ in enumerate(chunk):
+            im_time[(c_["scene_id"], c_["im_id"])] = im_time.get((c_["scene_id"], c_["im_id"]), 0.0) + dt + c_["prep_s"]
+            item = dict(scene_id=c_["scene_id"], im_id=c_["im_id"], obj_id=o, gt_index=c_["gt_index"], points=int(c_["pc"].shape[0]),
+                        model=None)
+            summary.append(item)
+            if r["pick"][b] < 0:
+                skipped["no_pick"] += 1
+                continue
+            rec = r["records"][r["pick"][b]][b] if icp_stats is None else r["selected"][b]
+            score = -float(r["best"][b])
+            if ver is not None:
+                rec = ver["records"][b]
+                k_ = int(ver["chosen"][b])
+                score = float(ver["scores"][b, k_]) if k_ >= 0 else 0.0
+                item["verify"] = dict(hypotheses=int(np.count_nonzero((ver["hypotheses"][b]["flags"] & verify.EMPTY) == 0)),
+                                      chosen=k_, score=score, score_first=float(ver["scores"][b, 0]))
+            if icp_stats is not None:
+                st = icp_stats[b]
+                item["icp"] = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
+            Rb, tb = bop.pose_to_bop(np.asarray(rec["R"], dtype=np.float64).reshape(3, 3), np.asarray(rec["t"], dtype=np.float64), mesh_scale,
+                                     obj.centre)
+            item.update(model=["dino", "shot"][r["pick"][b]], loss=float(r["best"][b]), score=score)
+            rows.append(dict(scene_id=c_["scene_id"], im_id=c_["im_id"], obj_id=o, score=score, R=Rb, t=tb))
+
+    for s_id, im, o, _ in tlist:
+        sc = ds.scene(s_id)
+        info = ds.gt_info(s_id)[im]
+        K = sc["camera"][im]["K"]
+        depth = None
+        for g, gt in enumerate(sc["gt"].get(im, [])):
+            if gt["obj_id"] != o or info[g]["visib_fract"] < vmin:
+                continue
+            t0 = time.perf_counter()
+            if depth is None:
+                depth = ds.depth(s_id, im)
+            m = ds.mask_visib(s_id, im, g)
+            pc, _ = ops.backproject(depth.astype(np.float64), K, m, return_device=True)    # as the depth mode does
+            inst_seed = (seed * 1000003 + gid[0]) & 0x7FFFFFFF
+            if pc.shape[0]:
+                pc = pc[ops.downsample(pc, cfg.res, inst_seed, return_device=True)]
+            pc = pc.cpu().numpy()
+            if pc.shape[0] > 50000:
+                pc = pc[np.random.RandomState(inst_seed).randint(pc.shape[0], size=50000)]
+            gid[0] += 1
+            if pc.shape[0] < cfg.num_more + 2:
+                skipped["too_few_points"] += 1
+                continue
+            if ((pc.max(0) - pc.min(0)).max() / cfg.res) > 1000:                           # eval.py:200
+                skipped["too_large"] += 1
+                continue
+            key = (o, K.tobytes(), depth.shape)
+            pending.setdefault(key, []).append(dict(scene_id=s_id, im_id=im, gt_index=g, gid=gid[0] - 1, pc=pc, gt=gt, depth=depth,
+                                                    mask=m, K=K, prep_s=time.perf_counter() - t0))
+            if len(pending[key]) >= int(batch_instances):
+                flush(key)
+    for key in list(pending):
+        flush(key)
+    res = bop_data.make_results([r_["scene_id"] for r_ in rows], [r_["im_id"] for r_ in rows], [r_["obj_id"] for r_ in rows],
+                                [r_["score"] for r_ in rows], np.asarray([r_["R"] for r_ in rows]).reshape(-1, 3, 3),
+                                np.asarray([r_["t"] for r_ in rows]).reshape(-1, 3),
+                                [im_time[(r_["scene_id"], r_["im_id"])] for r_ in rows])
+    bop_data.write_results(out_csv, res)
+    scored = bop_data.score(ds, bop_data.read_results(out_csv), tlist, vmin)              # the file, as a reader of it scores it
+    report = dict(data="bop", bop_root=str(bop_root), split=str(split), targets=len(tlist), instances=len(summary), rows=len(rows),
+                  skipped=skipped, out_csv=str(out_csv), teacher_prior=bool(teacher_prior),
+                  opt_refinement="100 Adam steps (cppf_refine_pose)" if opt else "off", bop=scored, results=summary)
+    if icp_iters > 0:
+        report["icp_refinement"] = "%d point-to-plane ICP iterations against each object's model (cppf_icp_refine)" % icp_iters
+    if hypotheses > 1:
+        report["verification"] = ("%d pose hypotheses per instance from %d peaks per vote, rendered and compared with the depth "
+                                  "at tau = %g m (cppf_pose_hypotheses, cppf_depth_fit_counts)" % (hypotheses, verify.PEAKS, verify_tau))
+    print(json.dumps(report if debug else {k_: v for k_, v in report.items() if k_ != "results"}))
+    if out:
+        with open(out, "w") as f:
+            json.dump(report, f)
+    return report
 
 
 def _teacher_prior(canon, dev):
@@ -536,8 +683,25 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          category=None, categories=None, seed=0, ckpt_dir=None, ckpt_shot=None, ckpt_dino=None, depth=None, mask=None,
          intrinsics=None, depth_scale=1000.0, out=None, out_pkl=None, log_dir=None, data_root="NOCS/real_test", out_dir=None,
          desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
-         models_info=None, hypotheses=1, verify_tau=None):
+         models_info=None, hypotheses=1, verify_tau=None, bop_root=None, split="test", targets=None, out_csv=None,
+         teacher_prior=False, model_scale=0.001):
     custom = False
+    if data == "bop":
+        # the BOP-dataset mode: its models come from the dataset, every other mode below runs as before
+        if not bop_root or not out_csv:
+            raise ValueError("--data=bop needs --bop_root (the dataset folder) and --out_csv (the results file to write)")
+        if int(hypotheses) < 1:
+            raise ValueError("--hypotheses must be >= 1, not %d" % int(hypotheses))
+        if gt_pose is not None or mesh:
+            raise ValueError("--data=bop takes the models and the true poses from the dataset: --mesh and --gt_pose belong to --data=depth")
+        dev = ops._dev()
+        torch.manual_seed(seed)
+        return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev), bop_root, split, out_csv, targets,
+                        float(model_scale), angle_tol, imp_wt_margin, backproj_ratio,
+                        num_pairs, num_rots, opt, geo_branch, visual_branch, seed, batch_instances, int(icp_iters), int(hypotheses),
+                        verify_tau, bool(teacher_prior), None, debug, out)
+    if teacher_prior:
+        raise ValueError("--teacher_prior builds the prior from a BOP dataset's ground-truth poses: it needs --data=bop")
     icp_iters = int(icp_iters)
     hypotheses = int(hypotheses)
     if hypotheses < 1:

@@ -392,6 +392,22 @@ int cppf_vsd_counts(int P, int I, int H, int W, const float* depth_test, const i
 int cppf_mssd_mspd(int P, const float* verts, int V, const double* syms, int S, const double* pose_est, const double* pose_gt,
                    const double* h_K, float* mssd, float* mspd, void* stream);
 
+/* ---- ground-truth visibility of BOP scenes: scene_gt_info's counts and boxes, mask_visib (the reference has no such step) ----
+ * cppf_gt_visibility: G ground-truth instances, renders float32[G,H,W] (each instance rendered alone, cppf_render_depth's
+ * output; 0 = nothing drawn), img_idx int32[G] (the test image of each instance), depth_test float32[I,H,W] (metres, 0 = no
+ * reading), h_K and delta as for cppf_vsd_counts.  Per pixel, with cppf_vsd_counts' float64 distance conversion and its vis_gt
+ * rule: all = d_gt > 0, valid = all && d_test > 0, visib = all && (dist_gt - dist_test <= delta || d_test == 0).
+ * counts int64[G,3] = (#all, #valid, #visib): BOP's px_count_all, px_count_valid, px_count_visib; visib_fract = #visib / #all
+ * is the caller's division.  bbox int32[G,8] = (x, y, w, h) of `all` (bbox_obj), then of `visib` (bbox_visib): min column, min
+ * row, extents; (-1, -1, -1, -1) for an empty set.  bbox_obj is the box of the part INSIDE the image: bop_toolkit takes it from
+ * a render on an enlarged canvas, so its box also covers what falls outside.  mask_visib uint8[G,H,W] = 255 where visib, else
+ * 0, or NULL (not written).  An instance whose img_idx lies outside [0, I) is not counted: counts 0, boxes -1, mask 0.
+ * G <= 65535, G = 0 launches nothing; H, W <= 8192; no workspace; one launch after the outputs are cleared on the stream.
+ * Integer atomics only: the outputs do not depend on the batch or the order.  The exact order of the operations is stated in
+ * cppf2_amd/csrc/cppf_bop.hip. */
+int cppf_gt_visibility(int G, int I, int H, int W, const float* depth_test, const int32_t* img_idx, const float* renders,
+                       const double* h_K, double delta, int64_t* counts, int32_t* bbox, uint8_t* mask_visib, void* stream);
+
 /* ---- instance-level hypothesis verification: render and compare (not in the reference) -------------------------------
  * Several peaks of each rotation-bin vote become pose hypotheses; each hypothesis' render (cppf_render_depth) is counted
  * against the observed depth, and cppf2_amd/verify.py keeps the one that explains most of it.  The exact order of the
