@@ -740,6 +740,28 @@ __global__ __launch_bounds__(256) void grid_argmax_partial_kernel(const uint32_t
   }
 }
 
+// Cell (ix, iy, iz) of a flat C-order index of a scene's grid, and the cell's world coordinates (train_dino.py:212-213): the
+// one definition grid_argmax_final_kernel and the grid_peaks kernels share, so that peak 0 of cppf_grid_peaks and the arg-max
+// of cppf_vote_center cannot drift apart.
+struct GridCell {
+  int64_t ix, iy, iz;
+};
+__device__ __forceinline__ GridCell grid_unravel(const CppfSceneGrid& g, int64_t i) {
+  const int64_t gyz = (int64_t)g.g[1] * g.g[2];
+  GridCell c;
+  c.ix = gyz > 0 ? i / gyz : 0;
+  const int64_t rem = gyz > 0 ? i - c.ix * gyz : 0;
+  c.iy = g.g[2] > 0 ? rem / g.g[2] : 0;
+  c.iz = g.g[2] > 0 ? rem - c.iy * g.g[2] : 0;
+  return c;
+}
+__device__ __forceinline__ void grid_cell_world(const CppfSceneGrid& g, int64_t i, double res, double* __restrict__ out) {
+  const GridCell c = grid_unravel(g, i);
+  out[0] = (double)g.c0[0] + (double)c.ix * res;
+  out[1] = (double)g.c0[1] + (double)c.iy * res;
+  out[2] = (double)g.c0[2] + (double)c.iz * res;
+}
+
 // stage 2: combine partials, unravel, world coordinates (train_dino.py:212-213)
 __global__ __launch_bounds__(64) void grid_argmax_final_kernel(const SlabBest* __restrict__ partial, int s_max,
                                                                int fixed_parts, const int* __restrict__ ctl,
@@ -765,15 +787,131 @@ __global__ __launch_bounds__(64) void grid_argmax_final_kernel(const SlabBest* _
     out_argmax[b] = bi;
     // a scene whose grid exceeds cells_cap received no votes: its peak is the sentinel 0xFFFFFFFF
     if (out_peak) out_peak[b] = ((int64_t)g.ncell > cells_cap) ? 0xFFFFFFFFu : bv;
-    if (out_world) {
-      const int64_t gyz = (int64_t)g.g[1] * g.g[2];
-      const int64_t ix = gyz > 0 ? bi / gyz : 0;
-      const int64_t rem = gyz > 0 ? bi - ix * gyz : 0;
-      const int64_t iy = g.g[2] > 0 ? rem / g.g[2] : 0;
-      const int64_t iz = g.g[2] > 0 ? rem - iy * g.g[2] : 0;
-      out_world[3 * b + 0] = (double)g.c0[0] + (double)ix * res;
-      out_world[3 * b + 1] = (double)g.c0[1] + (double)iy * res;
-      out_world[3 * b + 2] = (double)g.c0[2] + (double)iz * res;
+    if (out_world) grid_cell_world(g, bi, res, out_world + 3 * b);
+  }
+}
+
+// ---- separated peaks of the vote grid: greedy non-maximum suppression, exact, integer arithmetic only ---------------------
+// Per scene, on the uint32 grid cppf_vote_center wrote (G = ncell cells, C order; G = 0 for a scene above cells_cap):
+//   peak 0 = the first maximum of the grid (largest value, lowest flat index on ties; index 0 for an all-zero grid or G = 0):
+//            what grid_argmax_final_kernel reports;
+//   peak k = the first maximum over the cells with a value > 0 that no earlier peak suppresses; a cell (ix, iy, iz) is
+//            suppressed by a peak (px, py, pz) when (ix-px)^2 + (iy-py)^2 + (iz-pz)^2 <= sep_cells^2 (int64);
+//   no cell left: the scene has run out of peaks (n_peaks = peaks found, at least 1).
+// One masked first-maximum pass over the grid per peak (grid_peaks_pass_kernel, launched K times): pass k reads the k earlier
+// peaks' cells into LDS, each thread keeps the largest 64-bit key (value << 32 | 0xFFFFFFFF - index) of its unsuppressed cells
+// -- a larger key IS the first-maximum order, so the order of evaluation cannot matter --, the workgroup reduces its threads'
+// keys and merges with one 64-bit atomic max into keys[b, k] (zeroed before pass 0).  An integer max is associative and
+// commutative: the atomics cannot affect the result, and a scene's keys do not depend on the batch.  A cell is unravelled and
+// tested against the earlier peaks only when its key beats the thread's best so far.  Key 0 = no peak (every real key has a
+// value > 0).  grid_peaks_final_kernel turns the keys into the outputs.
+#define GP_MAX_K 16
+#define GP_THREADS 256
+
+__device__ __forceinline__ uint32_t grid_peak_index(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)key; }
+
+__global__ __launch_bounds__(GP_THREADS) void grid_peaks_pass_kernel(const uint32_t* __restrict__ grid,
+                                                                     const int64_t* __restrict__ grid_off, int64_t cells_cap,
+                                                                     const CppfSceneGrid* __restrict__ grids,
+                                                                     unsigned long long* __restrict__ keys, int K, int k,
+                                                                     long long sep2) {
+  const int b = blockIdx.y;
+  const CppfSceneGrid g = grids[b];
+  const int G = ((int64_t)g.ncell <= cells_cap) ? g.ncell : 0;
+  if (G <= 0) return;
+  unsigned long long* kb = keys + (int64_t)b * K;
+  __shared__ int s_p[GP_MAX_K * 3];
+  __shared__ int s_stop;
+  __shared__ unsigned long long s_w[GP_THREADS / 64];
+  if (threadIdx.x == 0) s_stop = 0;
+  __syncthreads();
+  if ((int)threadIdx.x < k) {                     // the earlier passes' keys are final: they were written by earlier launches
+    const unsigned long long pk = kb[threadIdx.x];
+    if (pk == 0ull) {
+      s_stop = 1;                                 // the scene ran out of peaks before this pass
+    } else {
+      const GridCell c = grid_unravel(g, (int64_t)grid_peak_index(pk));
+      s_p[3 * threadIdx.x + 0] = (int)c.ix;
+      s_p[3 * threadIdx.x + 1] = (int)c.iy;
+      s_p[3 * threadIdx.x + 2] = (int)c.iz;
+    }
+  }
+  __syncthreads();
+  if (s_stop) return;
+  const uint32_t* gb = grid + (grid_off ? grid_off[b] : (int64_t)b * cells_cap);
+  const uint32_t gz = (uint32_t)g.g[2], gyz = (uint32_t)g.g[1] * (uint32_t)g.g[2];
+  unsigned long long best = 0ull;
+  auto consider = [&](uint32_t v, int i) {
+    const unsigned long long key = ((unsigned long long)v << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+    if (v == 0u || key <= best) return;
+    if (k > 0) {
+      const uint32_t ix = (uint32_t)i / gyz, rem = (uint32_t)i - ix * gyz, iy = rem / gz, iz = rem - iy * gz;
+      for (int j = 0; j < k; ++j) {               // k is uniform: LDS broadcast reads
+        const long long dx = (long long)ix - s_p[3 * j], dy = (long long)iy - s_p[3 * j + 1], dz = (long long)iz - s_p[3 * j + 2];
+        if (dx * dx + dy * dy + dz * dz <= sep2) return;
+      }
+    }
+    best = key;
+  };
+  // 16-byte loads over the aligned body of the scene's range; the (< 4)-cell head and tail go to workgroup 0
+  const int head = min(G, (int)((0u - (uint32_t)((uintptr_t)gb >> 2)) & 3u));
+  const int nvec = (G - head) >> 2;
+  const uint4* gv = (const uint4*)(gb + head);
+  for (int v = blockIdx.x * GP_THREADS + threadIdx.x; v < nvec; v += gridDim.x * GP_THREADS) {
+    const uint4 q = gv[v];
+    const int i0 = head + 4 * v;
+    consider(q.x, i0);
+    consider(q.y, i0 + 1);
+    consider(q.z, i0 + 2);
+    consider(q.w, i0 + 3);
+  }
+  if (blockIdx.x == 0 && threadIdx.x < 4) {
+    if ((int)threadIdx.x < head) consider(gb[threadIdx.x], (int)threadIdx.x);
+    const int t = head + 4 * nvec + (int)threadIdx.x;
+    if (t < G) consider(gb[t], t);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(best, off);
+    best = o > best ? o : best;
+  }
+  if (wave_lane() == 0) s_w[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < GP_THREADS / 64; ++w) best = s_w[w] > best ? s_w[w] : best;
+    if (best != 0ull) atomicMax(&kb[k], best);
+  }
+}
+
+// keys -> peak_idx int64[B,K], peak_val uint32[B,K], peak_world float64[B,K,3], n_peaks int32[B]; one wavefront per scene
+__global__ __launch_bounds__(64) void grid_peaks_final_kernel(const unsigned long long* __restrict__ keys, int K,
+                                                              const CppfSceneGrid* __restrict__ grids, int64_t cells_cap,
+                                                              double res, int64_t* __restrict__ peak_idx,
+                                                              uint32_t* __restrict__ peak_val, double* __restrict__ peak_world,
+                                                              int32_t* __restrict__ n_peaks) {
+  const int b = blockIdx.x, t = threadIdx.x;
+  const CppfSceneGrid g = grids[b];
+  const bool over = (int64_t)g.ncell > cells_cap;
+  const unsigned long long key = (t < K && !over && g.ncell > 0) ? keys[(int64_t)b * K + t] : 0ull;
+  const int found = __popcll(wave_ballot(key != 0ull));       // the non-zero keys are the leading ones (a pass stops at a gap)
+  if (t == 0 && n_peaks) n_peaks[b] = max(found, 1);
+  if (t >= K) return;
+  const int64_t o = (int64_t)b * K + t;
+  if (t == 0 || key != 0ull) {
+    // peak 0 always exists: index 0 / value 0 for an all-zero grid; a scene above cells_cap received no votes and carries
+    // cppf_vote_center's sentinel
+    const int64_t i = key != 0ull ? (int64_t)grid_peak_index(key) : 0;
+    peak_idx[o] = i;
+    if (peak_val) peak_val[o] = over ? 0xFFFFFFFFu : (uint32_t)(key >> 32);
+    if (peak_world) grid_cell_world(g, i, res, peak_world + 3 * o);
+  } else {
+    peak_idx[o] = -1;
+    if (peak_val) peak_val[o] = 0u;
+    if (peak_world) {
+      const double nan = __longlong_as_double(0x7ff8000000000000ll);
+      peak_world[3 * o + 0] = nan;
+      peak_world[3 * o + 1] = nan;
+      peak_world[3 * o + 2] = nan;
     }
   }
 }
@@ -934,6 +1072,35 @@ extern "C" int cppf_vote_center(int B, const float* pts, const int32_t* pt_off, 
                        best, p.s_max_parts);
   hipLaunchKernelGGL(grid_argmax_final_kernel, dim3(B), dim3(64), 0, st, best, p.s_max_parts, merge ? VC_ARG_BLOCKS : 0,
                      p.path == VC_PERSIST ? ctl : nullptr, grids, cells_cap, res, out_argmax, out_peak, out_world);
+  CPPF_LAUNCH_CHECK();
+  return CPPF_OK;
+}
+
+// workspace of cppf_grid_peaks: the 64-bit keys, one per (scene, peak)
+extern "C" int64_t cppf_grid_peaks_workspace_bytes(int B, int K) {
+  if (B <= 0 || K < 1 || K > GP_MAX_K) return 0;
+  return align_up((int64_t)B * K * 8, 256);
+}
+
+extern "C" int cppf_grid_peaks(int B, const CppfSceneGrid* grids, const uint32_t* grid, const int64_t* grid_off,
+                               int64_t cells_cap, double res, int K, int sep_cells, int64_t* peak_idx, uint32_t* peak_val,
+                               double* peak_world, int32_t* n_peaks, void* workspace, int64_t workspace_bytes, void* stream) {
+  CPPF_CHECK_ARG(B > 0 && B <= 0xffff && grids && grid && peak_idx);
+  CPPF_CHECK_ARG(K >= 1 && K <= GP_MAX_K && sep_cells >= 0 && res > 0.0 && cells_cap > 0 && cells_cap <= 0x7fffffffLL);
+  const int64_t need = cppf_grid_peaks_workspace_bytes(B, K);
+  CPPF_CHECK_ARG(workspace && workspace_bytes >= need);
+  hipStream_t st = (hipStream_t)stream;
+  unsigned long long* keys = (unsigned long long*)workspace;
+  CPPF_HIP(hipMemsetAsync(keys, 0, (size_t)B * K * 8, st));
+  // 16 cells per thread and round of the grid-stride loop; at most ~8192 workgroups per pass
+  int nbx = (int)std::min<int64_t>(std::max<int64_t>((cells_cap + GP_THREADS * 16 - 1) / (GP_THREADS * 16), 1), 256);
+  if ((int64_t)nbx * B > 8192) nbx = std::max(1, 8192 / B);
+  const long long sep2 = (long long)sep_cells * sep_cells;
+  for (int k = 0; k < K; ++k)
+    hipLaunchKernelGGL(grid_peaks_pass_kernel, dim3(nbx, B), dim3(GP_THREADS), 0, st, grid, grid_off, cells_cap, grids, keys, K, k,
+                       sep2);
+  hipLaunchKernelGGL(grid_peaks_final_kernel, dim3(B), dim3(64), 0, st, keys, K, grids, cells_cap, res, peak_idx, peak_val,
+                     peak_world, n_peaks);
   CPPF_LAUNCH_CHECK();
   return CPPF_OK;
 }

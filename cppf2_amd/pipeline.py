@@ -23,6 +23,12 @@ RESULT_DTYPE = np.dtype([("argmax", "<i8"), ("t", "<f8", (3,)), ("R", "<f8", (3,
                          ("up_count", "<f4"), ("right_count", "<f4"), ("flags", "<i4"), ("ncell", "<i4"), ("pad_", "<i4", (3,))])
 assert RESULT_DTYPE.itemsize == C.sizeof(SceneResult) == 160
 
+# Suppression radius between centre-vote peaks, metres (vote(centre_peaks=C)).  The back-vote's own agreement distance is no
+# fixed length (a percentile of the batch's errors), so this is verify.TAU: centres closer than the depth tolerance of the
+# verification are the same hypothesis to it.  10 cells at res = 2e-3.  DESIGN.md section 17.
+CENTRE_SEP = 0.02
+MAX_CENTRE_PEAKS = 16
+
 
 class VotingPipeline:
     """Decode -> centre vote -> back-vote filter -> rotation votes -> pose, for a fixed batch geometry.
@@ -154,6 +160,37 @@ class VotingPipeline:
                                        self.ws_vote_bytes, ops._p(self.argmax), ops._p(self.peak), ops._p(self.world),
                                        st), "cppf_vote_center")
 
+    def grid_peaks(self, grid, grid_off, K, sep_cells):
+        """cppf_grid_peaks on the grids vote_center() wrote into grid / grid_off (self.grids holds their geometry): up to K
+        peaks per scene, no two within sep_cells cells of each other.  Returns device tensors (peak_idx int64 [B,K], peak_val
+        int32 [B,K] holding the uint32 bits like self.peak, peak_world float64 [B,K,3], n_peaks int32 [B]); slots past a
+        scene's last peak carry -1 / 0 / NaN."""
+        K = int(K)
+        if not 1 <= K <= MAX_CENTRE_PEAKS:
+            raise _lib.CppfError("grid_peaks: K must be in [1, %d], not %d" % (MAX_CENTRE_PEAKS, K))
+        if int(sep_cells) < 0:
+            raise _lib.CppfError("grid_peaks: sep_cells must be >= 0, not %d" % int(sep_cells))
+        d, B = self.dev, self.B
+        out = (torch.empty((B, K), dtype=torch.int64, device=d), torch.empty((B, K), dtype=torch.int32, device=d),
+               torch.empty((B, K, 3), dtype=torch.float64, device=d), torch.empty((B,), dtype=torch.int32, device=d))
+        need = _L.cppf_grid_peaks_workspace_bytes(B, K)
+        if getattr(self, "_ws_peaks", None) is None or self._ws_peaks.numel() < need:
+            self._ws_peaks = torch.empty((need,), dtype=torch.uint8, device=d)
+        _lib.check(_L.cppf_grid_peaks(B, ops._p(self.grids), ops._p(grid), ops._p(grid_off), self.cells_cap,
+                                      C.c_double(self.res), K, int(sep_cells), ops._p(out[0]), ops._p(out[1]), ops._p(out[2]),
+                                      ops._p(out[3]), ops._p(self._ws_peaks), need, ops._stream()), "cppf_grid_peaks")
+        return out
+
+    def sep_cells(self, sep=None):
+        """The suppression radius in cells of a distance in metres (default CENTRE_SEP), at this pipeline's res."""
+        return int(round((CENTRE_SEP if sep is None else float(sep)) / self.res))
+
+    def set_centre(self, argmax, peak, world):
+        """Replaces the voted centre the later stages read (backvote: world; assemble: argmax, peak, world) by device copies."""
+        self.argmax.copy_(argmax)
+        self.peak.copy_(peak)
+        self.world.copy_(world)
+
     def backvote(self, pts, idx):
         _lib.check(_L.cppf_backvote_filter(self.B, ops._p(pts), ops._p(self.pt_off), ops._p(idx), self.k,
                                            ops._p(self.tup_off), ops._p(self.tr), ops._p(self.world), self.axes,
@@ -262,20 +299,62 @@ class VotingPipeline:
                                        ops._p(self.kept_count), int(bool(y_only)), int(steps), C.c_float(lr),
                                        ops._p(self.results), ops._stream()), "cppf_refine_pose")
 
-    def vote(self, pts, idx, logits, uniforms, pred_scales=None, grid=None, grid_off=None):
+    def vote(self, pts, idx, logits, uniforms, pred_scales=None, grid=None, grid_off=None, centre_peaks=1, sep=None):
         """Everything after the MLP: eval.py:225-313.  All arguments are device tensors in the batch layout.
         Returns the device tensor of B result records (uint8 [B,160]); use results_to_numpy() to read them.
         logits=None: the bins are already in self.bins (drawn by the MLP's output layer, ops.reslayer_split_decode).
         pred_scales: float32 [T, 3], or a callable evaluated after the back-vote filter that returns it -- the scale head is read
-        only for the kept pairs (eval.py:272), so a caller can run it on just those rows (kept_rows32 / kept_count / max_kept)."""
+        only for the kept pairs (eval.py:272), so a caller can run it on just those rows (kept_rows32 / kept_count / max_kept).
+        centre_peaks = C > 1 (not in the reference): the centre vote is written to a grid (the caller's, or one the pipeline
+        allocates once), C peaks at least `sep` metres apart (default CENTRE_SEP) are taken from it (grid_peaks), and
+        backvote -> rot_bins -> assemble run once per peak with that peak as the voted centre -- peaks C-1 .. 1 first, peak 0
+        (the first maximum) last, so that every buffer ends as the default call leaves it.  self.centre_results uint8
+        [C,B,160] and self.centre_counts float32 [C,2,B,S] keep each peak's records and rotation-vote counts
+        (centre_results[0] = results); a scene with fewer than c+1 peaks runs peak c's stages on its peak 0 and its record is
+        marked empty (flags bit0).  self.centre_idx / centre_val / centre_world / centre_n are grid_peaks' outputs.  No host
+        synchronisation.  C = 1 (default): the reference's path, no grid, no extra launch.
+        Cost of C > 1: the grid the pipeline allocates is B x cells_cap x 4 bytes (8 MB per scene at the default cells_cap, 512 MB
+        at B = 64; a twin() has its own) and is kept for the pipeline's life; each call also allocates small temporaries (the
+        peak arrays, the copies of the first maximum), so a C > 1 call cannot run under capture()."""
+        C_ = int(centre_peaks)
+        if not 1 <= C_ <= MAX_CENTRE_PEAKS:
+            raise _lib.CppfError("vote: centre_peaks must be in [1, %d], not %d" % (MAX_CENTRE_PEAKS, C_))
         if logits is None:
             self.decode_from_bins(pts, idx)
         else:
             self.decode(pts, idx, logits, uniforms)
+        scales = (lambda: pred_scales() if callable(pred_scales) else pred_scales)
+        if C_ == 1:
+            self.vote_center(pts, idx, grid, grid_off)
+            self.backvote(pts, idx)
+            self.rot_bins(pts, idx)
+            self.assemble(scales())
+            return self.results
+        if grid is None:
+            if getattr(self, "_cp_grid", None) is None:
+                self._cp_grid = torch.empty((self.B * self.cells_cap,), dtype=torch.int32, device=self.dev)
+                self._cp_grid_off = torch.arange(self.B, dtype=torch.int64, device=self.dev) * self.cells_cap
+            grid, grid_off = self._cp_grid, self._cp_grid_off
+        if getattr(self, "centre_results", None) is None or self.centre_results.shape[0] != C_:
+            self.centre_results = torch.empty((C_, self.B, 160), dtype=torch.uint8, device=self.dev)
+            self.centre_counts = torch.empty((C_, 2, self.B, self.S), dtype=torch.float32, device=self.dev)
         self.vote_center(pts, idx, grid, grid_off)
-        self.backvote(pts, idx)
-        self.rot_bins(pts, idx)
-        self.assemble(pred_scales() if callable(pred_scales) else pred_scales)
+        first = (self.argmax.clone(), self.peak.clone(), self.world.clone())
+        self.centre_idx, self.centre_val, self.centre_world, self.centre_n = self.grid_peaks(grid, grid_off, C_, self.sep_cells(sep))
+        for c in range(C_ - 1, -1, -1):
+            if c:
+                has = self.centre_n > c                                    # scenes without a peak c fall back to their peak 0
+                self.set_centre(torch.where(has, self.centre_idx[:, c], first[0]), torch.where(has, self.centre_val[:, c], first[1]),
+                                torch.where(has[:, None], self.centre_world[:, c], first[2]))
+            else:
+                self.set_centre(*first)
+            self.backvote(pts, idx)
+            self.rot_bins(pts, idx)
+            self.assemble(scales())
+            self.centre_results[c].copy_(self.results)
+            self.centre_counts[c].copy_(self.counts)
+            if c:
+                self.centre_results[c][:, 140:144].view(torch.int32).bitwise_or_((~has).to(torch.int32)[:, None])
         return self.results
 
     def capture(self, pts, idx, logits, uniforms, pred_scales=None):

@@ -32,6 +32,11 @@ What the image cannot provide is stated, not faked:
     each is refined by --icp_iters, rendered, and the one whose render explains the most of the observed instance is
     reported.  Each result gains `verify`, and with --gt_pose `bop_first` (the errors of the selected pose: what H = 1
     reports).  --hypotheses=1 (default): off.
+  * `--hypotheses=H --centre_peaks=C` (C > 1; --data=depth and --data=bop) also verifies translation hypotheses: each pass takes C
+    peaks of its centre-vote grid at least 2 cm apart (cppf_grid_peaks) and runs the back-vote filter, both rotation votes and the
+    pose assembly again for every peak (VotingPipeline.vote(centre_peaks=C)); the hypotheses of the further peaks follow those of
+    the first maximum in the list (_instance_hypotheses), and `verify` gains `centre_peak`, the peak the chosen hypothesis came
+    from.  --centre_peaks=1 (default): off.
   * `--data=bop --bop_root=<dir> --split=<name> [--targets=<json>] --out_csv=<file> [--model_scale=0.001]` runs the instance-level
     path over a BOP-format dataset (cppf2_amd.bop_data; not in the reference): per target the instances' masks come from
     mask_visib/ (computed by cppf_gt_visibility when the folder is missing: the "ground-truth masks" protocol), each is
@@ -164,7 +169,7 @@ def _pipelines(dev, Ns, num_pairs, k, cfg, num_rots, angle_tol, backproj_ratio, 
 @torch.no_grad()
 def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_pairs, num_rots, angle_tol=1.,
                  imp_wt_margin=0.01, backproj_ratio=.1, opt=False, geo_branch=True, visual_branch=True, up_sym=False,
-                 priors=None, keep=False, scale_priors=None, two_streams=True, hypotheses=None):
+                 priors=None, keep=False, scale_priors=None, two_streams=True, hypotheses=None, centre_peaks=1):
     """eval.py:207-372 for a batch of instances of one category.  pcs: list of float32 [N_b,3]; descs: list of float32
     [N_b,1024] arrays or (device) tensors (DINOv2 features at the points: inputs to the path); priors: optional callable(idx_global, base) -> logit
     prior [T,6,nb] added to both models' logits; scale_priors: optional float32 [B,3] teacher box extents that stand in for
@@ -176,7 +181,11 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
     (eval.py:308-310).  Same records as the one-stream order (keep=True, which hands out intermediates, uses that order).
     hypotheses: None (default) or H >= 1: each pass also forms H pose hypotheses from the peaks of its two votes
     (verify.hypotheses, right after its vote and before `opt`; slot 0 is the pass' assembled record), returned as
-    out["hypotheses"] = [2 x RESULT_DTYPE [B,H]] (model 0, model 1)."""
+    out["hypotheses"] = [2 x RESULT_DTYPE [B,H]] (model 0, model 1).
+    centre_peaks: C >= 1 (needs hypotheses): each pass votes with VotingPipeline.vote(centre_peaks=C) and forms H hypotheses per
+    centre-vote peak from that peak's counts and record; out["centre_hypotheses"] = [2 x RESULT_DTYPE [C,B,H]], whose [m][0] is
+    out["hypotheses"][m] (the first maximum: what C = 1 gives), and out["centre_n"] = [2 x int32 [B]] the peaks each scene had.
+    Records, losses and the selection are those of C = 1."""
     dev = ops._dev()
     B = len(pcs)
     Ns = [int(p.shape[0]) for p in pcs]
@@ -216,6 +225,12 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
         hypotheses = int(hypotheses)
         if hypotheses < 1:
             raise ValueError("hypotheses must be >= 1, not %d" % hypotheses)
+    centre_peaks = int(centre_peaks)
+    if centre_peaks < 1:
+        raise ValueError("centre_peaks must be >= 1, not %d" % centre_peaks)
+    if centre_peaks > 1 and hypotheses is None:
+        raise ValueError("centre_peaks > 1 forms hypotheses per centre-vote peak: it needs hypotheses")
+    centre_hyps, centre_n = [None, None], [None, None]
     dino_scored = torch.cuda.Event() if two else None
 
     def one_pass(model_idx):
@@ -250,11 +265,20 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
                                                            scatter=(pp.kept_count, pp.max_kept, scales_buf))
             return (scale_prior + 1e-3 * s_).contiguous() if scale_prior is not None else s_.contiguous()
         pred_scales = scales() if keep else scales
-        pp.vote(pts, idx, None if pred_cls is None else pred_cls.contiguous(), u, pred_scales)
+        if centre_peaks > 1:
+            pp.vote(pts, idx, None if pred_cls is None else pred_cls.contiguous(), u, pred_scales, centre_peaks=centre_peaks)
+        else:
+            pp.vote(pts, idx, None if pred_cls is None else pred_cls.contiguous(), u, pred_scales)
         if hypotheses is not None:
             # here, on this pass' stream: the one-stream order reuses pp.counts for the next pass, and `opt` rewrites the records
             hyps[model_idx] = verify.hypotheses(pp.counts[0], pp.counts[1], pp.sphere, pp.results, hypotheses, pp.up_axis,
                                                 pp.right_axis, y_only=up_sym)
+            if centre_peaks > 1:
+                # the further peaks' hypotheses from their own counts and records (peak 0's are the ones above)
+                centre_hyps[model_idx] = [hyps[model_idx]] + [
+                    verify.hypotheses(pp.centre_counts[c, 0], pp.centre_counts[c, 1], pp.sphere, pp.centre_results[c], hypotheses,
+                                      pp.up_axis, pp.right_axis, y_only=up_sym) for c in range(1, centre_peaks)]
+                centre_n[model_idx] = pp.centre_n
         if opt:
             pp.refine(pts, idx, up_sym)                                                    # eval.py:319-355
         if two and model_idx == 0:
@@ -295,6 +319,10 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
                scale_norm=scale_norm.astype(np.float64), idx=idx, pipe=pipe, pts=pts)
     if hypotheses is not None:
         out["hypotheses"] = [pipe.results_to_numpy(h_.reshape(-1, 160)).reshape(B, hypotheses) for h_ in hyps]
+    if centre_peaks > 1:
+        out["centre_hypotheses"] = [np.stack([pipe.results_to_numpy(h_.reshape(-1, 160)).reshape(B, hypotheses) for h_ in ch])
+                                    for ch in centre_hyps]
+        out["centre_n"] = [n_.cpu().numpy() for n_ in centre_n]
     if keep:
         out["kept"] = kept
         out["shot_feat"], out["normal"] = extra["shot_feat"].cpu().numpy(), extra["normal"].cpu().numpy()
@@ -502,39 +530,77 @@ def main_nocs(setups, log_dir, data_root="NOCS/real_test", out_dir=None, desc_np
 
 
 
+def _instance_hypotheses(selected, pick, hyps, enabled, H):
+    """The hypothesis list of one instance (pure host code).  selected: its selected record (after `opt`: what H = 1 reports);
+    pick: the picked pass (-1: none); hyps[m][c]: pass m's hypothesis records of centre-vote peak c (RESULT_DTYPE [H'], slot 0 =
+    the pass' record for that centre; hyps[m] may be None for a pass that formed none); enabled[m]: pass m takes part.
+    Order.  Centre peak 0 (the first maximum of the vote grid), exactly the list without further centre peaks: the selected
+    record, the other peak combinations of the picked pass, then those of the other pass if it is enabled; empty records
+    (flags bit0) dropped.  Then the further centre peaks, round-robin: the first hypothesis of peak 1, of peak 2, ..., then
+    their second ones, and so on, each peak's own list being the picked pass' combinations followed by the other enabled pass'.
+    When H cuts the list, peak 0's part is cut first to min(its length, H - the number of further peaks that have a hypothesis)
+    (at least 1), so that a small H still sees every centre once; with one centre peak that is the plain cut at H.
+    Returns (records RESULT_DTYPE [H], centre int64 [H]): slots past the end of the list carry the selected record with flags
+    bit0 and centre -1."""
+    from cppf2_amd import verify
+    from cppf2_amd.pipeline import RESULT_DTYPE
+    recs = np.zeros((H,), dtype=RESULT_DTYPE)
+    centre = np.full((H,), -1, dtype=np.int64)
+    lst = []
+    p_ = int(pick)
+    if p_ >= 0:
+        order = [p_] + ([1 - p_] if enabled[1 - p_] and hyps[1 - p_] is not None else [])
+        n_c = len(hyps[p_])
+
+        def of_peak(c):
+            out = []
+            for m in order:
+                out += list(hyps[m][c][1:] if (m == p_ and c == 0) else hyps[m][c])
+            return [h_ for h_ in out if not h_["flags"] & verify.EMPTY]
+        first = [selected] + of_peak(0)
+        first = [h_ for h_ in first if not h_["flags"] & verify.EMPTY]
+        others = [of_peak(c) for c in range(1, n_c)]
+        live = sum(1 for o_ in others if o_)
+        lst = [(h_, 0) for h_ in first[:max(1, H - live)]]
+        for j in range(max([len(o_) for o_ in others], default=0)):
+            lst += [(o_[j], c + 1) for c, o_ in enumerate(others) if j < len(o_)]
+        lst = lst[:H]
+    for h in range(H):
+        if h < len(lst):
+            recs[h], centre[h] = lst[h]
+        else:
+            recs[h] = selected
+            recs["flags"][h] |= verify.EMPTY
+    return recs, centre
+
+
 def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, icp_iters, tau):
-    """The hypotheses of each instance, in order: its selected record (after `opt`: what H = 1 reports), the other peak
-    combinations of the picked pass, then those of the other pass if it is enabled; cut at H (empty slots past the end).  An
-    instance without a pick gets only empty slots.  Then verify.select (ICP first when icp_iters > 0) on the instance's image."""
+    """The hypotheses of each instance in _instance_hypotheses' order, cut at H (empty slots past the end; an instance without a
+    pick gets only empty slots), then verify.select (ICP first when icp_iters > 0) on the instance's image.  The result also
+    carries centre int64 [B,H] (the centre-vote peak of each hypothesis, -1 for empty slots) and centre_peak int64 [B] (that of
+    the chosen one)."""
     from cppf2_amd import verify
     from cppf2_amd.pipeline import RESULT_DTYPE
     recs = np.zeros((B, H), dtype=RESULT_DTYPE)
+    centre = np.full((B, H), -1, dtype=np.int64)
+    per_pass = r.get("centre_hypotheses") or [h_[None] for h_ in r["hypotheses"]]
     for b in range(B):
-        p_ = int(r["pick"][b])
-        if p_ < 0:
-            lst = []
-        else:
-            lst = [r["selected"][b]] + list(r["hypotheses"][p_][b][1:])
-            if enabled[1 - p_]:
-                lst += list(r["hypotheses"][1 - p_][b])
-            lst = [h_ for h_ in lst if not h_["flags"] & verify.EMPTY][:H]
-        for h in range(H):
-            if h < len(lst):
-                recs[b, h] = lst[h]
-            else:
-                recs[b, h] = r["selected"][b]
-                recs["flags"][b, h] |= verify.EMPTY
+        recs[b], centre[b] = _instance_hypotheses(r["selected"][b], r["pick"][b], [pp_[:, b] for pp_ in per_pass], enabled, H)
     if np.ndim(depth) == 3:                        # one image and mask per instance (main_bop)
         img, msk = np.asarray(depth, dtype=np.float32), np.asarray(mask, dtype=bool)
     else:
         img = np.broadcast_to(np.asarray(depth, dtype=np.float32), (B,) + np.shape(depth))
         msk = np.broadcast_to(np.asarray(mask, dtype=bool), (B,) + np.shape(mask))
-    return verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=icp_iters, tau=tau)
+    out = verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=icp_iters, tau=tau)
+    out["centre"] = centre
+    out["centre_peak"] = centre[np.arange(B), np.maximum(out["chosen"], 0)]
+    return out
 
 
 def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1,
              num_pairs=50000, num_rots=180, opt=True, geo_branch=True, visual_branch=True, seed=0, batch_instances=16,
-             icp_iters=0, hypotheses=1, verify_tau=None, teacher_prior=False, visib_gt_min=None, debug=False, out=None):
+             icp_iters=0, hypotheses=1, verify_tau=None, teacher_prior=False, visib_gt_min=None, debug=False, out=None,
+             centre_peaks=1):
     """The instance-level path over one split of a BOP-format dataset (cppf2_amd.bop_data.Dataset): one estimate per valid
     ground-truth instance of every target, from its visible mask; poses written to `out_csv` in BOP's frame and scored with
     bop_data.score.  Instances of one object (and one K and image size) are evaluated in batches of `batch_instances` across
@@ -575,7 +641,8 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
             scale_priors = np.stack([ext] * B)
         r = run_ensemble(cfg, dino_model, shot_model, [c_["pc"] for c_ in chunk], descs, seed, [c_["gid"] for c_ in chunk],
                          num_pairs, num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
-                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if hypotheses > 1 else None)
+                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if hypotheses > 1 else None,
+                         centre_peaks=centre_peaks)
         pt_off = np.cumsum([0] + [c_["pc"].shape[0] for c_ in chunk])
         ver = icp_stats = None
         if icp_iters > 0 and o not in icp_models:
@@ -605,6 +672,8 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
                 score = float(ver["scores"][b, k_]) if k_ >= 0 else 0.0
                 item["verify"] = dict(hypotheses=int(np.count_nonzero((ver["hypotheses"][b]["flags"] & verify.EMPTY) == 0)),
                                       chosen=k_, score=score, score_first=float(ver["scores"][b, 0]))
+                if centre_peaks > 1:
+                    item["verify"]["centre_peak"] = int(ver["centre_peak"][b])
             if icp_stats is not None:
                 st = icp_stats[b]
                 item["icp"] = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
@@ -660,11 +729,25 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
     if hypotheses > 1:
         report["verification"] = ("%d pose hypotheses per instance from %d peaks per vote, rendered and compared with the depth "
                                   "at tau = %g m (cppf_pose_hypotheses, cppf_depth_fit_counts)" % (hypotheses, verify.PEAKS, verify_tau))
+        if centre_peaks > 1:
+            report["verification"] += _CENTRE_NOTE % centre_peaks
     print(json.dumps(report if debug else {k_: v for k_, v in report.items() if k_ != "results"}))
     if out:
         with open(out, "w") as f:
             json.dump(report, f)
     return report
+
+
+_CENTRE_NOTE = "; translation hypotheses from %d separated peaks of each centre vote (cppf_grid_peaks)"
+
+
+def _centre_peaks_flag(centre_peaks, hypotheses):
+    centre_peaks = int(centre_peaks)
+    if centre_peaks < 1:
+        raise ValueError("--centre_peaks must be >= 1, not %d" % centre_peaks)
+    if centre_peaks > 1 and int(hypotheses) <= 1:
+        raise ValueError("--centre_peaks > 1 verifies translation hypotheses among the pose hypotheses: it needs --hypotheses > 1")
+    return centre_peaks
 
 
 def _teacher_prior(canon, dev):
@@ -684,7 +767,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          intrinsics=None, depth_scale=1000.0, out=None, out_pkl=None, log_dir=None, data_root="NOCS/real_test", out_dir=None,
          desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
          models_info=None, hypotheses=1, verify_tau=None, bop_root=None, split="test", targets=None, out_csv=None,
-         teacher_prior=False, model_scale=0.001):
+         teacher_prior=False, model_scale=0.001, centre_peaks=1):
     custom = False
     if data == "bop":
         # the BOP-dataset mode: its models come from the dataset, every other mode below runs as before
@@ -692,6 +775,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
             raise ValueError("--data=bop needs --bop_root (the dataset folder) and --out_csv (the results file to write)")
         if int(hypotheses) < 1:
             raise ValueError("--hypotheses must be >= 1, not %d" % int(hypotheses))
+        centre_peaks = _centre_peaks_flag(centre_peaks, hypotheses)
         if gt_pose is not None or mesh:
             raise ValueError("--data=bop takes the models and the true poses from the dataset: --mesh and --gt_pose belong to --data=depth")
         dev = ops._dev()
@@ -699,7 +783,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev), bop_root, split, out_csv, targets,
                         float(model_scale), angle_tol, imp_wt_margin, backproj_ratio,
                         num_pairs, num_rots, opt, geo_branch, visual_branch, seed, batch_instances, int(icp_iters), int(hypotheses),
-                        verify_tau, bool(teacher_prior), None, debug, out)
+                        verify_tau, bool(teacher_prior), None, debug, out, centre_peaks)
     if teacher_prior:
         raise ValueError("--teacher_prior builds the prior from a BOP dataset's ground-truth poses: it needs --data=bop")
     icp_iters = int(icp_iters)
@@ -708,6 +792,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         raise ValueError("--hypotheses must be >= 1, not %d" % hypotheses)
     if hypotheses > 1 and (data != "depth" or not mesh):
         raise ValueError("--hypotheses > 1 verifies poses against the object's mesh: it needs --data=depth and --mesh")
+    centre_peaks = _centre_peaks_flag(centre_peaks, hypotheses)
     if icp_iters > 0 and (data != "depth" or not mesh):
         raise ValueError("--icp_iters > 0 refines against the object's mesh: it needs --data=depth and --mesh")
     if gt_pose is not None and (data != "depth" or not mesh):
@@ -794,7 +879,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
             scale_priors = np.stack([s["extent"] for s in scenes])
         r = run_ensemble(cfg, dino_model, shot_model, [s["pc"] for s in scenes], descs, seed, scene_ids, num_pairs,
                          num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
-                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if verify_obj is not None else None)
+                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if verify_obj is not None else None,
+                         centre_peaks=centre_peaks)
         cls_id = category2id.get(cat, 0)
         icp_stats = None
         ver = None
@@ -828,6 +914,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                     c_ = int(ver["chosen"][b])
                     item["verify"] = dict(hypotheses=int(np.count_nonzero((ver["hypotheses"][b]["flags"] & verify.EMPTY) == 0)),
                                           chosen=c_, score=float(ver["scores"][b, c_]), score_first=float(ver["scores"][b, 0]))
+                    if centre_peaks > 1:
+                        item["verify"]["centre_peak"] = int(ver["centre_peak"][b])
                 if scenes[b]["R"] is not None:
                     item["tr_err_cm"] = float(np.linalg.norm(rec["t"] - scenes[b]["t"]) * 100)
                     item["rot_err_deg"] = geometry.rot_err_deg(rec["R"], scenes[b]["R"], up_sym)
@@ -879,6 +967,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
     if verify_obj is not None:
         report["verification"] = ("%d pose hypotheses per instance from %d peaks per vote, rendered and compared with the depth "
                                   "at tau = %g m (cppf_pose_hypotheses, cppf_depth_fit_counts)" % (hypotheses, verify.PEAKS, verify_tau))
+        if centre_peaks > 1:
+            report["verification"] += _CENTRE_NOTE % centre_peaks
     if bop_obj is not None and bop_reported:
         errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
         report["bop"] = dict(bop.average_recall(errs, bop_obj.diameter, bop_width), delta=bop.DELTA, taus=list(bop.TAUS))

@@ -197,6 +197,25 @@ int cppf_vote_center(int B, const float* pts, const int32_t* pt_off, const int32
                      void* workspace, int64_t workspace_bytes,
                      int64_t* out_argmax, uint32_t* out_peak, double* out_world, void* stream);
 
+/* Separated peaks of the centre-vote grid (not in the reference, which reads the arg-max only): greedy non-maximum suppression,
+ * exact and in integer arithmetic.  grids / grid / grid_off / cells_cap / res: as handed to cppf_vote_center, which wrote the
+ * uint32 grids (any accumulation mode, weighted or not); grid_off NULL: scene b at b * cells_cap.  1 <= K <= 16 peaks per scene,
+ * sep_cells >= 0 the suppression radius in cells.  Per scene:
+ *   peak 0 = the first maximum of the grid (largest value, lowest flat index on ties): cppf_vote_center's out_argmax / out_peak /
+ *     out_world bit for bit, including index 0 for an all-zero grid and, for a scene whose ncell > cells_cap, index 0 with the
+ *     sentinel value 0xFFFFFFFF (such a scene has n_peaks = 1);
+ *   peak k = the first maximum over the cells with a value > 0 that no earlier peak suppresses; cell (ix, iy, iz) is suppressed by a
+ *     peak (px, py, pz) when (ix-px)^2 + (iy-py)^2 + (iz-pz)^2 <= sep_cells^2 (integers);
+ *   when no cell is left the remaining slots carry peak_idx = -1, peak_val = 0, peak_world = NaN.
+ * Outputs: peak_idx int64[B,K] (flat C-order cell), peak_val uint32[B,K], peak_world float64[B,K,3] = (double)c0 + (double)i * res
+ * per axis (cppf_vote_center's arithmetic), n_peaks int32[B] (>= 1); peak_val / peak_world / n_peaks may be NULL.  K masked passes
+ * over the grid, merged by integer max on (value, inverted index) keys: a scene's peaks do not depend on the batch or its order.
+ * workspace: cppf_grid_peaks_workspace_bytes(B, K) bytes (0 for invalid sizes).  B <= 65535. */
+int64_t cppf_grid_peaks_workspace_bytes(int B, int K);
+int cppf_grid_peaks(int B, const CppfSceneGrid* grids, const uint32_t* grid, const int64_t* grid_off, int64_t cells_cap,
+                    double res, int K, int sep_cells, int64_t* peak_idx, uint32_t* peak_val, double* peak_world,
+                    int32_t* n_peaks, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- a7. back-vote ("noisy pair") filter + importance weights: replaces eval.py:251-275.
  *   centers: float64[B,3] voted centres (T_est); kidx/gamma: per scene, the order-statistic index and
  *   interpolation weight np.percentile(back_errs, ratio*100) uses (device arrays int32[B], float32[B];
