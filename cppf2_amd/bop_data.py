@@ -9,7 +9,8 @@ the results CSV, and the BOP'19 average recall of a results file over a dataset.
 Layout read (and written by write_dataset): models/models_info.json and models/obj_{id:06d}.ply (model units, `mesh_scale` to
 metres); {split}/{scene:06d}/scene_camera.json (cam_K, depth_scale per image), scene_gt.json (cam_R_m2c, cam_t_m2c, obj_id per
 instance), depth/{im:06d}.png (16 bit; metres = value * depth_scale / 1000), and optionally scene_gt_info.json and
-mask_visib/{im:06d}_{gt:06d}.png, which are computed with bop.gt_visibility when absent.  Poses are handed out in the record
+mask_visib/{im:06d}_{gt:06d}.png, which are computed with bop.gt_visibility when absent; read_detections / write_detections
+handle a detections file (COCO-style JSON, run-length encoded masks: masks.py).  Poses are handed out in the record
 convention of bop.py (centred model, metres).  No BOP dataset and no bop_toolkit were available to compare against: the formats
 and rules are written from the BOP'19 definitions and parity with bop_toolkit's numbers is unpinned.
 """
@@ -102,6 +103,73 @@ def read_results(path):
 def read_targets(path):
     """[(scene_id, im_id, obj_id, inst_count)] of a BOP targets file (test_targets_bop19.json)."""
     return [(int(t["scene_id"]), int(t["im_id"]), int(t["obj_id"]), int(t.get("inst_count", 1))) for t in _read_json(path)]
+
+
+# ----------------------------------------------------------------------------------------------
+# detections file (the BOP challenge's "default detections": COCO-style JSON with run-length encoded masks)
+# ----------------------------------------------------------------------------------------------
+def _detection(e, where, image_size):
+    from . import masks
+    try:
+        seg = e["segmentation"]
+        size = [int(x) for x in seg["size"]]
+        if len(size) != 2 or min(size) < 1:
+            raise ValueError("segmentation size %r is not [H, W]" % (seg["size"],))
+        det = dict(scene_id=int(e["scene_id"]), image_id=int(e["image_id"]), category_id=int(e["category_id"]),
+                   bbox=[float(x) for x in e.get("bbox", [0, 0, 0, 0])], score=float(e["score"]), time=float(e.get("time", -1.0)),
+                   size=(size[0], size[1]))
+        if len(det["bbox"]) != 4:
+            raise ValueError("bbox %r is not [x, y, w, h]" % (e["bbox"],))
+        counts = seg["counts"]
+        if isinstance(counts, (str, bytes)):
+            counts = masks.string_to_counts(counts)
+        elif not isinstance(counts, (list, tuple)) or any(isinstance(x, bool) or not isinstance(x, int) for x in counts):
+            raise ValueError("segmentation counts are a list of integers or a compressed string")
+        det["counts"] = [int(x) for x in masks.check_counts(counts, size[0], size[1])]
+    except (KeyError, TypeError, ValueError) as err:                  # (masks.RleError is a ValueError)
+        raise BopDataError("%s: %s%s" % (where, "missing field " if isinstance(err, KeyError) else "", err)) from None
+    check_detection_size(det, image_size, where)
+    return det
+
+
+def check_detection_size(det, image_size, where="detection"):
+    """BopDataError when a detection's mask size differs from its image's.  image_size: (H, W), a callable (scene_id, image_id)
+    -> (H, W), or None (not checked)."""
+    if image_size is None:
+        return
+    want = image_size(det["scene_id"], det["image_id"]) if callable(image_size) else image_size
+    if tuple(int(x) for x in want) != tuple(det["size"]):
+        raise BopDataError("%s: mask size %s differs from the %s of image %d of scene %d" % (
+            where, list(det["size"]), [int(x) for x in want], det["image_id"], det["scene_id"]))
+
+
+def read_detections(path, image_size=None):
+    """[dict(scene_id, image_id, category_id (= obj_id), bbox [x, y, w, h], score, time, size (H, W), counts [int])] of a
+    detections file: a JSON list with one entry per detection, its mask under segmentation {counts, size [H, W]} as COCO run
+    lengths (a list, or the compressed string: masks.string_to_counts).  BopDataError for a missing field, a mask size that
+    differs from the image's (image_size: see check_detection_size), runs that do not sum to H * W, a negative run and a string
+    that does not parse."""
+    try:
+        entries = _read_json(path)
+    except ValueError as err:
+        raise BopDataError("%s: not JSON (%s)" % (path, err)) from None
+    if not isinstance(entries, list):
+        raise BopDataError("%s: a detections file is a JSON list" % path)
+    return [_detection(e, "%s entry %d" % (path, n), image_size) for n, e in enumerate(entries)]
+
+
+def write_detections(path, dets, compress=True):
+    """Writes a detections file read_detections gives back: dets as read_detections returns them (time and bbox optional);
+    compress: counts as COCO's compressed string, else as a list."""
+    from . import masks
+    out = []
+    for d in dets:
+        H, W = (int(x) for x in d["size"])
+        counts = [int(x) for x in masks.check_counts(d["counts"], H, W)]
+        out.append(dict(scene_id=int(d["scene_id"]), image_id=int(d["image_id"]), category_id=int(d["category_id"]),
+                        bbox=[float(x) for x in d.get("bbox", [0, 0, 0, 0])], score=float(d["score"]), time=float(d.get("time", -1.0)),
+                        segmentation=dict(counts=masks.counts_to_string(counts) if compress else counts, size=[H, W])))
+    _write_json(path, out)
 
 
 # ----------------------------------------------------------------------------------------------

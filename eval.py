@@ -46,6 +46,16 @@ What the image cannot provide is stated, not faked:
     the negated alignment loss; time: the image's share of its batches' wall time), which bop_data.score then scores.
     `--teacher_prior` (this mode only) builds the logit prior and the scale from each instance's ground-truth pose, the same
     stand-in the synthetic mode uses: trained checkpoints are absent from this tree, and without it untrained weights vote noise.
+  * `--data=bop --detections=<json> [--det_score_min=0.0]` starts from a detections file instead (bop_data.read_detections:
+    COCO-style JSON, one entry per detection with a score and a run-length encoded mask): every detection of a target's object
+    in its image with score >= det_score_min is decoded on the GPU (cppf2_amd.masks, cppf_rle_decode) and gives one CSV row
+    (score: the detection's, times the verification score with --hypotheses > 1); bop_data.score keeps the best inst_count per
+    target.  With `--teacher_prior` a detection takes the prior of the valid ground-truth instance whose visible mask overlaps
+    it most; one that overlaps none is dropped (skipped.no_gt_for_prior).
+  * `--clean_masks [--mask_jump=0.01]` (--data=bop, with or without detections; `--clean_mask` with --data=depth) cuts every
+    mask down to its largest depth-connected component (cppf_mask_components: valid 4-neighbours within mask_jump metres)
+    before back-projection and verification: depth-separated bleed of a detector's mask onto the background or onto a
+    neighbour goes, a table the object stands on stays.  Off by default.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import json
@@ -600,13 +610,17 @@ def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, 
 def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1,
              num_pairs=50000, num_rots=180, opt=True, geo_branch=True, visual_branch=True, seed=0, batch_instances=16,
              icp_iters=0, hypotheses=1, verify_tau=None, teacher_prior=False, visib_gt_min=None, debug=False, out=None,
-             centre_peaks=1):
+             centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False, mask_jump=None):
     """The instance-level path over one split of a BOP-format dataset (cppf2_amd.bop_data.Dataset): one estimate per valid
     ground-truth instance of every target, from its visible mask; poses written to `out_csv` in BOP's frame and scored with
     bop_data.score.  Instances of one object (and one K and image size) are evaluated in batches of `batch_instances` across
-    images.  Returns the report (report["bop"] = bop_data.score's)."""
+    images.  detections: a detections file (bop_data.read_detections); every detection of a target's object in its image with
+    score >= det_score_min then stands where the ground-truth instances stood, its mask decoded on the GPU (masks.decode_batch,
+    one call per target), and gives one CSV row (score: the detection's, times the verification score with hypotheses > 1).
+    clean_masks: every mask is cut down to its largest depth-connected component (masks.clean, mask_jump metres) before
+    back-projection and verification.  Returns the report (report["bop"] = bop_data.score's)."""
     import time
-    from cppf2_amd import bop, bop_data, icp, verify
+    from cppf2_amd import bop, bop_data, icp, masks, verify
     dev = ops._dev()
     cfg, dino_model, shot_model = setup
     up_sym = bool(cfg.get("up_sym", False))
@@ -617,6 +631,29 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
     icp_models, pending, rows, summary = {}, {}, [], []
     im_time = {}
     skipped = dict(too_few_points=0, too_large=0, no_pick=0)
+    mask_jump = masks.JUMP if mask_jump is None else float(mask_jump)
+    if clean_masks:
+        skipped["empty_after_clean"] = 0
+    dets = None
+    if detections is not None:
+        # every detection's runs are checked here; its size against its image's when the image is read
+        n_detections = 0
+        dets = {}
+        wanted = {(s_, i_, o_) for s_, i_, o_, _ in tlist}
+        skipped.update(below_score=0, no_target=0)
+        if "empty_after_clean" not in skipped:
+            skipped["empty_after_clean"] = 0
+        if teacher_prior:
+            skipped["no_gt_for_prior"] = 0
+        for n_, det in enumerate(bop_data.read_detections(detections)):
+            n_detections += 1
+            key = (det["scene_id"], det["image_id"], det["category_id"])
+            if key not in wanted:
+                skipped["no_target"] += 1
+            elif det["score"] < float(det_score_min):
+                skipped["below_score"] += 1
+            else:
+                dets.setdefault(key, []).append(dict(det, index=n_))
     gid = [0]
 
     def flush(key):
@@ -660,6 +697,8 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
             im_time[(c_["scene_id"], c_["im_id"])] = im_time.get((c_["scene_id"], c_["im_id"]), 0.0) + dt + c_["prep_s"]
             item = dict(scene_id=c_["scene_id"], im_id=c_["im_id"], obj_id=o, gt_index=c_["gt_index"], points=int(c_["pc"].shape[0]),
                         model=None)
+            if dets is not None:
+                item.update(detection=c_["det"]["index"], det_score=c_["det"]["score"])
             summary.append(item)
             if r["pick"][b] < 0:
                 skipped["no_pick"] += 1
@@ -679,29 +718,69 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
                 item["icp"] = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
             Rb, tb = bop.pose_to_bop(np.asarray(rec["R"], dtype=np.float64).reshape(3, 3), np.asarray(rec["t"], dtype=np.float64), mesh_scale,
                                      obj.centre)
+            if dets is not None:
+                score = c_["det"]["score"] * score if ver is not None else c_["det"]["score"]
             item.update(model=["dino", "shot"][r["pick"][b]], loss=float(r["best"][b]), score=score)
             rows.append(dict(scene_id=c_["scene_id"], im_id=c_["im_id"], obj_id=o, score=score, R=Rb, t=tb))
 
+    def candidates(s_id, im, o, info, gts, depth):
+        """The masks that stand for the instances of one target: [dict(mask bool [H,W], gt, gt_index, det)].  Ground-truth mode:
+        the visible mask of every valid instance.  Detections: every kept detection's decoded mask, one decode call; with the
+        teacher prior each takes the valid ground-truth instance of its object whose visible mask overlaps it most (IoU; the
+        lower instance index on ties) and is dropped when none overlaps."""
+        valid = [g for g, gt in enumerate(gts) if gt["obj_id"] == o and info[g]["visib_fract"] >= vmin]
+        if dets is None:
+            return [dict(mask=ds.mask_visib(s_id, im, g), gt=gts[g], gt_index=g, det=None) for g in valid]
+        lst = dets.get((s_id, im, o), [])
+        if not lst:
+            return []
+        for det in lst:
+            bop_data.check_detection_size(det, depth.shape, "%s entry %d" % (detections, det["index"]))
+        decoded = masks.decode_batch([det["counts"] for det in lst], depth.shape[0], depth.shape[1]).cpu().numpy() > 0
+        out = []
+        gt_masks = [ds.mask_visib(s_id, im, g) for g in valid] if teacher_prior else []
+        for det, m in zip(lst, decoded):
+            g = None
+            if teacher_prior:
+                inter = [int(np.count_nonzero(m & gm)) for gm in gt_masks]
+                iou = [i_ / max(int(np.count_nonzero(m | gm)), 1) for i_, gm in zip(inter, gt_masks)]
+                if not inter or max(inter) == 0:
+                    skipped["no_gt_for_prior"] += 1
+                    continue
+                g = valid[int(np.argmax(iou))]
+            out.append(dict(mask=m, gt=None if g is None else gts[g], gt_index=g, det=det))
+        return out
+
+    depth_of = {}
     for s_id, im, o, _ in tlist:
         sc = ds.scene(s_id)
         info = ds.gt_info(s_id)[im]
         K = sc["camera"][im]["K"]
-        depth = None
-        for g, gt in enumerate(sc["gt"].get(im, [])):
-            if gt["obj_id"] != o or info[g]["visib_fract"] < vmin:
-                continue
+        t0 = time.perf_counter()
+        if (s_id, im) not in depth_of:
+            depth_of = {(s_id, im): ds.depth(s_id, im)}                                    # (the last image's is kept)
+        depth = depth_of[(s_id, im)]
+        cands = candidates(s_id, im, o, info, sc["gt"].get(im, []), depth)
+        if clean_masks and cands:
+            kept, stats = masks.clean(np.stack([c_["mask"] for c_ in cands]), depth, 0, mask_jump)
+            kept, stats = kept.cpu().numpy() > 0, stats.cpu().numpy()
+            for c_, m_, st_ in zip(cands, kept, stats):
+                c_.update(mask=m_, clean=dict(components=int(st_[0]), kept_pixels=int(st_[2]), valid_pixels=int(st_[3])))
+        shared = (time.perf_counter() - t0) / max(len(cands), 1)
+        for c_ in cands:
             t0 = time.perf_counter()
-            if depth is None:
-                depth = ds.depth(s_id, im)
-            m = ds.mask_visib(s_id, im, g)
+            m = c_["mask"]
+            gid[0] += 1
+            if clean_masks and not m.any():
+                skipped["empty_after_clean"] += 1
+                continue
             pc, _ = ops.backproject(depth.astype(np.float64), K, m, return_device=True)    # as the depth mode does
-            inst_seed = (seed * 1000003 + gid[0]) & 0x7FFFFFFF
+            inst_seed = (seed * 1000003 + gid[0] - 1) & 0x7FFFFFFF
             if pc.shape[0]:
                 pc = pc[ops.downsample(pc, cfg.res, inst_seed, return_device=True)]
             pc = pc.cpu().numpy()
             if pc.shape[0] > 50000:
                 pc = pc[np.random.RandomState(inst_seed).randint(pc.shape[0], size=50000)]
-            gid[0] += 1
             if pc.shape[0] < cfg.num_more + 2:
                 skipped["too_few_points"] += 1
                 continue
@@ -709,8 +788,9 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
                 skipped["too_large"] += 1
                 continue
             key = (o, K.tobytes(), depth.shape)
-            pending.setdefault(key, []).append(dict(scene_id=s_id, im_id=im, gt_index=g, gid=gid[0] - 1, pc=pc, gt=gt, depth=depth,
-                                                    mask=m, K=K, prep_s=time.perf_counter() - t0))
+            pending.setdefault(key, []).append(dict(scene_id=s_id, im_id=im, gt_index=c_["gt_index"], gid=gid[0] - 1, pc=pc,
+                                                    gt=c_["gt"], depth=depth, mask=m, K=K, det=c_["det"],
+                                                    prep_s=shared + time.perf_counter() - t0))
             if len(pending[key]) >= int(batch_instances):
                 flush(key)
     for key in list(pending):
@@ -724,6 +804,11 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
     report = dict(data="bop", bop_root=str(bop_root), split=str(split), targets=len(tlist), instances=len(summary), rows=len(rows),
                   skipped=skipped, out_csv=str(out_csv), teacher_prior=bool(teacher_prior),
                   opt_refinement="100 Adam steps (cppf_refine_pose)" if opt else "off", bop=scored, results=summary)
+    if dets is not None:
+        report.update(detections=n_detections, detections_file=str(detections), det_score_min=float(det_score_min))
+    if clean_masks:
+        report["mask_cleaning"] = ("largest depth-connected component of each mask, neighbours within %g m "
+                                   "(cppf_mask_components)" % mask_jump)
     if icp_iters > 0:
         report["icp_refinement"] = "%d point-to-plane ICP iterations against each object's model (cppf_icp_refine)" % icp_iters
     if hypotheses > 1:
@@ -767,8 +852,12 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          intrinsics=None, depth_scale=1000.0, out=None, out_pkl=None, log_dir=None, data_root="NOCS/real_test", out_dir=None,
          desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
          models_info=None, hypotheses=1, verify_tau=None, bop_root=None, split="test", targets=None, out_csv=None,
-         teacher_prior=False, model_scale=0.001, centre_peaks=1):
+         teacher_prior=False, model_scale=0.001, centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False,
+         clean_mask=False, mask_jump=None):
     custom = False
+    clean_masks = bool(clean_masks) or bool(clean_mask)
+    if mask_jump is not None and not (float(mask_jump) >= 0.0 and np.isfinite(float(mask_jump))):
+        raise ValueError("--mask_jump is a distance in metres >= 0, not %r" % (mask_jump,))
     if data == "bop":
         # the BOP-dataset mode: its models come from the dataset, every other mode below runs as before
         if not bop_root or not out_csv:
@@ -783,7 +872,12 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev), bop_root, split, out_csv, targets,
                         float(model_scale), angle_tol, imp_wt_margin, backproj_ratio,
                         num_pairs, num_rots, opt, geo_branch, visual_branch, seed, batch_instances, int(icp_iters), int(hypotheses),
-                        verify_tau, bool(teacher_prior), None, debug, out, centre_peaks)
+                        verify_tau, bool(teacher_prior), None, debug, out, centre_peaks, detections, float(det_score_min), clean_masks,
+                        mask_jump)
+    if detections is not None:
+        raise ValueError("--detections is a BOP detections file: it needs --data=bop")
+    if clean_masks and data != "depth":
+        raise ValueError("--clean_masks cleans instance masks against the depth image: it needs --data=bop or --data=depth")
     if teacher_prior:
         raise ValueError("--teacher_prior builds the prior from a BOP dataset's ground-truth poses: it needs --data=bop")
     icp_iters = int(icp_iters)
@@ -852,6 +946,14 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
             d = np.array(Image.open(depth)).astype(np.float64) / float(depth_scale)
             m = np.array(Image.open(mask))
             m = (m[..., 0] if m.ndim == 3 else m) > 0
+            if clean_masks:
+                # the largest depth-connected component of the mask (cppf_mask_components): what is back-projected and verified
+                from cppf2_amd import masks
+                kept, stats = masks.clean(m[None], d.astype(np.float32), 0, masks.JUMP if mask_jump is None else float(mask_jump))
+                m = kept[0].cpu().numpy() > 0
+                mask_stats = [int(x) for x in stats[0].cpu().numpy()]
+                if not m.any():
+                    raise ValueError("--clean_mask: no depth-connected component of the mask has %d pixels" % masks.MIN_PIXELS)
             K = np.array(intrinsics if intrinsics is not None else
                          [[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]], dtype=np.float64).reshape(3, 3)
             pc, _ = ops.backproject(d, K, m, return_device=True)               # eval.py:185-189 (flip + f32 cast folded in)
@@ -961,6 +1063,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
 
     report = dict(categories=categories, instances=len(summary),
                   opt_refinement="100 Adam steps (cppf_refine_pose)" if opt else "off", results=summary)
+    if clean_masks:
+        report["mask_cleaning"] = dict(components=mask_stats[0], kept_pixels=mask_stats[2], valid_pixels=mask_stats[3])
     if icp_model is not None:
         report["icp_refinement"] = "%d point-to-plane ICP iterations against %s (cppf_icp_refine)" % (icp_iters, os.path.basename(mesh))
         report["icp"] = [s_["icp"] for s_ in summary if "icp" in s_]

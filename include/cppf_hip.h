@@ -427,6 +427,31 @@ int cppf_mssd_mspd(int P, const float* verts, int V, const double* syms, int S, 
 int cppf_gt_visibility(int G, int I, int H, int W, const float* depth_test, const int32_t* img_idx, const float* renders,
                        const double* h_K, double delta, int64_t* counts, int32_t* bbox, uint8_t* mask_visib, void* stream);
 
+/* ---- detector masks: run-length decoding and depth-connected cleaning (the reference uses a mask as given, eval.py:173-201) ----
+ * Integers only: a mask's output bytes do not depend on the batch or the order.  D masks, D <= 65535, D = 0 launches nothing;
+ * one image size H x W (<= 8192 each) per call.  The exact order of the operations is stated in cppf2_amd/csrc/cppf_mask.hip.
+ *
+ * cppf_rle_decode: COCO's run-length rule.  runs int32[total_runs] (device): the D masks' run lengths one after the other,
+ * run_off int32[D+1] (device): mask d owns runs[run_off[d] .. run_off[d+1]-1].  The runs of a mask are column-major (position
+ * c * H + r) and alternate 0s and 1s, starting with 0s.  out uint8[D,H,W], row-major, 255 or 0; positions past the end of a
+ * mask's runs are 0.  The caller checks that the runs are non-negative and sum to H * W (cppf2_amd/masks.py does, on the host,
+ * before the launch); whatever they hold, no access leaves the arrays.  No workspace, one launch.
+ *
+ * cppf_mask_components: the largest depth-connected component of each mask.  masks uint8[D,H,W] (!= 0: set), depths
+ * float32[I,H,W] (metres), img_idx int32[D] (the image of each mask; outside [0, I): an empty result).  A pixel is valid when
+ * mask != 0 && depth > 0 && depth is finite; two valid 4-neighbours are connected when fabsf(d_a - d_b) <= jump (one float32
+ * subtraction; jump >= 0, finite, metres).  A component's label is its lowest flat index r * W + c.  Kept: the component with
+ * the most pixels, ties to the lowest label, if it has at least min_pixels (>= 0) pixels.  out_mask uint8[D,H,W] = 255 on the
+ * kept component, else 0 (it may be `masks` itself); stats int32[D,4] = (components, kept label or -1, kept pixels, valid
+ * pixels).  workspace: cppf_mask_components_workspace_bytes(D, H, W) bytes, 8-byte aligned (0 for sizes the call refuses).
+ * Five launches behind two clears on the stream, no host synchronisation. */
+int cppf_rle_decode(int D, int H, int W, const int32_t* runs, int64_t total_runs, const int32_t* run_off, uint8_t* out,
+                    void* stream);
+int64_t cppf_mask_components_workspace_bytes(int D, int H, int W);
+int cppf_mask_components(int D, int I, int H, int W, const uint8_t* masks, const float* depths, const int32_t* img_idx, float jump,
+                         int min_pixels, uint8_t* out_mask, int32_t* stats, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 /* ---- instance-level hypothesis verification: render and compare (not in the reference) -------------------------------
  * Several peaks of each rotation-bin vote become pose hypotheses; each hypothesis' render (cppf_render_depth) is counted
  * against the observed depth, and cppf2_amd/verify.py keeps the one that explains most of it.  The exact order of the
