@@ -102,6 +102,8 @@ STABLE = {
     "cppf_render_depth": (_i, [_i, _p, _i64, _p, _p, _i64, _p, _p, _i, _i, _f, _f, _i, _p, _p, _p, _p, _i64, _i64, _p]),
     "cppf_icp_workspace_bytes": (_i64, [_i, _i]),
     "cppf_icp_refine": (_i, [_i, _p, _p, _i, _p, _p, _i, _i, _f, _f, _p, _p, _p, _i64, _p]),
+    "cppf_icp_depth_workspace_bytes": (_i64, [_i, _i, _i]),
+    "cppf_icp_refine_depth": (_i, [_i, _p, _p, _i, _p, _p, _i, _p, _i, _i, _i, _p, _p, _f, _i, _f, _f, _p, _p, _p, _i64, _p]),
     "cppf_vsd_counts": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _p, _d, _p, _p, _i, _p, _p]),
     "cppf_mssd_mspd": (_i, [_i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p]),
     "cppf_gt_visibility": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _d, _p, _p, _p, _p]),

@@ -83,7 +83,60 @@ def _workspace(B, max_n, dev):
     return ws
 
 
-def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST):
+_WS_DEPTH = {}           # the same for cppf_icp_refine_depth
+
+
+def _workspace_depth(B, max_n, M, dev):
+    key = shot._key(dev)
+    ws = _WS_DEPTH.pop(key, None)
+    need = _L.cppf_icp_depth_workspace_bytes(B, max_n, M)
+    if need < 0:
+        raise CppfError("cppf_icp_depth_workspace_bytes: invalid sizes B=%d max_n=%d M=%d" % (B, max_n, M))
+    if ws is None or ws.numel() < need:
+        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+    _WS_DEPTH[key] = ws
+    while len(_WS_DEPTH) > WS_CACHE_MAX:
+        del _WS_DEPTH[next(iter(_WS_DEPTH))]
+    return ws
+
+
+def _depth_args(depth, img_idx, K, model_weight, B):
+    """The host side of refine's depth arguments, checked before anything touches a device: (I, H, W, img_idx int32 [B] NumPy,
+    K float64 [9], model_weight)."""
+    shape = tuple(depth.shape)
+    if len(shape) == 2:
+        shape = (1,) + shape
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError("icp.refine: depth must be a non-empty [H,W] or [I,H,W] image batch, not %s" % (tuple(depth.shape),))
+    dt = depth.dtype
+    if dt not in (torch.float32, np.dtype(np.float32)):
+        raise ValueError("icp.refine: depth must be float32 metres, not %s" % (dt,))
+    I = shape[0]
+    if K is None:
+        raise ValueError("icp.refine: depth needs K, the camera's 3x3 intrinsics")
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError("icp.refine: K must be a 3x3 matrix, not %s" % (K.shape,))
+    if not (np.isfinite(K[0, 0]) and np.isfinite(K[1, 1]) and K[0, 0] > 0 and K[1, 1] > 0):
+        raise ValueError("icp.refine: K needs finite fx, fy > 0")
+    w = float(model_weight)
+    if not (w > 0 and np.isfinite(w)):
+        raise ValueError("icp.refine: model_weight must be finite and > 0, not %r" % (model_weight,))
+    if img_idx is None:
+        if I == B:
+            idx = np.arange(B, dtype=np.int32)
+        elif I == 1:
+            idx = np.zeros(B, dtype=np.int32)
+        else:
+            raise ValueError("icp.refine: %d depth images for %d instances need img_idx" % (I, B))
+    else:
+        idx = (img_idx.cpu().numpy() if torch.is_tensor(img_idx) else np.asarray(img_idx)).astype(np.int32).reshape(-1)
+        if idx.size != B:
+            raise ValueError("icp.refine: img_idx of %d entries for %d instances" % (idx.size, B))
+    return I, shape[1], shape[2], idx, np.ascontiguousarray(K.reshape(9)), w
+
+
+def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST, depth=None, img_idx=None, K=None, model_weight=1.0):
     """Refines the poses of `results` in place against `model` (cppf_icp_refine) and returns the stats float32 [B,4]: inliers
     of the last iteration, their RMS point-to-plane distance, inliers / n, iterations that changed the pose.
 
@@ -91,7 +144,27 @@ def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST):
     results: the records, either a device uint8 [B,160] tensor (a VotingPipeline's results / selected; stats come back as a
     device tensor) or a pipeline.RESULT_DTYPE array (stats come back as a NumPy array).  Records flagged empty (flags bit0)
     are left as they are; every other one gets flags bit4.  B = 0 (pt_off of one entry) is an empty batch: nothing is launched
-    and the stats are an empty [0,4] array (device tensor or NumPy, as above)."""
+    and the stats are an empty [0,4] array (device tensor or NumPy, as above).
+
+    depth (float32 metres, [H,W] or [I,H,W], NumPy or device tensor) adds the model-to-depth terms (cppf_icp_refine_depth,
+    DESIGN.md section 19): every model sample facing the camera is associated with the surface seen at its pixel of image
+    img_idx[b] (int [B]; default arange(B) when I == B, zeros when I == 1) through the intrinsics K (3x3), its terms weighted by
+    model_weight.  The stats are then float32 [B,8]: the four above for the observed points, then the model-side inliers of the
+    last iteration, their RMS distance, inliers / visible in-image samples, and the visible in-image samples.  With depth,
+    pts = None and pt_off = None mean no observed points (no mask): B is then the number of records."""
+    if depth is None:
+        if img_idx is not None or K is not None or float(model_weight) != 1.0:
+            raise ValueError("icp.refine: img_idx, K and model_weight belong to depth")
+        if pts is None or pt_off is None:
+            raise ValueError("icp.refine: without depth, pts and pt_off are required")
+    elif (pts is None) != (pt_off is None):
+        raise ValueError("icp.refine: pts and pt_off are given together or not at all")
+    if depth is not None:
+        nrec = len(results) if isinstance(results, np.ndarray) else results.shape[0]
+        dargs = _depth_args(depth, img_idx, K, model_weight, nrec)
+        if pt_off is None:
+            pts, pt_off = np.zeros((0, 3), dtype=np.float32), np.zeros(nrec + 1, dtype=np.int64)
+    ncol = 4 if depth is None else 8
     dev = ops._dev()
     host_records = isinstance(results, np.ndarray)
     if host_records:
@@ -105,20 +178,32 @@ def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST):
     if B != rec.shape[0]:
         raise CppfError("icp.refine: %d records for %d instances" % (rec.shape[0], B))
     if B == 0:
-        return np.zeros((0, 4), dtype=np.float32) if host_records else torch.zeros((0, 4), dtype=torch.float32, device=dev)
-    max_n = max(int(np.diff(off_h).max()), 1)
+        return np.zeros((0, ncol), dtype=np.float32) if host_records else torch.zeros((0, ncol), dtype=torch.float32, device=dev)
+    max_n = int(np.diff(off_h).max())
+    if depth is None:
+        max_n = max(max_n, 1)
     pts = ops._t(pts, torch.float32, dev).reshape(-1, 3).contiguous()
     if pts.shape[0] < off_h[-1]:
         raise CppfError("icp.refine: pt_off reaches %d points, pts holds %d" % (off_h[-1], pts.shape[0]))
     off = pt_off.to(device=dev, dtype=torch.int32).contiguous() if torch.is_tensor(pt_off) else \
         torch.from_numpy(off_h.astype(np.int32)).to(dev)
     mp, mn = model.device(dev)
-    stats = torch.empty((B, 4), dtype=torch.float32, device=dev)
-    ws = _workspace(B, max_n, dev)
+    stats = torch.empty((B, ncol), dtype=torch.float32, device=dev)
     d0, d1 = (float(x) for x in max_dist)
-    _lib.check(_L.cppf_icp_refine(B, ops._p(pts), ops._p(off), max_n, ops._p(mp), ops._p(mn), mp.shape[0], int(iters),
-                                  C.c_float(d0), C.c_float(d1), ops._p(rec), ops._p(stats), ops._p(ws), ws.numel(),
-                                  ops._stream()), "cppf_icp_refine")
+    if depth is None:
+        ws = _workspace(B, max_n, dev)
+        _lib.check(_L.cppf_icp_refine(B, ops._p(pts), ops._p(off), max_n, ops._p(mp), ops._p(mn), mp.shape[0], int(iters),
+                                      C.c_float(d0), C.c_float(d1), ops._p(rec), ops._p(stats), ops._p(ws), ws.numel(),
+                                      ops._stream()), "cppf_icp_refine")
+    else:
+        I, H, W, idx, K9, w = dargs
+        dimg = ops._t(depth, torch.float32, dev).reshape(I, H, W).contiguous()
+        idx_d = torch.from_numpy(idx).to(dev)
+        ws = _workspace_depth(B, max_n, mp.shape[0], dev)
+        _lib.check(_L.cppf_icp_refine_depth(B, ops._p(pts) if max_n > 0 else None, ops._p(off), max_n, ops._p(mp), ops._p(mn),
+                                            mp.shape[0], ops._p(dimg), I, H, W, ops._p(idx_d), K9.ctypes.data_as(C.c_void_p),
+                                            C.c_float(w), int(iters), C.c_float(d0), C.c_float(d1), ops._p(rec), ops._p(stats),
+                                            ops._p(ws), ws.numel(), ops._stream()), "cppf_icp_refine_depth")
     if host_records:
         results[...] = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=results.dtype).reshape(results.shape)
         return stats.cpu().numpy()

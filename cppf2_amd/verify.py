@@ -125,20 +125,21 @@ def _as_records(records):
 
 
 def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_model=None, icp_iters=0, tau=TAU,
-           chunk=RENDER_CHUNK):
+           chunk=RENDER_CHUNK, icp_depth=False, icp_model_weight=1.0):
     """Verifies H pose hypotheses of each of B instances and keeps one per instance.
 
     obj_or_mesh: a bop.ObjectInfo or a render.Mesh (metres); depth [B,H_img,W_img] or [H_img,W_img] (metres, 0 = no reading) and
     mask (non-zero: the instance) of the same shape: instance b is seen in image b; K: the camera's 3x3 intrinsics; records
     [B,H] (RESULT_DTYPE, or a device uint8 [B,H,160] tensor such as hypotheses() returns).  With icp_iters > 0, every
     non-empty hypothesis is first refined by icp.refine against icp_model (an icp.ModelPoints) from the instance's points pts
-    float32 [N,3] (camera frame), pt_off int [B+1].  Each hypothesis is then rendered (back faces culled); one that is not
+    float32 [N,3] (camera frame), pt_off int [B+1]; with icp_depth that refinement also uses the instance's depth image (the
+    model-to-depth terms of icp.refine(depth=...), weighted by icp_model_weight) and icp is float32 [B,H,8].  Each hypothesis is then rendered (back faces culled); one that is not
     finite, or puts a vertex nearer than render.ZNEAR (the renderer does not clip), is not drawn and scores 0.  score() of its
     fit_counts at (tau,) ranks it, and choose() picks.
 
     Returns dict(records RESULT_DTYPE [B] (the chosen records, flags bit5, the hypothesis index in pad_[1]; an instance whose
     hypotheses are all empty keeps records[b, 0] unmarked), chosen int64 [B] (-1: none), scores float64 [B,H] (NaN for empty
-    slots), counts int64 [B,H,5], hypotheses RESULT_DTYPE [B,H] (after ICP), icp float32 [B,H,4] or None)."""
+    slots), counts int64 [B,H,5], hypotheses RESULT_DTYPE [B,H] (after ICP), icp float32 [B,H,4] ([B,H,8] with icp_depth) or None)."""
     obj = obj_or_mesh if isinstance(obj_or_mesh, bop.ObjectInfo) else bop.ObjectInfo.from_mesh(obj_or_mesh)
     dev = ops._dev()
     host, rec = _as_records(records)
@@ -160,8 +161,12 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
         # each instance's points once per hypothesis: the B*H records refine in one batch
         sel = torch.from_numpy(np.concatenate([np.arange(off[b], off[b + 1]) for b in range(B) for _ in range(Hh)])).to(dev)
         rep_off = np.concatenate([[0], np.cumsum(np.repeat(np.diff(off), Hh))])
-        stats = icp.refine(icp_model, p[sel].contiguous(), rep_off, rec, iters=int(icp_iters))
-        stats = stats.cpu().numpy().reshape(B, Hh, 4)
+        if icp_depth:                              # hypothesis h of instance b is record b * H + h: it reads image b
+            stats = icp.refine(icp_model, p[sel].contiguous(), rep_off, rec, iters=int(icp_iters), depth=d,
+                               img_idx=np.repeat(np.arange(B), Hh), K=K, model_weight=icp_model_weight)
+        else:
+            stats = icp.refine(icp_model, p[sel].contiguous(), rep_off, rec, iters=int(icp_iters))
+        stats = stats.cpu().numpy().reshape(B, Hh, -1)
         host = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=RESULT_DTYPE).reshape(B, Hh).copy()
     # poses of the records (float64), drawable ones
     R = host["R"].reshape(-1, 3, 3)

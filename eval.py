@@ -22,6 +22,10 @@ What the image cannot provide is stated, not faked:
   * `--data=depth --mesh=<ply|obj> [--mesh_scale=1.0] --icp_iters=N` (N > 0) refines the selected pose of the instance by N
     point-to-plane ICP iterations against samples of the object's mesh (cppf2_amd.icp, cppf_icp_refine; not in the
     reference), after the ensemble selection and `opt`; the report gains the ICP stats.  --icp_iters=0 (default): off.
+  * `--icp_iters=N --icp_depth [--icp_model_weight=1.0]` (--data=depth and --data=bop) adds the model-to-depth terms to that ICP
+    (cppf_icp_refine_depth): every model sample facing the camera is associated with the surface the depth
+    image shows at its pixel, inside the mask or not, its terms weighted by --icp_model_weight; on both routes, the direct
+    refinement and the per-hypothesis one of --hypotheses > 1.  The ICP stats gain the model-side figures.  Off by default.
   * `--data=depth --mesh=<ply|obj> --gt_pose=<.npy|.txt> [--models_info=<json>]` scores the reported pose against the true one
     (a 3x4 or 4x4 model -> OpenCV camera matrix in the record convention, metres) with the BOP metrics VSD, MSSD and MSPD
     (cppf2_amd.bop; --models_info: the object's BOP models_info entry, for its symmetries and diameter): each result gains
@@ -584,7 +588,27 @@ def _instance_hypotheses(selected, pick, hyps, enabled, H):
     return recs, centre
 
 
-def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, icp_iters, tau):
+def _icp_item(st):
+    """The ICP stats of one instance as the report carries them; the model-side figures when cppf_icp_refine_depth ran."""
+    item = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
+    if len(st) == 8:
+        item.update(model_inliers=int(st[4]), model_rms=float(st[5]), model_inlier_frac=float(st[6]), model_visible=int(st[7]))
+    return item
+
+
+def _icp_depth_flag(icp_depth, icp_model_weight, icp_iters):
+    if icp_depth and int(icp_iters) <= 0:
+        raise ValueError("--icp_depth adds the model-to-depth terms to the ICP refinement: it needs --icp_iters > 0")
+    w = float(icp_model_weight)
+    if not (w > 0 and np.isfinite(w)):
+        raise ValueError("--icp_model_weight must be finite and > 0, not %r" % (icp_model_weight,))
+    if w != 1.0 and not icp_depth:
+        raise ValueError("--icp_model_weight weighs the model-to-depth terms: it needs --icp_depth")
+    return bool(icp_depth), w
+
+
+def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, icp_iters, tau, icp_depth=False,
+                      icp_model_weight=1.0):
     """The hypotheses of each instance in _instance_hypotheses' order, cut at H (empty slots past the end; an instance without a
     pick gets only empty slots), then verify.select (ICP first when icp_iters > 0) on the instance's image.  The result also
     carries centre int64 [B,H] (the centre-vote peak of each hypothesis, -1 for empty slots) and centre_peak int64 [B] (that of
@@ -601,7 +625,9 @@ def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, 
     else:
         img = np.broadcast_to(np.asarray(depth, dtype=np.float32), (B,) + np.shape(depth))
         msk = np.broadcast_to(np.asarray(mask, dtype=bool), (B,) + np.shape(mask))
-    out = verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=icp_iters, tau=tau)
+    extra = dict(icp_depth=True, icp_model_weight=icp_model_weight) if icp_depth else {}
+    out = verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=icp_iters, tau=tau,
+                        **extra)
     out["centre"] = centre
     out["centre_peak"] = centre[np.arange(B), np.maximum(out["chosen"], 0)]
     return out
@@ -610,7 +636,8 @@ def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, 
 def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1,
              num_pairs=50000, num_rots=180, opt=True, geo_branch=True, visual_branch=True, seed=0, batch_instances=16,
              icp_iters=0, hypotheses=1, verify_tau=None, teacher_prior=False, visib_gt_min=None, debug=False, out=None,
-             centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False, mask_jump=None):
+             centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False, mask_jump=None, icp_depth=False,
+             icp_model_weight=1.0):
     """The instance-level path over one split of a BOP-format dataset (cppf2_amd.bop_data.Dataset): one estimate per valid
     ground-truth instance of every target, from its visible mask; poses written to `out_csv` in BOP's frame and scored with
     bop_data.score.  Instances of one object (and one K and image size) are evaluated in batches of `batch_instances` across
@@ -687,11 +714,15 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
         if hypotheses > 1:
             ver = _verify_instances(r, B, hypotheses, (geo_branch, visual_branch), obj, np.stack([c_["depth"] for c_ in chunk]),
                                     np.stack([c_["mask"] for c_ in chunk]), chunk[0]["K"], pt_off, icp_models.get(o), icp_iters,
-                                    verify_tau)
+                                    verify_tau, icp_depth, icp_model_weight)
             if icp_iters > 0:
                 icp_stats = ver["icp"][np.arange(B), np.maximum(ver["chosen"], 0)]
         elif icp_iters > 0:
-            icp_stats = icp.refine(icp_models[o], r["pts"], pt_off, r["selected"], iters=icp_iters)
+            extra = {}
+            if icp_depth:
+                extra = dict(depth=np.stack([c_["depth"] for c_ in chunk]).astype(np.float32), K=chunk[0]["K"],
+                             model_weight=icp_model_weight)
+            icp_stats = icp.refine(icp_models[o], r["pts"], pt_off, r["selected"], iters=icp_iters, **extra)
         dt = (time.perf_counter() - t0) / B
         for b, c_ in enumerate(chunk):
             im_time[(c_["scene_id"], c_["im_id"])] = im_time.get((c_["scene_id"], c_["im_id"]), 0.0) + dt + c_["prep_s"]
@@ -714,8 +745,7 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
                 if centre_peaks > 1:
                     item["verify"]["centre_peak"] = int(ver["centre_peak"][b])
             if icp_stats is not None:
-                st = icp_stats[b]
-                item["icp"] = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
+                item["icp"] = _icp_item(icp_stats[b])
             Rb, tb = bop.pose_to_bop(np.asarray(rec["R"], dtype=np.float64).reshape(3, 3), np.asarray(rec["t"], dtype=np.float64), mesh_scale,
                                      obj.centre)
             if dets is not None:
@@ -811,6 +841,8 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
                                    "(cppf_mask_components)" % mask_jump)
     if icp_iters > 0:
         report["icp_refinement"] = "%d point-to-plane ICP iterations against each object's model (cppf_icp_refine)" % icp_iters
+        if icp_depth:
+            report["icp_refinement"] = _ICP_DEPTH_NOTE % (icp_iters, "each object's model", icp_model_weight)
     if hypotheses > 1:
         report["verification"] = ("%d pose hypotheses per instance from %d peaks per vote, rendered and compared with the depth "
                                   "at tau = %g m (cppf_pose_hypotheses, cppf_depth_fit_counts)" % (hypotheses, verify.PEAKS, verify_tau))
@@ -823,6 +855,8 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
     return report
 
 
+_ICP_DEPTH_NOTE = ("%d point-to-plane ICP iterations against %s, observed points to model and model samples to the depth image, "
+                   "model weight %g (cppf_icp_refine_depth)")
 _CENTRE_NOTE = "; translation hypotheses from %d separated peaks of each centre vote (cppf_grid_peaks)"
 
 
@@ -853,8 +887,12 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
          models_info=None, hypotheses=1, verify_tau=None, bop_root=None, split="test", targets=None, out_csv=None,
          teacher_prior=False, model_scale=0.001, centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False,
-         clean_mask=False, mask_jump=None):
+         clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0):
     custom = False
+    if data in ("depth", "bop"):
+        icp_depth, icp_model_weight = _icp_depth_flag(icp_depth, icp_model_weight, icp_iters)
+    elif icp_depth:
+        raise ValueError("--icp_depth refines against the depth image: it needs --data=depth or --data=bop")
     clean_masks = bool(clean_masks) or bool(clean_mask)
     if mask_jump is not None and not (float(mask_jump) >= 0.0 and np.isfinite(float(mask_jump))):
         raise ValueError("--mask_jump is a distance in metres >= 0, not %r" % (mask_jump,))
@@ -873,7 +911,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                         float(model_scale), angle_tol, imp_wt_margin, backproj_ratio,
                         num_pairs, num_rots, opt, geo_branch, visual_branch, seed, batch_instances, int(icp_iters), int(hypotheses),
                         verify_tau, bool(teacher_prior), None, debug, out, centre_peaks, detections, float(det_score_min), clean_masks,
-                        mask_jump)
+                        mask_jump, icp_depth, icp_model_weight)
     if detections is not None:
         raise ValueError("--detections is a BOP detections file: it needs --data=bop")
     if clean_masks and data != "depth":
@@ -988,13 +1026,15 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         ver = None
         if verify_obj is not None:
             ver = _verify_instances(r, B, hypotheses, (geo_branch, visual_branch), verify_obj, d, m, K,
-                                    np.cumsum([0] + [s["pc"].shape[0] for s in scenes]), icp_model, icp_iters, verify_tau)
+                                    np.cumsum([0] + [s["pc"].shape[0] for s in scenes]), icp_model, icp_iters, verify_tau,
+                                    icp_depth, icp_model_weight)
             if icp_model is not None:
                 icp_stats = ver["icp"][np.arange(B), np.maximum(ver["chosen"], 0)]
         elif icp_model is not None:
             # after the ensemble selection (and `opt`): the selected record of each instance against the mesh
+            extra = dict(depth=d.astype(np.float32), K=K, model_weight=icp_model_weight) if icp_depth else {}
             icp_stats = icp.refine(icp_model, r["pts"], np.cumsum([0] + [s["pc"].shape[0] for s in scenes]), r["selected"],
-                                   iters=icp_iters)
+                                   iters=icp_iters, **extra)
         for b in range(B):
             RT, sc = np.eye(4), np.ones(3)                                      # eval.py:143-144 defaults
             item = dict(scene=scene_ids[b], category=cat, model=None)
@@ -1010,8 +1050,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                             losses=[float(r["losses"][0][b]), float(r["losses"][1][b])], pred_RT=RT.tolist(),
                             pred_scale=sc.tolist())
                 if icp_stats is not None:
-                    st = icp_stats[b]
-                    item["icp"] = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
+                    item["icp"] = _icp_item(icp_stats[b])
                 if ver is not None:
                     c_ = int(ver["chosen"][b])
                     item["verify"] = dict(hypotheses=int(np.count_nonzero((ver["hypotheses"][b]["flags"] & verify.EMPTY) == 0)),
@@ -1067,6 +1106,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         report["mask_cleaning"] = dict(components=mask_stats[0], kept_pixels=mask_stats[2], valid_pixels=mask_stats[3])
     if icp_model is not None:
         report["icp_refinement"] = "%d point-to-plane ICP iterations against %s (cppf_icp_refine)" % (icp_iters, os.path.basename(mesh))
+        if icp_depth:
+            report["icp_refinement"] = _ICP_DEPTH_NOTE % (icp_iters, os.path.basename(mesh), icp_model_weight)
         report["icp"] = [s_["icp"] for s_ in summary if "icp" in s_]
     if verify_obj is not None:
         report["verification"] = ("%d pose hypotheses per instance from %d peaks per vote, rendered and compared with the depth "

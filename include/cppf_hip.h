@@ -384,6 +384,24 @@ int cppf_icp_refine(int B, const float* pts, const int32_t* pt_off, int max_n, c
                     int M, int iters, float d0, float d1, CppfSceneResult* results, float* stats, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* cppf_icp_refine_depth: the same refinement with the other direction added, model to depth image (3 launches per iteration, no
+ * host synchronisation).  Besides the observed points' terms, every model sample that faces the camera under the current pose
+ * is projected to its pixel of the instance's depth image (depth float32[I,H,W], metres; img_idx int32[B]: the image of each
+ * instance, outside [0, I): no model-side terms for it; K: host, 3x3 row-major, fx, fy > 0; pixel (r, c) back-projects through
+ * (c, r)), the depth there (finite and > 0) is back-projected, and when that point lies within d_k of the sample it adds its
+ * point-to-plane terms times model_weight (> 0) to the same normal equations.  There is no z-buffer: a sample hidden by another
+ * part of the object meets the nearer surface, and the distance gate drops it.  max_n = 0 with an all-zero pt_off (pts may be
+ * null) refines without observed points, i.e. without a mask.  The inlier test (>= 6) and the solve use the weighted sums of
+ * both sides.  The exact arithmetic is stated in cppf2_amd/csrc/cppf_icp.hip.  No atomics.
+ * stats float32[B,8]: [0..2] as cppf_icp_refine's, for the observed points; [3] iterations with a non-zero step; [4] model-side
+ * inliers of the last iteration, [5] their RMS of e, [6] inliers / visible in-image samples, [7] visible in-image samples.
+ * workspace: cppf_icp_depth_workspace_bytes(B, max_n, M) bytes (< 0 for invalid sizes; CPPF_ECAPACITY when too small). */
+int64_t cppf_icp_depth_workspace_bytes(int B, int max_n, int M);
+int cppf_icp_refine_depth(int B, const float* pts, const int32_t* pt_off, int max_n, const float* model_pts, const float* model_nrm,
+                          int M, const float* depth, int I, int H, int W, const int32_t* img_idx, const double* K,
+                          float model_weight, int iters, float d0, float d1, CppfSceneResult* results, float* stats,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- instance-level pose errors: the BOP metrics VSD, MSSD, MSPD (Hodan et al.; BOP'19; the reference has no scorer) ----
  * Both calls take P (estimate, ground truth) pairs, P <= 65535; P = 0 launches nothing.  h_K = (fx, fy, cx, cy), host doubles,
  * one K for every pair.  Neither needs a workspace.  Integer atomics only: the results do not depend on the batch or the order.
