@@ -31,7 +31,8 @@ struct Mat3d {
 // with positive depth.  Arithmetic as the reference: float64 rays K^-1 [u, v, 1], xyz * z / xyz_z, then (after the
 // reference's double negation of x and y cancels) a cast to float32.
 // REF64 (cppf_backproject64): float64 depth in, float64 points out WITH the reference's negated x and y -- utils/util.py:2586-2607
-// itself, bit for bit (every operation below is the one NumPy performs, in float64, in its order).
+// itself (every operation below is the one NumPy performs, in float64, in its order), bit for bit for intrinsics without skew:
+// with skew, NumPy's matmul may fuse k1*v into the sum, which -ffp-contract=off forbids here.
 template <typename TD, typename TO, bool REF64>
 __global__ __launch_bounds__(PREP_THREADS) void backproject_kernel(const TD* __restrict__ depth,
                                                                    const uint8_t* __restrict__ mask, int H, int W,
@@ -96,7 +97,8 @@ extern "C" int cppf_backproject64(const double* depth, const uint8_t* mask, int 
 // ---------------------------------------------------------------------------------------------
 // voxel down-sample: open-addressing hash of voxel keys; every voxel keeps the point with the smallest Philox
 // priority (= a uniformly random member, independent of thread order); survivors are emitted in ascending point
-// index by an ordered compaction, so the result is reproducible.
+// index by an ordered compaction, so the result is reproducible.  The key packs the three voxel indices into 21-bit fields: at
+// most 2^21 cells per axis (include/cppf_hip.h).
 // ---------------------------------------------------------------------------------------------
 #define VOX_EMPTY 0xffffffffffffffffull
 

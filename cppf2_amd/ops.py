@@ -885,7 +885,8 @@ def backproject(depth, intrinsics, instance_mask, return_device=False):
 
 def backproject_reference(depth, intrinsics, instance_mask):
     """utils/util.py:2586-2607 as the reference returns it: (pts float64[n,3] with x and y negated, (rows, cols) int64) --
-    cppf_backproject64: float64 depth in, the reference's float64 operations in its order, bit-identical to NumPy's array."""
+    cppf_backproject64: float64 depth in, the reference's float64 operations in its order; bit-identical to NumPy's array for
+    intrinsics without skew (with skew NumPy's matmul may fuse a product and differ in the last place of x)."""
     dev = _dev()
     d = _t(depth, torch.float64, dev)
     m = _t(np.asarray(instance_mask) != 0 if not isinstance(instance_mask, torch.Tensor) else instance_mask != 0,

@@ -329,13 +329,19 @@ int cppf_backproject(const float* depth, const uint8_t* mask, int H, int W, cons
                      float* out_pts, int32_t* out_rowcol, int32_t* out_count, void* stream);
 /* backproject() (utils/util.py:2586-2607) exactly as the reference returns it (ABI 9): depth float64[H,W], out_pts float64[cap,3]
  * with x and y NEGATED (the reference's own convention; its callers negate them back, eval.py:187-188) -- the same float64
- * operations in the same order, so the array is bit-identical to NumPy's.  What `utils.util.backproject` binds. */
+ * operations, each rounded where it stands: x = (k0*u + k1*v) + k2 per row of inv(K), then x*z/w, y*z/w, w*z/w.  For intrinsics
+ * without skew the array is bit-identical to NumPy's (one product of each ray coordinate is by 0, one by 1); with skew NumPy's
+ * matmul may fuse a product into the sum and differ in the last place of x (tests/test_prep.py).  What `utils.util.backproject`
+ * binds. */
 int cppf_backproject64(const double* depth, const uint8_t* mask, int H, int W, const double* h_kinv, int cap,
                        double* out_pts, int32_t* out_rowcol, int32_t* out_count, void* stream);
 /* One uniformly random point per `res` voxel (anchored at the cloud's min corner): replaces downsample()
  * (utils/util.py:39-46, open3d voxel_down_sample_and_trace + np.random.choice).  The draw is Philox(seed, point
  * index), so the kept set does not depend on thread order; out_idx int32[n] holds the kept point indices in
- * ascending order, out_count their number. */
+ * ascending order, out_count their number.  The kept point of a voxel is the one with the smallest
+ * (philox4x32_10(counter (i,0,0,7), key (seed_lo, seed_hi)).v[0] << 32) | i.  Voxel index = floor((p - min) / res) in float32 per
+ * axis; the three indices are packed into 21-bit fields of one 64-bit key, so the cloud may span at most 2^21 cells per axis
+ * (extent / res < 2^21).  Beyond that, voxels alias; the call does not check it. */
 int64_t cppf_voxel_downsample_workspace_bytes(int64_t n);
 int cppf_voxel_downsample(const float* pts, int n, float res, uint64_t seed, int32_t* out_idx, int32_t* out_count,
                           void* workspace, int64_t workspace_bytes, void* stream);

@@ -34,7 +34,8 @@ def downsample(pc, res):
 def backproject(depth, intrinsics, instance_mask):
     """utils/util.py:2586-2607: (pts float64[n,3] with x and y negated, (rows, cols)) for the masked pixels with depth > 0, in
     np.where's row-major order.  cppf_backproject64 on the GPU: the reference's float64 operations in the reference's order, so
-    the array is the reference's bit for bit (callers negate x, y back and cast to float32, eval.py:187-189)."""
+    for intrinsics without skew the array is the reference's bit for bit; with skew NumPy's matmul may fuse a product and differ
+    in the last place of x (callers negate x, y back and cast to float32, eval.py:187-189)."""
     return _ops.backproject_reference(depth, intrinsics, instance_mask)
 
 
