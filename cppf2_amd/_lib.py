@@ -124,6 +124,8 @@ STABLE = {
     "cppf_alignment_loss": (_i, [_i, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p]),
     "cppf_ensemble_select": (_i, [_i, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "cppf_assemble_pose": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "cppf_pair_keys": (_i, [_i, _p, _p, _p, _p, _i, _p, _p, _i64, _i, _f, _i, _p, _i, _p, _p, _p]),
+    "cppf_pair_table_draw": (_i, [_i, _p, _p, _p, _i, _p, _p, _i64, _i, _f, _i, _p, _p, _p, _i64, _p, _p, _p, _p]),
 }
 
 EXPERIMENTAL = {

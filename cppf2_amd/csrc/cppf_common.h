@@ -292,6 +292,47 @@ __device__ __forceinline__ float sqrt_rn(float x) {
   return r;
 }
 
+// The point-pair feature key of a pair-feature table (cppf_table.hip): length bin and three angle bins of
+// (p0, n0) -> (p1, n1), every operation a float32 one in the written order and no transcendental (the angle bins compare
+// cosines with edges[j] = cos(j pi / na), filled by the host), so that a NumPy float32 restatement gives the same key.
+// key = -1: coincident points, a pair of nd * d_step or longer, an all-zero normal (a normal nan_to_zero_ cleared) or a
+// non-finite input.  The length bin is clamped to nd - 1: len < nd * d_step does not bound the ROUNDED quotient len / d_step.
+struct PairKey {
+  int key, bd, a1, a2, a3;
+};
+
+__device__ __forceinline__ int pair_angle_bin(float c, int na, const float* __restrict__ edges) {
+  int a = 0;
+  for (int j = 1; j < na; ++j) a += (c < edges[j]) ? 1 : 0;
+  return a;
+}
+
+__device__ __forceinline__ PairKey pair_key(const float* __restrict__ p0, const float* __restrict__ p1, const float* __restrict__ n0,
+                                            const float* __restrict__ n1, int nd, float d_step, int na,
+                                            const float* __restrict__ edges) {
+  PairKey r;
+  r.key = -1; r.bd = 0; r.a1 = 0; r.a2 = 0; r.a3 = 0;
+  const float ax = p0[0], ay = p0[1], az = p0[2], bx = p1[0], by = p1[1], bz = p1[2];
+  const float n0x = n0[0], n0y = n0[1], n0z = n0[2], n1x = n1[0], n1y = n1[1], n1z = n1[2];
+  const float dx = bx - ax, dy = by - ay, dz = bz - az;
+  const float len = __builtin_sqrtf((dx * dx + dy * dy) + dz * dz);
+  // x - x is 0 for a finite x and NaN otherwise: one sum tests all twelve inputs
+  const float fin = (((ax - ax) + (ay - ay)) + ((az - az) + (bx - bx))) + (((by - by) + (bz - bz)) + ((n0x - n0x) + (n0y - n0y))) +
+                    (((n0z - n0z) + (n1x - n1x)) + ((n1y - n1y) + (n1z - n1z)));
+  const bool zero0 = n0x == 0.0f && n0y == 0.0f && n0z == 0.0f, zero1 = n1x == 0.0f && n1y == 0.0f && n1z == 0.0f;
+  if (!(fin == 0.0f) || zero0 || zero1 || len == 0.0f || !(len < (float)nd * d_step)) return r;
+  const float c1 = ((n0x * dx + n0y * dy) + n0z * dz) / len;
+  const float c2 = ((n1x * dx + n1y * dy) + n1z * dz) / len;
+  const float c3 = (n0x * n1x + n0y * n1y) + n0z * n1z;
+  const int bd = (int)(len / d_step);
+  r.bd = bd < nd - 1 ? bd : nd - 1;
+  r.a1 = pair_angle_bin(c1, na, edges);
+  r.a2 = pair_angle_bin(c2, na, edges);
+  r.a3 = pair_angle_bin(c3, na, edges);
+  r.key = ((r.bd * na + r.a1) * na + r.a2) * na + r.a3;
+  return r;
+}
+
 // first-maximum reduction on (value, index) pairs: larger value wins, ties -> smaller index.
 __device__ __forceinline__ void argmax_combine(uint32_t& v, int64_t& i, uint32_t ov, int64_t oi) {
   if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }

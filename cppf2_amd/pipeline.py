@@ -299,10 +299,11 @@ class VotingPipeline:
                                        ops._p(self.kept_count), int(bool(y_only)), int(steps), C.c_float(lr),
                                        ops._p(self.results), ops._stream()), "cppf_refine_pose")
 
-    def vote(self, pts, idx, logits, uniforms, pred_scales=None, grid=None, grid_off=None, centre_peaks=1, sep=None):
+    def vote(self, pts, idx, logits, uniforms, pred_scales=None, grid=None, grid_off=None, centre_peaks=1, sep=None, nb=None):
         """Everything after the MLP: eval.py:225-313.  All arguments are device tensors in the batch layout.
         Returns the device tensor of B result records (uint8 [B,160]); use results_to_numpy() to read them.
-        logits=None: the bins are already in self.bins (drawn by the MLP's output layer, ops.reslayer_split_decode).
+        logits=None: the bins are already in self.bins (drawn by the MLP's output layer, ops.reslayer_split_decode, or from a
+        pair-feature table, pair_table.PairTable.draw); nb: their bin count when it is not the default 32 (read only then).
         pred_scales: float32 [T, 3], or a callable evaluated after the back-vote filter that returns it -- the scale head is read
         only for the kept pairs (eval.py:272), so a caller can run it on just those rows (kept_rows32 / kept_count / max_kept).
         centre_peaks = C > 1 (not in the reference): the centre vote is written to a grid (the caller's, or one the pipeline
@@ -320,7 +321,7 @@ class VotingPipeline:
         if not 1 <= C_ <= MAX_CENTRE_PEAKS:
             raise _lib.CppfError("vote: centre_peaks must be in [1, %d], not %d" % (MAX_CENTRE_PEAKS, C_))
         if logits is None:
-            self.decode_from_bins(pts, idx)
+            self.decode_from_bins(pts, idx, 32 if nb is None else nb)
         else:
             self.decode(pts, idx, logits, uniforms)
         scales = (lambda: pred_scales() if callable(pred_scales) else pred_scales)

@@ -60,6 +60,12 @@ What the image cannot provide is stated, not faked:
     mask down to its largest depth-connected component (cppf_mask_components: valid 4-neighbours within mask_jump metres)
     before back-projection and verification: depth-separated bleed of a detector's mask onto the background or onto a
     neighbour goes, a table the object stands on stays.  Off by default.
+  * `--pair_table=<npz>` (--data=depth) / `--pair_tables=<dir>` (--data=bop: one obj_%06d.npz per object; a missing one is an
+    error that names the file) vote from the object's pair-feature table (python -m cppf2_amd.pair_table)
+    instead of the two models: one pass (run_table) whose bins are looked up from each tuple's point-pair feature, no prior, no
+    checkpoint; --hypotheses, --centre_peaks, --icp_iters, --icp_depth, --opt, --gt_pose, --out_csv, --detections and
+    --clean_masks work as before, and the report gains `table_hits` (per instance: tuples that took their own cell, a
+    neighbouring cell, the whole table).  Not with --teacher_prior, --ckpt_* or the synthetic / NOCS modes.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import json
@@ -92,10 +98,13 @@ def _flag(v):
     return v
 
 
-def load_custom(ckpt_shot=None, ckpt_dino=None, config_dir="config", device=None):
-    """The instance-level setup of the reference's demo (config/custom.yaml: no category group): (cfg, dino, shot)."""
+def load_custom(ckpt_shot=None, ckpt_dino=None, config_dir="config", device=None, models=True):
+    """The instance-level setup of the reference's demo (config/custom.yaml: no category group): (cfg, dino, shot).
+    models=False: (cfg, None, None) -- a pair-feature table stands where the models stood (run_table)."""
     dev = device or ops._dev()
     cfg = load_config(config_dir, "custom", [])
+    if not models:
+        return cfg, None, None
     dino_model = BeyondCPPFDino(cfg).to(dev).eval()
     shot_model = BeyondCPPFShot(cfg).to(dev).eval()
     if ckpt_dino:
@@ -180,6 +189,72 @@ def _pipelines(dev, Ns, num_pairs, k, cfg, num_rots, angle_tol, backproj_ratio, 
     return hit[:3]
 
 
+def _vote_cap(pcs, cfg):
+    """cells_cap of a batch's vote grids (a power of two >= 2^18); refuses an instance the reference skips (eval.py:200) and a
+    batch whose grids do not fit."""
+    for p in pcs:                                                                          # eval.py:200
+        if ((p.max(0) - p.min(0)).max() / cfg.res) > 1000:
+            raise ValueError("instance larger than 1000 cells: the reference skips it (eval.py:200); drop it from the batch")
+    cap = max(1 << 18, max(needed_cells(p, cfg.res) for p in pcs))
+    cap = 1 << int(np.ceil(np.log2(cap)))
+    if cap * len(pcs) > (1 << 33):
+        raise ValueError("vote grids of %d cells x %d instances do not fit one batch; evaluate fewer instances per call" % (cap, len(pcs)))
+    return cap
+
+
+def _hypothesis_args(hypotheses, centre_peaks):
+    """(hypotheses: None or int >= 1, centre_peaks: int >= 1) of run_ensemble / run_table, checked."""
+    if hypotheses is not None:
+        hypotheses = int(hypotheses)
+        if hypotheses < 1:
+            raise ValueError("hypotheses must be >= 1, not %d" % hypotheses)
+    centre_peaks = int(centre_peaks)
+    if centre_peaks < 1:
+        raise ValueError("centre_peaks must be >= 1, not %d" % centre_peaks)
+    if centre_peaks > 1 and hypotheses is None:
+        raise ValueError("centre_peaks > 1 forms hypotheses per centre-vote peak: it needs hypotheses")
+    return hypotheses, centre_peaks
+
+
+def _pass_hypotheses(pp, hypotheses, centre_peaks, up_sym):
+    """(H hypotheses of a pass from the peaks of its two votes, slot 0 = its assembled record; with centre_peaks > 1 also the
+    list per centre-vote peak, peak 0's being the former, else None), right after the pass' vote: device tensors."""
+    from cppf2_amd import verify
+    hyps = verify.hypotheses(pp.counts[0], pp.counts[1], pp.sphere, pp.results, hypotheses, pp.up_axis, pp.right_axis,
+                             y_only=up_sym)
+    if centre_peaks <= 1:
+        return hyps, None
+    # the further peaks' hypotheses from their own counts and records (peak 0's are the ones above)
+    return hyps, [hyps] + [verify.hypotheses(pp.centre_counts[c, 0], pp.centre_counts[c, 1], pp.sphere, pp.centre_results[c],
+                                             hypotheses, pp.up_axis, pp.right_axis, y_only=up_sym) for c in range(1, centre_peaks)]
+
+
+def _pass_output(pipe, records, idx, pts, hypotheses, hyps, centre_hyps, centre_n):
+    """The dict run_ensemble / run_table return, from the two passes' records (host), after pipe.select(): refuses records that
+    were not voted; hyps / centre_hyps / centre_n: per pass, device tensors or None."""
+    B = pipe.B
+    for rec in records:
+        bad = np.nonzero(rec["flags"] & 6)[0]
+        if bad.size:
+            raise RuntimeError("instances %s were not voted (flags %s: grid above cells_cap / int32)" %
+                               (bad.tolist(), rec["flags"][bad].tolist()))
+    chosen = pipe.results_to_numpy(pipe.selected)
+    losses = pipe.losses.cpu().numpy()                                                     # [2,B] float64
+    pick = chosen["pad_"][:, 0].astype(np.int64)
+    best = pipe.best.cpu().numpy()
+    scale = records[0]["scale"].copy()                                                     # eval.py:308-310: float32 [B,3]
+    scale_norm = np.array([np.linalg.norm(s_) for s_ in scale], dtype=np.float32)          # np.linalg.norm per instance
+    out = dict(records=records, selected=chosen, losses=losses, pick=pick, best=best, scale=scale.astype(np.float64),
+               scale_norm=scale_norm.astype(np.float64), idx=idx, pipe=pipe, pts=pts)
+    if hypotheses is not None:
+        out["hypotheses"] = [pipe.results_to_numpy(h_.reshape(-1, 160)).reshape(B, hypotheses) for h_ in hyps]
+    if centre_hyps[0] is not None:
+        out["centre_hypotheses"] = [np.stack([pipe.results_to_numpy(h_.reshape(-1, 160)).reshape(B, hypotheses) for h_ in ch])
+                                    for ch in centre_hyps]
+        out["centre_n"] = [n_.cpu().numpy() for n_ in centre_n]
+    return out
+
+
 @torch.no_grad()
 def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_pairs, num_rots, angle_tol=1.,
                  imp_wt_margin=0.01, backproj_ratio=.1, opt=False, geo_branch=True, visual_branch=True, up_sym=False,
@@ -204,13 +279,7 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
     B = len(pcs)
     Ns = [int(p.shape[0]) for p in pcs]
     k = cfg.num_more + 2
-    for p in pcs:                                                                          # eval.py:200
-        if ((p.max(0) - p.min(0)).max() / cfg.res) > 1000:
-            raise ValueError("instance larger than 1000 cells: the reference skips it (eval.py:200); drop it from the batch")
-    cap = max(1 << 18, max(needed_cells(p, cfg.res) for p in pcs))
-    cap = 1 << int(np.ceil(np.log2(cap)))
-    if cap * B > (1 << 33):
-        raise ValueError("vote grids of %d cells x %d instances do not fit one batch; evaluate fewer instances per call" % (cap, B))
+    cap = _vote_cap(pcs, cfg)
     pts = torch.from_numpy(np.concatenate(pcs)).to(dev)
     two = bool(two_streams) and not keep
     pipe, twin, scale_bufs = _pipelines(dev, Ns, num_pairs, k, cfg, num_rots, angle_tol, backproj_ratio, imp_wt_margin, cap, two)
@@ -234,16 +303,7 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
     kept = []
     extra = {}
     hyps = [None, None]
-    if hypotheses is not None:
-        from cppf2_amd import verify
-        hypotheses = int(hypotheses)
-        if hypotheses < 1:
-            raise ValueError("hypotheses must be >= 1, not %d" % hypotheses)
-    centre_peaks = int(centre_peaks)
-    if centre_peaks < 1:
-        raise ValueError("centre_peaks must be >= 1, not %d" % centre_peaks)
-    if centre_peaks > 1 and hypotheses is None:
-        raise ValueError("centre_peaks > 1 forms hypotheses per centre-vote peak: it needs hypotheses")
+    hypotheses, centre_peaks = _hypothesis_args(hypotheses, centre_peaks)
     centre_hyps, centre_n = [None, None], [None, None]
     dino_scored = torch.cuda.Event() if two else None
 
@@ -285,13 +345,8 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
             pp.vote(pts, idx, None if pred_cls is None else pred_cls.contiguous(), u, pred_scales)
         if hypotheses is not None:
             # here, on this pass' stream: the one-stream order reuses pp.counts for the next pass, and `opt` rewrites the records
-            hyps[model_idx] = verify.hypotheses(pp.counts[0], pp.counts[1], pp.sphere, pp.results, hypotheses, pp.up_axis,
-                                                pp.right_axis, y_only=up_sym)
+            hyps[model_idx], centre_hyps[model_idx] = _pass_hypotheses(pp, hypotheses, centre_peaks, up_sym)
             if centre_peaks > 1:
-                # the further peaks' hypotheses from their own counts and records (peak 0's are the ones above)
-                centre_hyps[model_idx] = [hyps[model_idx]] + [
-                    verify.hypotheses(pp.centre_counts[c, 0], pp.centre_counts[c, 1], pp.sphere, pp.centre_results[c], hypotheses,
-                                      pp.up_axis, pp.right_axis, y_only=up_sym) for c in range(1, centre_peaks)]
                 centre_n[model_idx] = pp.centre_n
         if opt:
             pp.refine(pts, idx, up_sym)                                                    # eval.py:319-355
@@ -318,28 +373,65 @@ def run_ensemble(cfg, dino_model, shot_model, pcs, descs, seed, scene_ids, num_p
     # ---- ensemble selection (eval.py:217,365-372): strict '<' against inf, model 0 first -- on the device ---------
     pipe.select(geo_branch, visual_branch)
     records = [pipe.results_to_numpy(pipe.result_slots[m]) for m in (0, 1)]                # the 160-byte records: the first read
-    for rec in records:
-        bad = np.nonzero(rec["flags"] & 6)[0]
-        if bad.size:
-            raise RuntimeError("instances %s were not voted (flags %s: grid above cells_cap / int32)" %
-                               (bad.tolist(), rec["flags"][bad].tolist()))
-    chosen = pipe.results_to_numpy(pipe.selected)
-    losses = pipe.losses.cpu().numpy()                                                     # [2,B] float64
-    pick = chosen["pad_"][:, 0].astype(np.int64)
-    best = pipe.best.cpu().numpy()
-    scale = records[0]["scale"].copy()                                                     # eval.py:308-310: float32 [B,3]
-    scale_norm = np.array([np.linalg.norm(s_) for s_ in scale], dtype=np.float32)          # np.linalg.norm per instance
-    out = dict(records=records, selected=chosen, losses=losses, pick=pick, best=best, scale=scale.astype(np.float64),
-               scale_norm=scale_norm.astype(np.float64), idx=idx, pipe=pipe, pts=pts)
-    if hypotheses is not None:
-        out["hypotheses"] = [pipe.results_to_numpy(h_.reshape(-1, 160)).reshape(B, hypotheses) for h_ in hyps]
-    if centre_peaks > 1:
-        out["centre_hypotheses"] = [np.stack([pipe.results_to_numpy(h_.reshape(-1, 160)).reshape(B, hypotheses) for h_ in ch])
-                                    for ch in centre_hyps]
-        out["centre_n"] = [n_.cpu().numpy() for n_ in centre_n]
+    out = _pass_output(pipe, records, idx, pts, hypotheses, hyps, centre_hyps, centre_n)
     if keep:
         out["kept"] = kept
         out["shot_feat"], out["normal"] = extra["shot_feat"].cpu().numpy(), extra["normal"].cpu().numpy()
+    return out
+
+
+_TABLES = {}               # (path, device) -> pair_table.PairTable on the device
+
+
+def load_pair_table(path, dev):
+    """The pair-feature table of `path` on `dev`, loaded once per process; a missing file is an error that names it."""
+    from cppf2_amd import pair_table
+    key = (os.path.abspath(str(path)), str(torch.device(dev)))
+    if key not in _TABLES:
+        if not os.path.isfile(key[0]):
+            raise FileNotFoundError("pair table %s not found (build it with `python -m cppf2_amd.pair_table`)" % path)
+        _TABLES[key] = pair_table.PairTable.load(key[0]).to(dev)
+    return _TABLES[key]
+
+
+@torch.no_grad()
+def run_table(cfg, table, pcs, seed, scene_ids, num_pairs, num_rots, angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1,
+              opt=False, up_sym=False, hypotheses=None, centre_peaks=1):
+    """run_ensemble's place for a known object: ONE pass whose bins come from the object's pair-feature table
+    (pair_table.PairTable.vote) instead of the two model passes.  Normals:
+    shot.normals_device(pts, pt_off, res * 10), NaN -> 0; no descriptor is computed.  The pass writes record slot 0 and the
+    selection is select(True, False).  Returns run_ensemble's dict (records = the pass' twice, losses row 1 = inf, pick 0 or -1,
+    hypotheses / centre_hypotheses with the pass' list in both places: callers enable pass 0 only) plus table_hits int [B,3]."""
+    dev = ops._dev()
+    Ns = [int(p.shape[0]) for p in pcs]
+    k = cfg.num_more + 2
+    res_built = table.meta.get("res")
+    if res_built and abs(float(res_built) - float(cfg.res)) > 1e-9:
+        # the table's normals were estimated on clouds down-sampled at its res with radius 10 res: the scene's must be too
+        raise ValueError("the pair table was built at res = %g, the configuration has res = %g" % (res_built, cfg.res))
+    cap = _vote_cap(pcs, cfg)
+    hypotheses, centre_peaks = _hypothesis_args(hypotheses, centre_peaks)
+    pts = torch.from_numpy(np.concatenate(pcs)).to(dev)
+    pipe, _, _ = _pipelines(dev, Ns, num_pairs, k, cfg, num_rots, angle_tol, backproj_ratio, imp_wt_margin, cap, False)
+    idx = torch.cat([ops.sample_tuples(n, num_pairs, k, seed, (s,), dev) for s, n in zip(scene_ids, Ns)])
+    u = torch.cat([ops.philox_uniform(num_pairs, 6, seed, 1, (s,), dev) for s in scene_ids])
+    normal = ops.nan_to_zero_(shot.normals_device(pts, pipe.pt_off, cfg.res * 10))
+    pipe.use_slot(0)
+    table.vote(pipe, pts, normal, idx, u, **(dict(centre_peaks=centre_peaks) if centre_peaks > 1 else {}))
+    hits = table.last_hits
+    hyps = centre_hyps = None
+    if hypotheses is not None:
+        hyps, centre_hyps = _pass_hypotheses(pipe, hypotheses, centre_peaks, up_sym)
+    if opt:
+        pipe.refine(pts, idx, up_sym)
+    pipe.alignment_loss(pts, idx, up_sym)
+    pipe.select(True, False)
+    rec = pipe.results_to_numpy(pipe.result_slots[0])
+    out = _pass_output(pipe, [rec, rec], idx, pts, hypotheses, [hyps, hyps], [centre_hyps, centre_hyps],
+                       [pipe.centre_n] * 2 if centre_hyps is not None else [None, None])
+    out["losses"] = out["losses"].copy()
+    out["losses"][1] = np.inf                       # there is no second pass
+    out["table_hits"] = hits.cpu().numpy().astype(np.int64)
     return out
 
 
@@ -637,19 +729,23 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
              num_pairs=50000, num_rots=180, opt=True, geo_branch=True, visual_branch=True, seed=0, batch_instances=16,
              icp_iters=0, hypotheses=1, verify_tau=None, teacher_prior=False, visib_gt_min=None, debug=False, out=None,
              centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False, mask_jump=None, icp_depth=False,
-             icp_model_weight=1.0):
+             icp_model_weight=1.0, pair_tables=None):
     """The instance-level path over one split of a BOP-format dataset (cppf2_amd.bop_data.Dataset): one estimate per valid
     ground-truth instance of every target, from its visible mask; poses written to `out_csv` in BOP's frame and scored with
     bop_data.score.  Instances of one object (and one K and image size) are evaluated in batches of `batch_instances` across
     images.  detections: a detections file (bop_data.read_detections); every detection of a target's object in its image with
     score >= det_score_min then stands where the ground-truth instances stood, its mask decoded on the GPU (masks.decode_batch,
     one call per target), and gives one CSV row (score: the detection's, times the verification score with hypotheses > 1).
+    pair_tables: a folder of obj_%06d.npz pair-feature tables (python -m cppf2_amd.pair_table): each object's instances are then
+    voted from its table (run_table) instead of the two model passes; no prior.
     clean_masks: every mask is cut down to its largest depth-connected component (masks.clean, mask_jump metres) before
     back-projection and verification.  Returns the report (report["bop"] = bop_data.score's)."""
     import time
     from cppf2_amd import bop, bop_data, icp, masks, verify
     dev = ops._dev()
     cfg, dino_model, shot_model = setup
+    if pair_tables and teacher_prior:
+        raise ValueError("--pair_tables votes from the tables: it cannot be combined with --teacher_prior")
     up_sym = bool(cfg.get("up_sym", False))
     vmin = bop_data.VISIB_GT_MIN if visib_gt_min is None else float(visib_gt_min)
     ds = bop_data.Dataset(bop_root, split, mesh_scale)
@@ -682,6 +778,7 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
             else:
                 dets.setdefault(key, []).append(dict(det, index=n_))
     gid = [0]
+    enabled = (True, False) if pair_tables else (geo_branch, visual_branch)
 
     def flush(key):
         chunk, pending[key] = pending.get(key, []), []
@@ -692,7 +789,7 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
         obj = ds.object(o)
         B = len(chunk)
         descs = []
-        for c_ in chunk:                            # DINOv2 features are inputs to the path (weights absent): seeded unit vectors
+        for c_ in ([] if pair_tables else chunk):   # DINOv2 features are inputs to the path (weights absent): seeded unit vectors
             gen = torch.Generator(device="cpu").manual_seed(seed * 7919 + c_["gid"] + 1)
             descs.append(torch.nn.functional.normalize(torch.randn((c_["pc"].shape[0], 1024), generator=gen), dim=-1).numpy())
         priors = scale_priors = None
@@ -703,16 +800,21 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
             canon = [((c_["pc"].astype(np.float64) - c_["gt"]["t"]) @ c_["gt"]["R"] / diag).astype(np.float32) for c_ in chunk]
             priors = _teacher_prior(np.concatenate(canon), dev)
             scale_priors = np.stack([ext] * B)
-        r = run_ensemble(cfg, dino_model, shot_model, [c_["pc"] for c_ in chunk], descs, seed, [c_["gid"] for c_ in chunk],
-                         num_pairs, num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
-                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if hypotheses > 1 else None,
-                         centre_peaks=centre_peaks)
+        if pair_tables:
+            r = run_table(cfg, load_pair_table(os.path.join(str(pair_tables), "obj_%06d.npz" % o), dev), [c_["pc"] for c_ in chunk],
+                          seed, [c_["gid"] for c_ in chunk], num_pairs, num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt),
+                          up_sym, hypotheses if hypotheses > 1 else None, centre_peaks)
+        else:
+            r = run_ensemble(cfg, dino_model, shot_model, [c_["pc"] for c_ in chunk], descs, seed, [c_["gid"] for c_ in chunk],
+                             num_pairs, num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
+                             up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if hypotheses > 1 else None,
+                             centre_peaks=centre_peaks)
         pt_off = np.cumsum([0] + [c_["pc"].shape[0] for c_ in chunk])
         ver = icp_stats = None
         if icp_iters > 0 and o not in icp_models:
             icp_models[o] = icp.ModelPoints.from_mesh(ds.mesh(o))
         if hypotheses > 1:
-            ver = _verify_instances(r, B, hypotheses, (geo_branch, visual_branch), obj, np.stack([c_["depth"] for c_ in chunk]),
+            ver = _verify_instances(r, B, hypotheses, enabled, obj, np.stack([c_["depth"] for c_ in chunk]),
                                     np.stack([c_["mask"] for c_ in chunk]), chunk[0]["K"], pt_off, icp_models.get(o), icp_iters,
                                     verify_tau, icp_depth, icp_model_weight)
             if icp_iters > 0:
@@ -750,7 +852,9 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
                                      obj.centre)
             if dets is not None:
                 score = c_["det"]["score"] * score if ver is not None else c_["det"]["score"]
-            item.update(model=["dino", "shot"][r["pick"][b]], loss=float(r["best"][b]), score=score)
+            item.update(model="table" if pair_tables else ["dino", "shot"][r["pick"][b]], loss=float(r["best"][b]), score=score)
+            if pair_tables:
+                item["table_hits"] = [int(x) for x in r["table_hits"][b]]
             rows.append(dict(scene_id=c_["scene_id"], im_id=c_["im_id"], obj_id=o, score=score, R=Rb, t=tb))
 
     def candidates(s_id, im, o, info, gts, depth):
@@ -834,6 +938,8 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
     report = dict(data="bop", bop_root=str(bop_root), split=str(split), targets=len(tlist), instances=len(summary), rows=len(rows),
                   skipped=skipped, out_csv=str(out_csv), teacher_prior=bool(teacher_prior),
                   opt_refinement="100 Adam steps (cppf_refine_pose)" if opt else "off", bop=scored, results=summary)
+    if pair_tables:
+        report.update(pair_tables=str(pair_tables), table_hits=[s_.get("table_hits") for s_ in summary])
     if dets is not None:
         report.update(detections=n_detections, detections_file=str(detections), det_score_min=float(det_score_min))
     if clean_masks:
@@ -887,8 +993,20 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
          models_info=None, hypotheses=1, verify_tau=None, bop_root=None, split="test", targets=None, out_csv=None,
          teacher_prior=False, model_scale=0.001, centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False,
-         clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0):
+         clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0, pair_table=None, pair_tables=None):
     custom = False
+    if pair_table or pair_tables:
+        # a known object's pair-feature table stands where the two models stood (run_table): no prior, no checkpoints
+        flag = "--pair_table" if pair_table else "--pair_tables"
+        if pair_table and data != "depth":
+            raise ValueError("--pair_table is the table of the one object of --data=depth (--data=bop: --pair_tables=<dir>); "
+                             "the synthetic and NOCS modes have no table")
+        if pair_tables and data != "bop":
+            raise ValueError("--pair_tables is a folder of obj_%06d.npz tables for --data=bop (--data=depth: --pair_table=<npz>)")
+        if teacher_prior:
+            raise ValueError("%s votes from the table: it cannot be combined with --teacher_prior" % flag)
+        if ckpt_dir or ckpt_shot or ckpt_dino:
+            raise ValueError("%s votes from the table: it cannot be combined with --ckpt_*" % flag)
     if data in ("depth", "bop"):
         icp_depth, icp_model_weight = _icp_depth_flag(icp_depth, icp_model_weight, icp_iters)
     elif icp_depth:
@@ -907,11 +1025,11 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
             raise ValueError("--data=bop takes the models and the true poses from the dataset: --mesh and --gt_pose belong to --data=depth")
         dev = ops._dev()
         torch.manual_seed(seed)
-        return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev), bop_root, split, out_csv, targets,
+        return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev, models=not pair_tables), bop_root, split, out_csv, targets,
                         float(model_scale), angle_tol, imp_wt_margin, backproj_ratio,
                         num_pairs, num_rots, opt, geo_branch, visual_branch, seed, batch_instances, int(icp_iters), int(hypotheses),
                         verify_tau, bool(teacher_prior), None, debug, out, centre_peaks, detections, float(det_score_min), clean_masks,
-                        mask_jump, icp_depth, icp_model_weight)
+                        mask_jump, icp_depth, icp_model_weight, pair_tables)
     if detections is not None:
         raise ValueError("--detections is a BOP detections file: it needs --data=bop")
     if clean_masks and data != "depth":
@@ -964,7 +1082,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
     torch.manual_seed(seed)
     # eval.py:84-101: models and cfgs of every category up front
     if custom:
-        setups = {"custom": load_custom(ckpt_shot, ckpt_dino, device=dev)}
+        setups = {"custom": load_custom(ckpt_shot, ckpt_dino, device=dev, models=not pair_table)}
     else:
         setups = {c: load_category(c, ckpt_dir, ckpt_shot, ckpt_dino, device=dev) for c in categories}
     if data == "nocs":
@@ -1012,20 +1130,25 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         # DINOv2 features are inputs to the path (weights absent): seeded unit vectors stand in for them
         g = torch.Generator(device="cpu").manual_seed(seed + 1 + ci)
         descs = [torch.nn.functional.normalize(torch.randn((s["pc"].shape[0], 1024), generator=g), dim=-1).numpy()
-                 for s in scenes]
+                 for s in ([] if pair_table else scenes)]          # (a table pass reads no descriptor)
         priors = scale_priors = None
         if scenes[0]["pc_canon"] is not None:
             priors = _teacher_prior(np.concatenate([s["pc_canon"] for s in scenes]), dev)
             scale_priors = np.stack([s["extent"] for s in scenes])
-        r = run_ensemble(cfg, dino_model, shot_model, [s["pc"] for s in scenes], descs, seed, scene_ids, num_pairs,
-                         num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
-                         up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if verify_obj is not None else None,
-                         centre_peaks=centre_peaks)
+        if pair_table:
+            r = run_table(cfg, load_pair_table(pair_table, dev), [s["pc"] for s in scenes], seed, scene_ids, num_pairs, num_rots,
+                          angle_tol, imp_wt_margin, backproj_ratio, bool(opt), up_sym,
+                          hypotheses if verify_obj is not None else None, centre_peaks)
+        else:
+            r = run_ensemble(cfg, dino_model, shot_model, [s["pc"] for s in scenes], descs, seed, scene_ids, num_pairs,
+                             num_rots, angle_tol, imp_wt_margin, backproj_ratio, bool(opt), geo_branch, visual_branch,
+                             up_sym, priors, scale_priors=scale_priors, hypotheses=hypotheses if verify_obj is not None else None,
+                             centre_peaks=centre_peaks)
         cls_id = category2id.get(cat, 0)
         icp_stats = None
         ver = None
         if verify_obj is not None:
-            ver = _verify_instances(r, B, hypotheses, (geo_branch, visual_branch), verify_obj, d, m, K,
+            ver = _verify_instances(r, B, hypotheses, (True, False) if pair_table else (geo_branch, visual_branch), verify_obj, d, m, K,
                                     np.cumsum([0] + [s["pc"].shape[0] for s in scenes]), icp_model, icp_iters, verify_tau,
                                     icp_depth, icp_model_weight)
             if icp_model is not None:
@@ -1046,7 +1169,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                 RT[:3, 3] = rec["t"]
                 if r["scale_norm"][b] > 0:
                     sc = r["scale"][b] / r["scale_norm"][b]
-                item.update(model=["dino", "shot"][r["pick"][b]], loss=float(r["best"][b]),
+                item.update(model="table" if pair_table else ["dino", "shot"][r["pick"][b]], loss=float(r["best"][b]),
                             losses=[float(r["losses"][0][b]), float(r["losses"][1][b])], pred_RT=RT.tolist(),
                             pred_scale=sc.tolist())
                 if icp_stats is not None:
@@ -1060,6 +1183,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                 if scenes[b]["R"] is not None:
                     item["tr_err_cm"] = float(np.linalg.norm(rec["t"] - scenes[b]["t"]) * 100)
                     item["rot_err_deg"] = geometry.rot_err_deg(rec["R"], scenes[b]["R"], up_sym)
+            if pair_table:
+                item["table_hits"] = [int(x) for x in r["table_hits"][b]]
             summary.append(item)
             all_cls.append(cls_id); all_RT.append(RT); all_scale.append(sc)
             if scenes[b]["R"] is not None:
@@ -1102,6 +1227,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
 
     report = dict(categories=categories, instances=len(summary),
                   opt_refinement="100 Adam steps (cppf_refine_pose)" if opt else "off", results=summary)
+    if pair_table:
+        report.update(pair_table=str(pair_table), table_hits=[s_["table_hits"] for s_ in summary])
     if clean_masks:
         report["mask_cleaning"] = dict(components=mask_stats[0], kept_pixels=mask_stats[2], valid_pixels=mask_stats[3])
     if icp_model is not None:

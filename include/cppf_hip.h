@@ -611,6 +611,33 @@ int cppf_decode_from_bins(int B, const int32_t* bins, int nb, const float* pts, 
                           const int32_t* pt_off, const int32_t* tup_off, int64_t total_tuples, const double* h_axes,
                           float* scaled, float* scale, float* tr, float* rot, void* stream);
 
+/* ---- pair-feature tables (not in the reference): for a known rigid object the six bins of a tuple are
+ * looked up from the point-pair feature of its first two points instead of drawn from an MLP's logits.  All arithmetic is
+ * float32 in the written order, no transcendental on the device.
+ * Key of tuple t, i0 / i1 its first two indices: d = p1 - p0, len = sqrtf((dx*dx + dy*dy) + dz*dz),
+ * c1 = ((n0x*dx + n0y*dy) + n0z*dz) / len, c2 the same with n1, c3 = (n0x*n1x + n0y*n1y) + n0z*n1z; key = -1 if len == 0,
+ * !(len < nd * d_step), a normal is all zero or an input is not finite; else bd = min((int)(len / d_step), nd - 1),
+ * a(c) = #{j in 1..na-1 : c < edges[j]} with edges float32 [na + 1], edges[j] = float32(cos(j pi / na)) filled by the caller,
+ * key = ((bd*na + a1)*na + a2)*na + a3.  nd >= 1, 2 <= na <= 1024, nd * na^3 < INT32_MAX, d_step > 0.
+ * cppf_pair_keys: keys_out int32 [T]; with canon (float32 [total_points, 3], the canonical coordinates of the points) also
+ * payload_out uint8 [T, 8] (8-byte aligned): q(x) = (int)floorf((fminf(fmaxf(x, -0.5f), 0.5f) + 0.5f) * (nb - 1) + 0.5f) of the
+ * three coordinates of point i0 then of i1, then two zero bytes; 2 <= nb <= 256.  canon and payload_out are both given or both
+ * null. */
+int cppf_pair_keys(int B, const float* pts, const float* normals, const float* canon, const int32_t* idx, int k,
+                   const int32_t* pt_off, const int32_t* tup_off, int64_t total_tuples, int nd, float d_step, int na,
+                   const float* edges, int nb, int32_t* keys_out, uint8_t* payload_out, void* stream);
+/* cppf_pair_table_draw: cell_off int32 [nd*na^3 + 1] (exclusive prefix of the entries per cell), entries uint8 [E, 8] (8-byte
+ * aligned, 0 < E <= INT32_MAX), uniforms float32 [T, 6] in [0, 1) (column 0 is read), bins_out int32 [T, 6], hits int32 [B, 3]
+ * zeroed by the caller.  Per tuple the range of entries is, in this order: (source 0) its own cell if the key is valid and
+ * the cell non-empty; (source 1) for a valid key with an empty cell the first non-empty cell among those at bd-1, bd+1, a1-1,
+ * a1+1, a2-1, a2+1, a3-1, a3+1 (out-of-range ones skipped); (source 2) the whole table.  Entry
+ * start + min((int)(u0 * (float)n), n - 1) gives the six bins; hits[b, source] counts scene b's tuples exactly (integer
+ * atomics: no result depends on the launch order). */
+int cppf_pair_table_draw(int B, const float* pts, const float* normals, const int32_t* idx, int k, const int32_t* pt_off,
+                         const int32_t* tup_off, int64_t total_tuples, int nd, float d_step, int na, const float* edges,
+                         const int32_t* cell_off, const uint8_t* entries, int64_t E, const float* uniforms, int32_t* bins_out,
+                         int32_t* hits, void* stream);
+
 /* Batch mode (two HIP streams working on different batches): the cppf_reslayer_split* launches are
  * persistent -- one workgroup per CU holding the CU's whole register file -- so while one runs, no kernel of another stream
  * can start anywhere on the chip.  cppf_mlp_reserve_cus(n) makes every later launch of this process use n fewer CUs (never
