@@ -48,6 +48,9 @@ extern thread_local char g_cppf_err[256];
     if (rc_ != CPPF_OK) return rc_;                                                           \
   } while (0)
 
+// x rounded up to a multiple of a (workspace offsets and sizes; x >= 0)
+static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
 // Per-device facts of the launches, queried on first use and cached (written once under a lock -- the library keeps no
 // other state, see cppf_hip.h); both return CPPF_OK or CPPF_EHIP.  cppf_device_cus: the current device and its CU count.
 // cppf_allow_dynamic_lds: lets `kernel` use `bytes` of dynamic LDS on device `dev` (above 64 KiB it must be declared), set
@@ -278,6 +281,27 @@ __device__ __forceinline__ double wave_sum(double v) {
         __longlong_as_double((long long)(((unsigned long long)h[1] << 32) | l[1]));
   }
   return v;
+}
+// block_scan_flag: exclusive scan of one flag per thread over a workgroup of BV_THREADS (the back-vote filter's compaction,
+// vr_scan_kernel's ranks); returns this thread's offset, *total = block sum.  s_wave: BV_THREADS / 64 ints of LDS.
+#ifndef BV_THREADS
+#define BV_THREADS 1024
+#endif
+__device__ __forceinline__ int block_scan_flag(bool flag, int* s_wave, int* total) {
+  const unsigned long long m = __ballot(flag);
+  const int lane = wave_lane(), w = threadIdx.x >> 6;
+  const int within = __popcll(m & ((1ull << lane) - 1ull));
+  if (lane == 0) s_wave[w] = __popcll(m);
+  __syncthreads();
+  int base = 0, tot = 0;
+  for (int i = 0; i < BV_THREADS / 64; ++i) {
+    const int c = s_wave[i];
+    if (i < w) base += c;
+    tot += c;
+  }
+  __syncthreads();
+  *total = tot;
+  return base + within;
 }
 // sqrt_rn: correctly rounded float32 square root of a positive NORMAL finite x (the rounding step of the compiler's own
 // expansion -- the hardware root is within 1 ulp; pick the neighbour whose residual says so -- without its denormal

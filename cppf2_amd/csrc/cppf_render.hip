@@ -229,8 +229,6 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_raster_kernel(const Ren
   }
 }
 
-static inline int64_t render_align(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 struct RenderLayout {
   int64_t rec, bin, count, start, list, bytes;
 };
@@ -241,11 +239,11 @@ static bool render_layout(int B, int64_t total, int H, int W, int64_t cap, Rende
     return false;
   const int64_t tiles = (int64_t)B * ((W + RENDER_TILE - 1) / RENDER_TILE) * ((H + RENDER_TILE - 1) / RENDER_TILE);
   L->rec = 0;
-  L->bin = L->rec + render_align(total * (int64_t)sizeof(RenderRec));
-  L->count = L->bin + render_align(total * (int64_t)sizeof(RenderBin));
-  L->start = L->count + render_align(tiles * 4);
-  L->list = L->start + render_align((tiles + 1) * 8);
-  L->bytes = L->list + render_align(cap * 4);
+  L->bin = L->rec + align_up(total * (int64_t)sizeof(RenderRec), 256);
+  L->count = L->bin + align_up(total * (int64_t)sizeof(RenderBin), 256);
+  L->start = L->count + align_up(tiles * 4, 256);
+  L->list = L->start + align_up((tiles + 1) * 8, 256);
+  L->bytes = L->list + align_up(cap * 4, 256);
   return true;
 }
 

@@ -1349,8 +1349,6 @@ __global__ __launch_bounds__(64) void shot_hist_kernel(int B, const float* __res
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static inline int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
-
 // Byte offsets of the workspace, shared by every entry point.  The colour form appends two float4 Lab tables (the caller's order,
 // the cell-sorted order) to the 352 layout.
 struct ShotLayout {
@@ -1360,18 +1358,18 @@ struct ShotLayout {
 static ShotLayout shot_layout(int B, int64_t n, bool color) {
   ShotLayout L;
   L.hdr = 0;
-  L.cell_start = L.hdr + up256((int64_t)B * sizeof(CellHdr));
-  L.sorted_idx = L.cell_start + up256((int64_t)B * (CELL_CAP + 1) * 4);
-  L.sorted_pts = L.sorted_idx + up256(n * 4);
-  L.sums = L.sorted_pts + up256(n * 16);
-  L.pre = L.sums + up256(n * NSUM * 8);
-  L.scene_of = L.pre + up256(n * (int64_t)sizeof(LrfPre));
-  L.sorted_nrm = L.scene_of + up256(n * 4);
-  L.nbr_cnt = L.sorted_nrm + up256(n * 16) + 256;                     // one slot before the counts: the lists' radius
-  L.nbr_list = L.nbr_cnt - 256 + up256(n * 4 + 256);
-  L.lab = L.nbr_list + up256(n * (int64_t)NBR_CAP * 4);
-  L.sorted_lab = L.lab + (color ? up256(n * 16) : 0);
-  L.bytes = L.sorted_lab + (color ? up256(n * 16) : 0);
+  L.cell_start = L.hdr + align_up((int64_t)B * sizeof(CellHdr), 256);
+  L.sorted_idx = L.cell_start + align_up((int64_t)B * (CELL_CAP + 1) * 4, 256);
+  L.sorted_pts = L.sorted_idx + align_up(n * 4, 256);
+  L.sums = L.sorted_pts + align_up(n * 16, 256);
+  L.pre = L.sums + align_up(n * NSUM * 8, 256);
+  L.scene_of = L.pre + align_up(n * (int64_t)sizeof(LrfPre), 256);
+  L.sorted_nrm = L.scene_of + align_up(n * 4, 256);
+  L.nbr_cnt = L.sorted_nrm + align_up(n * 16, 256) + 256;           // one slot before the counts: the lists' radius
+  L.nbr_list = L.nbr_cnt - 256 + align_up(n * 4 + 256, 256);
+  L.lab = L.nbr_list + align_up(n * (int64_t)NBR_CAP * 4, 256);
+  L.sorted_lab = L.lab + (color ? align_up(n * 16, 256) : 0);
+  L.bytes = L.sorted_lab + (color ? align_up(n * 16, 256) : 0);
   return L;
 }
 

@@ -487,6 +487,60 @@ def test_stage_workspace_bytes_are_pinned():
         assert lib.cppf_vote_center_workspace_bytes(B, cells, T) == want, (B, cells, T)
 
 
+# Workspace sizes of the post-vote stages, recorded from the library as it was built while they shared one source file with the
+# centre vote (cppf_vote_center's are above).
+# (B, S, max_kept, num_rots, bmm_size) -> cppf_rot_bins_workspace_bytes.  The lookup-table path's partials are never smaller than
+# the dense path's sums (2 * nchunks * sub >= nchunks + 1 slots per scene): "dense wins" is at most a tie, one chunk and one sub-block.
+_RB_WORKSPACE_BYTES = {
+    (0, 720, 100, 180, 100000): 0, (2, 0, 100, 180, 100000): 0, (2, 720, -1, 180, 100000): 0, (2, 720, 100, 0, 100000): 0,
+    (2, 720, 100, 180, 0): 0,                                                              # each rejected argument
+    (2, 720, 0, 180, 100000): 414720, (64, 720, 0, 180, 100000): 2949120,                  # nothing kept
+    (15, 720, 2000, 180, 100000): 12441600, (16, 720, 2000, 180, 100000): 2949120,         # 32- and 160-pair row blocks
+    (2, 720, 2000, 180, 5760): 1451520, (2, 720, 2000, 180, 5761): 2903040,                # block target >= and < bmm_size
+    (16, 64, 50, 8, 1280): 16384, (16, 64, 50, 8, 1281): 32768,
+    (2, 64, 9, 8, 8): 18432, (2, 64, 9, 8, 4): 36864,                                      # num_rots == bmm_size, and above it
+    (2, 720, 10, 180, 2000): 23040,                                                        # the tie: dense == lookup-table
+    (2, 720, 100, 180, 100000): 414720,                                                    # the lookup-table size wins
+    (64, 720, 20000, 180, 100000): 106168320,                                              # the benchmark's own
+    (2, 64, 0, 8, 32): 2048, (2, 64, 1, 8, 32): 2048, (2, 64, 9, 8, 32): 6144,
+    (1, 1, 1, 1, 1): 256, (1, 32767, 100000, 1024, 1048576): 1644116992, (3, 721, 50000, 180, 100000): 56065024,
+}
+# (total_points, B) -> cppf_backvote_workspace_bytes
+_BV_WORKSPACE_BYTES = {(0, 1): 0, (1, 1): 256, (63, 4): 256, (64, 4): 256, (65, 4): 512, (100000, 64): 400128, (1 << 31, 1): 8589934592}
+# (B, K) -> cppf_grid_peaks_workspace_bytes
+_GP_WORKSPACE_BYTES = {(0, 4): 0, (-1, 4): 0, (4, 0): 0, (4, 17): 0, (1, 1): 256, (1, 16): 256, (4, 5): 256, (32, 1): 256, (33, 1): 512,
+                       (64, 16): 8192, (65535, 16): 8388608}
+
+
+def test_post_vote_workspace_bytes_are_pinned():
+    lib = _untraced_lib()
+    for args, want in _RB_WORKSPACE_BYTES.items():
+        assert lib.cppf_rot_bins_workspace_bytes(*args) == want, args
+    for args, want in _BV_WORKSPACE_BYTES.items():
+        assert lib.cppf_backvote_workspace_bytes(*args) == want, args
+    for args, want in _GP_WORKSPACE_BYTES.items():
+        assert lib.cppf_grid_peaks_workspace_bytes(*args) == want, args
+
+
+def test_rot_bins_refuses_chunks_shorter_than_one_pair_before_any_device_work():
+    """Validation order of cppf_rot_bins / cppf_rot_bins2: arguments, then the workspace size, then num_rots > bmm_size."""
+    lib = _untraced_lib()
+
+    def call(nax, bmm_size, short=0, num_rots=8, sphere=_AUX):
+        need = lib.cppf_rot_bins_workspace_bytes(2, 64, 9, num_rots, bmm_size) - short
+        cols = (0, 2) if nax == 2 else (0,)
+        return (lib.cppf_rot_bins2 if nax == 2 else lib.cppf_rot_bins)(
+            2, _X, _AUX, _IDX, 5, _AUX2, _B1, *cols, _IDX, _AUX, _B0, _AUX2, 9, num_rots, _TAB, _TAP, sphere, 64, 0.9, bmm_size, None,
+            0, 0, _OUT, None, None, _WQ, need, None)
+
+    for nax in (1, 2):
+        assert call(nax, 4) == _EUNSUPPORTED
+        assert lib.cppf_last_error_string() == b"cppf_rot_bins: bmm_size 4 < num_rots 8 unsupported"
+        assert call(nax, 4, short=1) == _EINVAL
+        assert call(nax, 4, sphere=None) == _EINVAL
+        assert call(nax, 32, num_rots=1025) == _EINVAL
+
+
 _SHOT_PARAMS = {
     "cppf_estimate_normals": ("B", "pts", "pt_off", "n", "normal_r", "out_normal", "ws", "ws_bytes", "flags", "stream"),
     "cppf_shot352": ("B", "pts", "pt_off", "n", "normal_r", "shot_r", "out_shot", "out_normal", "out_rf", "ws", "ws_bytes", "flags",

@@ -567,3 +567,105 @@ def test_vote_center_slab_cut_random_batches(cfg_seed):
     assert out[1][3].max() <= 1 << 21 and out[1][0].min() >= 0 and out[1][0].sum() > 0
     assert np.array_equal(out[1][0], out[2][0]), cfg_seed
     assert np.array_equal(out[1][1], out[2][1]) and np.array_equal(out[1][2], out[2][2]), cfg_seed
+
+
+def test_kept_rows_padding_rule_in_both_widths():
+    """cppf_kept_rows and cppf_kept_rows32 (one kernel, two row types) on scenes with 0, 1 and 5 tuples: exact against the padding
+    rule restated in NumPy, the two widths equal element for element, and max_kept = 0 returns OK without writing."""
+    from cppf2_amd import _lib
+    L = _lib.load()
+    B, max_kept = 3, 4
+    tup_off = np.array([0, 0, 1, 6], np.int32)
+    kept_tuple = np.array([0, 4, 0, 2, 3, 1], np.int32)            # scene 1: tuple 0; scene 2: tuples 4, 0, 2 (then unused entries)
+    kept_count = np.array([0, 1, 3], np.int32)
+    want = np.zeros((B, max_kept), np.int64)
+    for b in range(B):
+        t0, t1, n = tup_off[b], tup_off[b + 1], kept_count[b]
+        want[b] = t0 if t0 < t1 else 0                             # padding: the scene's first row, row 0 without tuples
+        want[b, :n] = t0 + kept_tuple[t0:t0 + n]
+    d = [torch.from_numpy(a).to(DEV) for a in (tup_off, kept_tuple, kept_count)]
+    for m in (max_kept, 0):
+        r64 = torch.full((B * max_kept,), -7, dtype=torch.int64, device=DEV)
+        r32 = torch.full((B * max_kept,), -7, dtype=torch.int32, device=DEV)
+        assert L.cppf_kept_rows(B, ops._p(d[0]), ops._p(d[1]), ops._p(d[2]), m, ops._p(r64), ops._stream()) == 0
+        assert L.cppf_kept_rows32(B, ops._p(d[0]), ops._p(d[1]), ops._p(d[2]), m, ops._p(r32), ops._stream()) == 0
+        exp = want.reshape(-1) if m else np.full(B * max_kept, -7, np.int64)
+        assert np.array_equal(r64.cpu().numpy(), exp), m
+        assert r32.cpu().numpy().dtype == np.int32 and np.array_equal(r32.cpu().numpy(), exp), m
+
+
+@pytest.mark.parametrize("max_kept", [0, 1, 9])
+def test_rot_bins_small_plan_equals_sphere_counts_on_explicit_candidates(max_kept):
+    """cppf_rot_bins / cppf_rot_bins2 called directly at B = 2, S = 64, 8 rotations, chunks of 32 rows: up to three chunks, and
+    (a degenerate pair shifts the rows) a dense block whose rows span two.  The dense and the lookup-table path each equal
+    cppf_sphere_counts on cppf_vote_rotation's explicit candidates bit for bit -- the pair weights are powers of two, so every
+    float64 sum is exact whatever order the atomics arrive in; the two-axis output is the two single-axis ones, axis-major; and
+    chunks shorter than one pair's rotations are refused."""
+    import ctypes as C
+    from cppf2_amd import _lib
+    L = _lib.load()
+    B, S, R, bmm, N, T = 2, 64, 8, 32, 12, 14
+    rng = np.random.RandomState(7)
+    pcs = rng.rand(B, N, 3).astype(np.float32)
+    idx = np.stack([rng.permutation(N)[:5] for _ in range(B * T)]).astype(np.int32)       # five distinct points per tuple
+    idx[3, 1] = idx[3, 0]                                                                  # scene 0, tuple 3: |ab| = 0
+    rot = rng.uniform(0.2, 1.3, (B * T, 3)).astype(np.float32)
+    kept_count = np.minimum([9, 5], max_kept).astype(np.int32)
+    kept_tuple = np.zeros(B * T, np.int32)
+    kept_wt = np.ones(B * T, np.float64)
+    kept_row0 = np.full(B * T, -1, np.int32)
+    for b in range(B):
+        pool = rng.permutation(T)
+        if b == 0:                                                                         # the degenerate pair is kept among nine, not alone
+            pool = np.concatenate([[3], pool[pool != 3]]) if max_kept == 9 else pool[pool != 3]
+        sel = np.sort(pool[:kept_count[b]])
+        kept_tuple[b * T:b * T + len(sel)] = sel
+        kept_wt[b * T:b * T + len(sel)] = 2.0 ** rng.randint(-1, 3, len(sel))
+        ok = idx[b * T + sel, 0] != idx[b * T + sel, 1]
+        kept_row0[b * T:b * T + len(sel)] = np.where(ok, (np.cumsum(ok) - ok) * R, -1)
+    sphere = np.array(ops.fibonacci_sphere(S), np.float32)
+    tol = 10.0
+    cos_thr = ops.cone_threshold(tol)
+    lut = ops.bin_lut_device(sphere, cos_thr, DEV)
+    assert lut is not None
+    cs, sn = ops.rotation_table(R, DEV)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    d_pts, d_idx, d_rot, d_sph = t(pcs.reshape(-1, 3)), t(idx), t(rot), t(sphere)
+    d_pt_off, d_tup_off = t(np.arange(B + 1, dtype=np.int32) * N), t(np.arange(B + 1, dtype=np.int32) * T)
+    d_kt, d_kc, d_kw, d_k0 = t(kept_tuple), t(kept_count), t(kept_wt), t(kept_row0)
+    need = lambda bmm_size: L.cppf_rot_bins_workspace_bytes(B, S, max_kept, R, bmm_size)
+    ws = torch.empty(max(need(bmm), need(4)), dtype=torch.uint8, device=DEV)
+
+    def call(nax, cols, use_lut, bmm_size=bmm):
+        counts = torch.full((nax, B, S), -1.0, device=DEV)
+        top_idx = torch.full((nax, B), -1, dtype=torch.int32, device=DEV)
+        top_cnt = torch.full((nax, B), -1.0, device=DEV)
+        head = (B, ops._p(d_pts), ops._p(d_pt_off), ops._p(d_idx), 5, ops._p(d_tup_off), ops._p(d_rot)) + tuple(cols)
+        tail = (ops._p(d_kt), ops._p(d_kc), ops._p(d_kw), ops._p(d_k0), max_kept, R, ops._p(cs), ops._p(sn), ops._p(d_sph), S,
+                C.c_float(cos_thr), bmm_size, ops._p(lut if use_lut else None), ops.LUT_ROWS, ops.LUT_COLS, ops._p(counts),
+                ops._p(top_idx), ops._p(top_cnt), ops._p(ws), need(bmm_size), ops._stream())
+        rc = (L.cppf_rot_bins2 if nax == 2 else L.cppf_rot_bins)(*(head + tail))
+        return rc, counts.cpu().numpy(), top_idx.cpu().numpy(), top_cnt.cpu().numpy()
+
+    # the reference: explicit candidates of each scene's kept pairs, counted chunk by chunk
+    want = np.zeros((2, B, S), np.float32)
+    for a, col in enumerate((0, 2)):
+        for b in range(B):
+            if kept_count[b] == 0:
+                continue                                                # no candidates: zero counts
+            sel = b * T + kept_tuple[b * T:b * T + kept_count[b]]
+            cand, valid = ops.vote_rotation(pcs[b], rot[sel, col], idx[sel, :2], R)
+            w = np.repeat(kept_wt[b * T:b * T + kept_count[b]][valid.cpu().numpy()], R)
+            assert cand.shape[0] == int((kept_row0[b * T:b * T + kept_count[b]] >= 0).sum())
+            want[a, b] = ops.sphere_counts(cand.reshape(-1, 3), sphere, bmm, tol, w).cpu().numpy()
+    if max_kept == 9:
+        assert want.max() > 0 and kept_row0[:9].max() == 7 * R         # 64 rows in scene 0: two full chunks, three sum slots
+    for use_lut in (False, True):
+        rc, c2, i2, n2 = call(2, (0, 2), use_lut)
+        assert rc == 0 and np.array_equal(c2, want), use_lut
+        assert np.array_equal(i2, want.argmax(-1)) and np.array_equal(n2, want.max(-1)), use_lut
+        for a, col in enumerate((0, 2)):                                # axis-major: [a] of the two-axis output is one single-axis call
+            rc, c1, i1, n1 = call(1, (col,), use_lut)
+            assert rc == 0 and np.array_equal(c1[0], c2[a]) and np.array_equal(i1[0], i2[a]) and np.array_equal(n1[0], n2[a])
+    rc = call(2, (0, 2), True, bmm_size=4)[0]
+    assert rc == -2 and L.cppf_last_error_string() == b"cppf_rot_bins: bmm_size 4 < num_rots 8 unsupported"

@@ -1,4 +1,4 @@
-"""GPU checks of cppf_grid_peaks (cppf_vote.hip) against the NumPy restatement (tests/grid_peaks_ref.py): every output array is
+"""GPU checks of cppf_grid_peaks (cppf_vote_center.hip) against the NumPy restatement (tests/grid_peaks_ref.py): every output array is
 compared for exact equality (NaN-aware for the world coordinates of empty slots) on real vote grids written by cppf_vote_center
 and on constructed grids; a scene's peaks do not depend on the batch; K = 1 is cppf_vote_center's own first maximum."""
 import ctypes as C

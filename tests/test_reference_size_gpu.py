@@ -31,7 +31,7 @@ from cppf2_amd import _lib, ops                # noqa: E402
 from cppf2_amd.pipeline import RESULT_DTYPE, VotingPipeline   # noqa: E402
 from test_refine import RF_CACHED_PAIRS, _kept_problem   # noqa: E402
 
-ASM_STAGE = 4096            # cppf_vote.hip: kept pairs whose scale-head rows are staged in LDS for the median
+ASM_STAGE = 4096            # cppf_backvote.hip: kept pairs whose scale-head rows are staged in LDS for the median
 UP, RIGHT, FRONT = [0, 1, 0], [1, 0, 0], [0, 0, 1]
 DEV = torch.device("cuda")
 
