@@ -224,6 +224,8 @@ int cppf_grid_peaks(int B, const CppfSceneGrid* grids, const uint32_t* grid, con
  *   kept_count int32[B]; kept_wt float64 (imp_pair_wt, same layout as kept_tuple);
  *   kept_row0 int32 (first row of the pair in the flattened candidate list of vote_rotation, -1 if
  *   |ab| <= 1e-7, train_dino.py:223); back_errs float32[T] and thr float32[B] optional.
+ *   pts and tr must be finite: a NaN error makes np.percentile return NaN (nothing kept), while the kernel ranks NaN last
+ *   and returns a finite threshold.
  *   workspace: cppf_backvote_workspace_bytes(total_points) bytes. */
 int64_t cppf_backvote_workspace_bytes(int64_t total_points, int B);
 int cppf_backvote_filter(int B, const float* pts, const int32_t* pt_off, const int32_t* idx, int k,
