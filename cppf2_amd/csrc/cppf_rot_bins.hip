@@ -507,8 +507,9 @@ extern "C" int cppf_vote_rotation(const float* pts, int n_points, const int32_t*
                                   const float* rot_angle, int num_rots, const float* cos_tab, const float* sin_tab,
                                   float* up, uint8_t* valid, int32_t* n_valid, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
-  CPPF_CHECK_ARG(pts && idx && rot_angle && cos_tab && sin_tab && up && valid && n_valid && workspace);
+  CPPF_CHECK_ARG(pts && cos_tab && sin_tab && up && valid && n_valid && workspace);
   CPPF_CHECK_ARG(n_points > 0 && k >= 2 && T >= 0 && num_rots > 0 && workspace_bytes >= (int64_t)T * 4);
+  CPPF_CHECK_ARG(T == 0 || (idx && rot_angle));      // empty inputs have no address (an empty torch tensor's is NULL)
   hipStream_t st = (hipStream_t)stream;
   int32_t* rank = (int32_t*)workspace;
   hipLaunchKernelGGL(vr_scan_kernel, dim3(1), dim3(BV_THREADS), 0, st, pts, idx, k, T, valid, rank, n_valid);
@@ -556,7 +557,8 @@ __global__ __launch_bounds__(256) void sphere_counts_kernel(const float* __restr
 extern "C" int cppf_sphere_counts(const float* cand, int64_t M, const double* wt, const float* sphere, int S,
                                   float cos_thr, int bmm_size, float* counts, void* workspace, int64_t workspace_bytes,
                                   void* stream) {
-  CPPF_CHECK_ARG(cand && sphere && counts && workspace && S > 0 && bmm_size > 0 && M >= 0);
+  CPPF_CHECK_ARG(sphere && counts && workspace && S > 0 && bmm_size > 0 && M >= 0);
+  CPPF_CHECK_ARG(M == 0 || cand);                    // no candidates: zero counts
   const int nchunks = (int)((M + bmm_size - 1) / bmm_size);
   const int mc = nchunks > 0 ? nchunks : 1;
   CPPF_CHECK_ARG(workspace_bytes >= (int64_t)mc * S * 8);

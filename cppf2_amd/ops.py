@@ -830,7 +830,12 @@ def vote_rotation(pc, preds_rot, point_idxs, num_rots=36, trig=None):
 
 
 def sphere_counts(pred, sphere_pts, bmm_size, angle_tol, wt=None):
-    """The accumulation half of get_topk_dir (eval.py:41-45): float32 counts [S] on the device."""
+    """The accumulation half of get_topk_dir (eval.py:41-45): float32 counts [S] on the device.
+
+    wt: divisors [M] or [M, 1] (None = ones).  The kernel divides in float64, the dtype of the reference's imp_pair_wt; weights of
+    any other dtype are promoted to float64 first, whereas the reference would divide in the weights' own dtype.  The two agree
+    bit for bit where the quotients are exact (power-of-two weights), otherwise to the rounding of that narrower division.
+    No candidates (M = 0) give all-zero counts."""
     dev = _dev()
     cand = _t(pred, torch.float32, dev).reshape(-1, 3)
     sph = _t(sphere_pts, torch.float32, dev)

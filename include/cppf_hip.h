@@ -278,7 +278,8 @@ int cppf_kept_rows32(int B, const int32_t* tup_off, const int32_t* kept_tuple, c
 
 /* Stand-alone halves with the reference's own signatures (used by the drop-in wrappers):
  * vote_rotation -> up float32[n_valid, num_rots, 3] (valid pairs compacted in order), valid uint8[T];
- * get_topk_dir on explicit candidates float32[M,3] with weights float64[M] (NULL = ones). */
+ * get_topk_dir on explicit candidates float32[M,3] with weights float64[M] (NULL = ones).
+ * T = 0 and M = 0 are valid (n_valid = 0, nothing written to up; all counts 0); idx / rot_angle / cand may then be NULL. */
 int cppf_vote_rotation(const float* pts, int n_points, const int32_t* idx, int k, int T, const float* rot_angle,
                        int num_rots, const float* cos_tab, const float* sin_tab,
                        float* up, uint8_t* valid, int32_t* n_valid, void* workspace, int64_t workspace_bytes,

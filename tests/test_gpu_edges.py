@@ -648,7 +648,12 @@ def test_rot_bins_small_plan_equals_sphere_counts_on_explicit_candidates(max_kep
         return rc, counts.cpu().numpy(), top_idx.cpu().numpy(), top_cnt.cpu().numpy()
 
     # the reference: explicit candidates of each scene's kept pairs, counted chunk by chunk
+    # ... which is itself held to the oracle: the same counts from O.get_topk_dir on O.vote_rotation's candidates.  Those differ from
+    # the device's only through tanf (a few ulp), so a bin is compared unless an oracle candidate's cosine lies within 1e-5 of its
+    # cone edge.
     want = np.zeros((2, B, S), np.float32)
+    near_edge = np.zeros((2, B, S), bool)
+    trig = (cs.cpu().numpy(), sn.cpu().numpy())
     for a, col in enumerate((0, 2)):
         for b in range(B):
             if kept_count[b] == 0:
@@ -658,6 +663,13 @@ def test_rot_bins_small_plan_equals_sphere_counts_on_explicit_candidates(max_kep
             w = np.repeat(kept_wt[b * T:b * T + kept_count[b]][valid.cpu().numpy()], R)
             assert cand.shape[0] == int((kept_row0[b * T:b * T + kept_count[b]] >= 0).sum())
             want[a, b] = ops.sphere_counts(cand.reshape(-1, 3), sphere, bmm, tol, w).cpu().numpy()
+            o_cand, o_valid = O.vote_rotation(pcs[b], rot[sel, col], idx[sel, :2], R, trig=trig)
+            assert np.array_equal(o_valid, valid.cpu().numpy()) and o_cand.shape == tuple(cand.shape)
+            o_cand = o_cand.reshape(-1, 3)
+            o_counts = O.get_topk_dir(o_cand, sphere, bmm, tol, w[:, None], return_counts=True)[2]
+            near_edge[a, b] = (np.abs(O._dot3_fma(o_cand, sphere.T) - np.float32(cos_thr)) < 1e-5).any(0)
+            assert np.array_equal(want[a, b][~near_edge[a, b]], o_counts[~near_edge[a, b]]), (a, b)
+    assert near_edge.mean() < 0.05
     if max_kept == 9:
         assert want.max() > 0 and kept_row0[:9].max() == 7 * R         # 64 rows in scene 0: two full chunks, three sum slots
     for use_lut in (False, True):
