@@ -21,17 +21,19 @@ def vsd_counts(d_test, d_est, d_gt, K, delta, diameter, taus, near=0.0):
     f = dist_factor(dt.shape[0], dt.shape[1], K)
     Dt, De, Dg = dt.astype(np.float64) * f, de.astype(np.float64) * f, dg.astype(np.float64) * f
     delta = float(delta)
-    vg = (dg > 0) & ((Dg - Dt <= delta) | (dt == 0))
-    ve = ((de > 0) & ((De - Dt <= delta) | (dt == 0))) | (vg & (de > 0))
-    inter = vg & ve
-    diff = np.abs(Dg - De)
+    with np.errstate(invalid="ignore"):                  # inf - inf = NaN, which passes no comparison (as in the kernel)
+        vg = (dg > 0) & ((Dg - Dt <= delta) | (dt == 0))
+        ve = ((de > 0) & ((De - Dt <= delta) | (dt == 0))) | (vg & (de > 0))
+        inter = vg & ve
+        diff = np.abs(Dg - De)
     thr = np.asarray(taus, dtype=np.float32).astype(np.float64) * float(np.float32(diameter))
     out = [int(np.count_nonzero(vg | ve)), int(np.count_nonzero(inter))]
     close = 0
     for t in thr:
         out.append(int(np.count_nonzero(inter & (diff >= t))))
         if near:
-            close += int(np.count_nonzero(inter & (np.abs(diff - t) <= near * t)))
+            with np.errstate(invalid="ignore"):
+                close += int(np.count_nonzero(inter & (np.abs(diff - t) <= near * t)))
     return np.array(out, dtype=np.int64), close
 
 

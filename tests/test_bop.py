@@ -232,3 +232,38 @@ def test_restatement_on_hand_built_depth_maps():
     # the distance conversion: a pixel off the principal point sees a longer ray than its depth
     f = BR.dist_factor(H, W, K_)
     assert f[12, 16] == 1.0 and f[0, 0] == np.sqrt((16 / 30.0) ** 2 + (12 / 30.0) ** 2 + 1)
+
+
+UNIT_K = np.array([[2.0 ** 40, 0, 0], [0, 2.0 ** 40, 0], [0, 0, 1]])      # dist_factor = 1 exactly: D = d
+
+
+def test_dist_factor_is_one_under_the_unit_k_and_at_the_principal_point_only():
+    assert (BR.dist_factor(127, 129, UNIT_K) == 1.0).all()
+    f = BR.dist_factor(24, 32, np.array([[30.0, 0, 16], [0, 30.0, 12], [0, 0, 1]]))
+    assert f[12, 16] == 1.0 and np.count_nonzero(f == 1.0) == 1 and (f >= 1.0).all()
+
+
+def test_vsd_restatement_at_exact_ties():
+    """delta = 2^-6, thresholds 2^-5 and 2^-3, every D equal to its depth: a gap equal to delta is visible and one float32 more
+    is not; a difference equal to thr_0 costs and one float32 less does not."""
+    f = np.float32
+    one = np.ones((1, 8), f)
+    dt, de = one.copy(), one.copy()
+    dt[0, 0] = f(1) - f(2.0 ** -6)
+    dt[0, 1] = np.nextafter(dt[0, 0], f(0))
+    de[0, 2] = f(1) + f(2.0 ** -5)
+    de[0, 3] = np.nextafter(de[0, 2], f(1))
+    c, _ = BR.vsd_counts(dt, de, one, UNIT_K, 2.0 ** -6, 0.25, (0.125, 0.5))
+    assert c.tolist() == [7, 7, 1, 0]
+
+
+def test_vsd_restatement_at_special_values():
+    """NaN and negative test depths hide the pixel, -0.0 and 0 are holes (visible), +inf lies behind everything (visible); a NaN,
+    -0.0 or negative estimate or ground truth is not drawn; an estimate at +inf over a visible ground truth costs at every tau."""
+    f = np.float32
+    nan, inf = f(np.nan), f(np.inf)
+    dt = np.array([[nan, -1, -0.0, inf, 0, 1, 1, 1]], f)
+    de = np.array([[1, 1, 1, 1, nan, inf, -0.0, -2]], f)
+    dg = np.array([[1, 1, 1, 1, 1, 1, nan, inf]], f)
+    c, _ = BR.vsd_counts(dt, de, dg, UNIT_K, 2.0 ** -6, 0.25, (0.125, 0.5))
+    assert c.tolist() == [4, 3, 1, 1]

@@ -203,3 +203,18 @@ def test_depth_fit_counts_rejects_bad_arguments(kw):
 
 def test_depth_fit_counts_zero_hypotheses_launch_nothing():
     assert _fit(off=(0, 0), P=0, depth=None, mask=None, renders=None, taus=None, counts=None) == 0
+
+
+def test_fit_counts_restatement_at_ties_and_special_values():
+    """One pixel per decision, tau = 2^-7 so that every difference is exact: diff = tau is no violation and fits, one float32
+    further out is a violation and does not fit (both signs); mask bytes 2 and 255 are set; NaN, negative and -0.0 observed
+    depths are unseen; +inf observed and drawn gives diff = NaN, which neither violates nor fits; a NaN render is not drawn and
+    is not 0 either (nothing unexplained)."""
+    f = np.float32
+    t = f(2.0 ** -7)
+    nan, inf = f(np.nan), f(np.inf)
+    d_o = np.array([[[1, 1, 1, 1, nan, -1, inf, -0.0]]], f)
+    m = np.array([[[1, 1, 2, 255, 1, 1, 1, 1]]], np.uint8)
+    d_h = np.array([[[f(1) - t, np.nextafter(f(1) - t, f(0)), f(1) + t, np.nextafter(f(1) + t, f(2)), 1, 1, inf, nan]]], f)
+    assert d_h[0, 0, 1] < d_h[0, 0, 0] < 1 < d_h[0, 0, 2] < d_h[0, 0, 3]
+    assert VR.fit_counts(d_o, m, [0, 1], d_h, [t, 0.0]).tolist() == [[7, 5, 1, 0, 2, 0]]

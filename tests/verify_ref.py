@@ -124,7 +124,8 @@ def fit_counts(depth, mask, hyp_off, renders, taus):
         obs = m & seen
         for p in range(hyp_off[i], hyp_off[i + 1]):
             dh = renders[p]
-            diff = do.astype(np.float64) - dh.astype(np.float64)
+            with np.errstate(invalid="ignore"):          # inf - inf = NaN, which passes no comparison (as in the kernel)
+                diff = do.astype(np.float64) - dh.astype(np.float64)
             drawn = dh > 0
             out[p, 0] = np.count_nonzero(drawn)
             out[p, 1] = np.count_nonzero(obs)
