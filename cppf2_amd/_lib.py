@@ -110,6 +110,11 @@ STABLE = {
     "cppf_rle_decode": (_i, [_i, _i, _i, _p, _i64, _p, _p, _p]),
     "cppf_mask_components_workspace_bytes": (_i64, [_i, _i, _i]),
     "cppf_mask_components": (_i, [_i, _i, _i, _i, _p, _p, _p, _f, _i, _p, _p, _p, _i64, _p]),
+    "cppf_plane_fit_workspace_bytes": (_i64, [_i, _i]),
+    "cppf_plane_fit": (_i, [_i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _p, _i64, _p]),
+    "cppf_plane_foreground": (_i, [_i, _i, _i, _p, _p, _p, _f, _f, _p, _p]),
+    "cppf_mask_segments_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "cppf_mask_segments": (_i, [_i, _i, _i, _i, _p, _p, _p, _f, _i, _i, _p, _p, _p, _p, _i64, _p]),
     "cppf_pose_hypotheses": (_i, [_i, _i, _p, _p, _p, _i, _f, _f, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
     "cppf_depth_fit_counts": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _p, _i, _p, _p]),
     "cppf_reslayer_split_stream_bytes": (_i64, [_i, _i, _i, _i]),

@@ -38,6 +38,20 @@
 //   5 write    out[d][i] = label[i] == kept ? 255 : 0 in groups of 4 bytes as above; stats[d][1] = kept label or -1,
 //              stats[d][2] = its pixels or 0
 //   A mask whose img_idx lies outside [0, I) has no valid pixel: stats (0, -1, 0, 0), mask 0.
+//
+// cppf_mask_segments: the M largest components instead of the largest one (mask proposals: cppf2_amd/segment.py).  Launches 1-3
+//   are cppf_mask_components' own kernels, unchanged; then
+//   4 rank     M launches of one kernel: round k takes the 64-bit atomicMax of cc_select_kernel's key over the roots with
+//              size >= min_pixels whose key lies below round k - 1's winner (round 0: all of them), into keys[d][k]: the
+//              components by size, descending, ties to the lowest label.  Round 0 also counts stats[d][0] (components) and
+//              stats[d][2] (components of at least min_pixels); a round whose predecessor found nothing returns at once.
+//   5 mark     grid (1, D), 64 threads: seg[d][k] = (label, pixels, INT_MAX, INT_MAX, -1, -1) for a kept rank, six -1 for an
+//              unused row; size[label] = -1 - k (the sizes are not needed any more: the word now maps a root to its rank);
+//              stats[d][1] = kept ranks
+//   6 write    rank[d][i] = the rank of label[i]'s component or 255, in groups of 4 bytes as above; the inclusive box of each
+//              rank by integer atomicMin / atomicMax, first in LDS, then one set of global atomics per rank and block
+//   The result is a pure function of the integer sizes and labels.  A mask whose img_idx lies outside [0, I): stats
+//   (0, 0, 0, 0), rank 255, seg -1.
 #include "cppf_common.h"
 
 #define MASK_THREADS 256
@@ -47,6 +61,7 @@
 #define RLE_PER_LANE 8
 #define RLE_CHUNK (MASK_THREADS * RLE_PER_LANE)        // runs per LDS pass (8 KiB of end positions)
 #define CC_ROUNDS 4                // wavefront-shared size adds before the per-lane fallback
+#define SEG_MAX 64                 // segments kept per mask at most (cppf_mask_segments)
 
 __global__ __launch_bounds__(MASK_THREADS) void rle_decode_kernel(const int32_t* __restrict__ runs, int64_t total_runs,
                                                                   const int32_t* __restrict__ run_off, int H, int W,
@@ -304,6 +319,129 @@ __global__ __launch_bounds__(MASK_THREADS) void cc_write_kernel(int HW, const in
   }
 }
 
+// ---- segments: the M largest components ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(MASK_THREADS) void cc_rank_kernel(int HW, int min_pixels, int M, int round, const int* __restrict__ labels,
+                                                               const int* __restrict__ sizes, int* __restrict__ stats,
+                                                               unsigned long long* __restrict__ keys) {
+  __shared__ uint32_t s_c[MASK_THREADS / CPPF_WAVE], s_b[MASK_THREADS / CPPF_WAVE];
+  __shared__ unsigned long long s_best;
+  const int d = blockIdx.y;
+  const unsigned long long bound = round ? keys[(int64_t)d * M + round - 1] : ~0ull;     // the same for the whole block
+  if (bound == 0) return;                                 // the round before found nothing (keys[d][round] stays 0)
+  const int* L = labels + (int64_t)d * HW;
+  const int* S = sizes + (int64_t)d * HW;
+  if (threadIdx.x == 0) s_best = 0;
+  __syncthreads();
+  uint32_t roots = 0, big = 0;
+  unsigned long long key = 0;
+  for (int i0 = blockIdx.x * MASK_THREADS; i0 < HW; i0 += gridDim.x * MASK_THREADS) {
+    const int i = i0 + threadIdx.x;
+    const bool root = i < HW && L[i] == i;
+    bool enough = false;
+    if (root) {
+      const int s = S[i];
+      enough = s >= min_pixels;
+      if (enough) {
+        const unsigned long long k = ((unsigned long long)(uint32_t)s << 32) | (0xFFFFFFFFu - (uint32_t)i);
+        key = k < bound && k > key ? k : key;
+      }
+    }
+    roots += (uint32_t)__popcll(wave_ballot(root));
+    big += (uint32_t)__popcll(wave_ballot(enough));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned long long o = __shfl_xor(key, off);
+    key = o > key ? o : key;
+  }
+  if (wave_lane() == 0) {
+    s_c[threadIdx.x / CPPF_WAVE] = roots;
+    s_b[threadIdx.x / CPPF_WAVE] = big;
+    if (key) atomicMax(&s_best, key);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (round == 0) {
+      uint32_t s = 0, b = 0;
+#pragma unroll
+      for (int k = 0; k < MASK_THREADS / CPPF_WAVE; ++k) { s += s_c[k]; b += s_b[k]; }
+      if (s) atomicAdd(&stats[4 * d], (int)s);
+      if (b) atomicAdd(&stats[4 * d + 2], (int)b);
+    }
+    if (s_best) atomicMax(&keys[(int64_t)d * M + round], s_best);
+  }
+}
+
+__global__ __launch_bounds__(CPPF_WAVE) void cc_mark_kernel(int HW, int M, const unsigned long long* __restrict__ keys,
+                                                            int* __restrict__ sizes, int* __restrict__ seg, int* __restrict__ stats) {
+  const int d = blockIdx.x, k = threadIdx.x;
+  const unsigned long long key = k < M ? keys[(int64_t)d * M + k] : 0ull;
+  if (k < M) {
+    int* row = seg + ((int64_t)d * M + k) * 6;
+    if (key) {
+      const int label = (int)(0xFFFFFFFFu - (uint32_t)key);
+      row[0] = label; row[1] = (int)(key >> 32);
+      row[2] = 0x7fffffff; row[3] = 0x7fffffff; row[4] = -1; row[5] = -1;
+      sizes[(int64_t)d * HW + label] = -1 - k;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) row[j] = -1;
+    }
+  }
+  const int kept = (int)__popcll(wave_ballot(key != 0));
+  if (k == 0) stats[4 * d + 1] = kept;
+}
+
+__global__ __launch_bounds__(MASK_THREADS) void cc_rank_write_kernel(int W, int HW, int M, const int* __restrict__ labels,
+                                                                     const int* __restrict__ sizes, int* __restrict__ seg,
+                                                                     uint8_t* __restrict__ out) {
+  __shared__ int s_box[SEG_MAX][4];
+  const int d = blockIdx.y;
+  const int* L = labels + (int64_t)d * HW;
+  const int* S = sizes + (int64_t)d * HW;
+  if (threadIdx.x < SEG_MAX) {
+    s_box[threadIdx.x][0] = 0x7fffffff; s_box[threadIdx.x][1] = 0x7fffffff;
+    s_box[threadIdx.x][2] = -1; s_box[threadIdx.x][3] = -1;
+  }
+  __syncthreads();
+  uint8_t* mk = out + (int64_t)d * HW;
+  const int m = (int)((uintptr_t)mk & 3);                 // groups as in rle_decode_kernel
+  const int nq = (HW + m + MASK_PX - 1) / MASK_PX;
+  for (int q = blockIdx.x * MASK_THREADS + threadIdx.x; q < nq; q += gridDim.x * MASK_THREADS) {
+    const int i0 = MASK_PX * q - m;
+    uint32_t bytes = 0;
+#pragma unroll
+    for (int j = 0; j < MASK_PX; ++j) {
+      const int i = i0 + j;
+      int rank = 255;
+      if (i >= 0 && i < HW) {
+        const int l = L[i];
+        const int s = l >= 0 ? S[l] : 0;                  // a kept root's word is -1 - rank, every other root's its size >= 1
+        if (s < 0 && -1 - s < M) {                        // (-1 - s < M always holds: the mark launch wrote it)
+          rank = -1 - s;
+          const int r = i / W, c = i - r * W;
+          atomicMin(&s_box[rank][0], c); atomicMin(&s_box[rank][1], r);
+          atomicMax(&s_box[rank][2], c); atomicMax(&s_box[rank][3], r);
+        }
+      }
+      bytes |= (uint32_t)rank << (8 * j);
+    }
+    if (i0 >= 0 && i0 + MASK_PX - 1 < HW) {
+      *reinterpret_cast<uint32_t*>(mk + i0) = bytes;
+    } else {
+#pragma unroll
+      for (int j = 0; j < MASK_PX; ++j)
+        if (i0 + j >= 0 && i0 + j < HW) mk[i0 + j] = (uint8_t)(bytes >> (8 * j));
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < M && s_box[threadIdx.x][2] >= 0) {
+    int* row = seg + ((int64_t)d * M + threadIdx.x) * 6;
+    atomicMin(row + 2, s_box[threadIdx.x][0]); atomicMin(row + 3, s_box[threadIdx.x][1]);
+    atomicMax(row + 4, s_box[threadIdx.x][2]); atomicMax(row + 5, s_box[threadIdx.x][3]);
+  }
+}
+
 static int64_t cc_best_bytes(int D) { return ((int64_t)D * 8 + 255) / 256 * 256; }
 
 extern "C" int64_t cppf_mask_components_workspace_bytes(int D, int H, int W) {
@@ -351,6 +489,48 @@ extern "C" int cppf_mask_components(int D, int I, int H, int W, const uint8_t* m
   hipLaunchKernelGGL(cc_select_kernel, grid, block, 0, st, HW, min_pixels, (const int*)labels, (const int*)sizes, (int*)stats, best);
   hipLaunchKernelGGL(cc_write_kernel, grid, block, 0, st, HW, (const int*)labels, (const unsigned long long*)best, (int*)stats,
                      out_mask);
+  CPPF_LAUNCH_CHECK();
+  return CPPF_OK;
+}
+
+static int64_t cc_keys_bytes(int D, int M) { return ((int64_t)D * M * 8 + 255) / 256 * 256; }
+
+extern "C" int64_t cppf_mask_segments_workspace_bytes(int D, int H, int W, int max_segments) {
+  if (D <= 0 || H <= 0 || W <= 0 || D > 65535 || H > MASK_MAX_DIM || W > MASK_MAX_DIM) return 0;
+  if (max_segments < 1 || max_segments > SEG_MAX) return 0;
+  return cc_keys_bytes(D, max_segments) + (int64_t)D * H * W * 2 * (int64_t)sizeof(int32_t);
+}
+
+extern "C" int cppf_mask_segments(int D, int I, int H, int W, const uint8_t* masks, const float* depths, const int32_t* img_idx,
+                                  float jump, int min_pixels, int max_segments, uint8_t* out_rank, int32_t* seg, int32_t* stats,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  CPPF_CHECK_ARG(D >= 0 && D <= 65535);
+  CPPF_CHECK_ARG(I >= 1 && H >= 1 && W >= 1 && H <= MASK_MAX_DIM && W <= MASK_MAX_DIM);
+  CPPF_CHECK_ARG(jump >= 0.0f && jump < __builtin_inff());
+  CPPF_CHECK_ARG(min_pixels >= 0);
+  CPPF_CHECK_ARG(max_segments >= 1 && max_segments <= SEG_MAX);
+  if (D == 0) return CPPF_OK;
+  CPPF_CHECK_ARG(masks && depths && img_idx && out_rank && seg && stats);
+  CPPF_CHECK_ARG(workspace && (uintptr_t)workspace % 8 == 0);
+  CPPF_CHECK_ARG(workspace_bytes >= cppf_mask_segments_workspace_bytes(D, H, W, max_segments));
+  hipStream_t st = (hipStream_t)stream;
+  const int HW = H * W, M = max_segments;
+  unsigned long long* keys = (unsigned long long*)workspace;
+  int* labels = (int*)((char*)workspace + cc_keys_bytes(D, M));
+  int* sizes = labels + (int64_t)D * HW;
+  CPPF_HIP(hipMemsetAsync(keys, 0, (size_t)cc_keys_bytes(D, M), st));
+  CPPF_HIP(hipMemsetAsync(stats, 0, (size_t)D * 4 * sizeof(int32_t), st));
+  const int blocks = (HW + MASK_THREADS - 1) / MASK_THREADS;
+  const dim3 grid(blocks < MASK_MAX_BLOCKS ? blocks : MASK_MAX_BLOCKS, D), block(MASK_THREADS);
+  hipLaunchKernelGGL(cc_init_kernel, grid, block, 0, st, masks, depths, I, img_idx, HW, labels, sizes, (int*)stats);
+  hipLaunchKernelGGL(cc_merge_kernel, grid, block, 0, st, depths, I, img_idx, H, W, jump, labels);
+  hipLaunchKernelGGL(cc_compress_kernel, grid, block, 0, st, HW, labels, sizes);
+  for (int k = 0; k < M; ++k)
+    hipLaunchKernelGGL(cc_rank_kernel, grid, block, 0, st, HW, min_pixels, M, k, (const int*)labels, (const int*)sizes, (int*)stats,
+                       keys);
+  hipLaunchKernelGGL(cc_mark_kernel, dim3(D), dim3(CPPF_WAVE), 0, st, HW, M, (const unsigned long long*)keys, sizes, (int*)seg,
+                     (int*)stats);
+  hipLaunchKernelGGL(cc_rank_write_kernel, grid, block, 0, st, W, HW, M, (const int*)labels, (const int*)sizes, (int*)seg, out_rank);
   CPPF_LAUNCH_CHECK();
   return CPPF_OK;
 }

@@ -66,6 +66,13 @@ What the image cannot provide is stated, not faked:
     checkpoint; --hypotheses, --centre_peaks, --icp_iters, --icp_depth, --opt, --gt_pose, --out_csv, --detections and
     --clean_masks work as before, and the report gains `table_hits` (per instance: tuples that took their own cell, a
     neighbouring cell, the whole table).  Not with --teacher_prior, --ckpt_* or the synthetic / NOCS modes.
+  * `--data=depth --propose_masks [--plane_hypotheses=256 --plane_tau=0.005 --plane_min_height=0.01 --mask_jump=0.01
+    --min_segment_pixels=200 --max_proposals=16]` stands where --mask stood: the support plane of the depth image is fitted and
+    dropped and what is left is cut into depth-connected segments (cppf2_amd.segment; the plane's
+    hypotheses are drawn from --seed).  Every proposal is one instance of the batch, with the tuple streams a --mask run of its
+    mask would have; proposals wider than 1000 cells or with too few points are skipped and counted.  The report gains `plane`,
+    `proposals` (pixels, bbox, pose; the verification score with --hypotheses > 1) and, with --hypotheses > 1, `best`: the
+    proposal with the highest score, ties to the larger one.  --gt_pose scores `best` when it exists, else every proposal.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import collections
@@ -567,6 +574,43 @@ def _centre_peaks_flag(centre_peaks, hypotheses):
     return centre_peaks
 
 
+_PROPOSE_FLAGS = ("plane_tau", "plane_hypotheses", "plane_min_height", "min_segment_pixels", "max_proposals")
+
+
+def _propose_flags(f):
+    """segment.propose's keyword arguments from the --propose_masks flags, or None when it is off."""
+    given = [k_ for k_ in _PROPOSE_FLAGS if getattr(f, k_) is not None]
+    if not f.propose_masks:
+        if given:
+            raise ValueError("--%s sets how masks are proposed: it needs --propose_masks" % given[0])
+        return None
+    if f.data != "depth":
+        raise ValueError("--propose_masks proposes the masks of one depth image: it needs --data=depth "
+                         "(--data=bop: python -m cppf2_amd.segment writes a detections file)")
+    if f.mask:
+        raise ValueError("--propose_masks replaces --mask: give one of them")
+    if bool(f.clean_masks) or bool(f.clean_mask):
+        raise ValueError("--clean_mask cleans a given mask: proposals are depth-connected already")
+    from cppf2_amd import masks, segment
+    p = dict(num_hyp=segment.NUM_HYP if f.plane_hypotheses is None else int(f.plane_hypotheses),
+             tau=segment.TAU if f.plane_tau is None else float(f.plane_tau),
+             min_height=segment.MIN_HEIGHT if f.plane_min_height is None else float(f.plane_min_height),
+             jump=masks.JUMP if f.mask_jump is None else float(f.mask_jump),
+             min_pixels=segment.MIN_SEGMENT_PIXELS if f.min_segment_pixels is None else int(f.min_segment_pixels),
+             max_segments=segment.MAX_SEGMENTS if f.max_proposals is None else int(f.max_proposals))
+    if not 1 <= p["num_hyp"] <= segment.MAX_HYP:
+        raise ValueError("--plane_hypotheses must be in 1 .. %d, not %d" % (segment.MAX_HYP, p["num_hyp"]))
+    if not (p["tau"] > 0 and np.isfinite(p["tau"])):
+        raise ValueError("--plane_tau is a distance in metres > 0, not %r" % (f.plane_tau,))
+    if not np.isfinite(p["min_height"]):
+        raise ValueError("--plane_min_height is a distance in metres, not %r" % (f.plane_min_height,))
+    if p["min_pixels"] < 0:
+        raise ValueError("--min_segment_pixels must be >= 0, not %d" % p["min_pixels"])
+    if not 1 <= p["max_segments"] <= segment.SEGMENTS_LIMIT:
+        raise ValueError("--max_proposals must be in 1 .. %d, not %d" % (segment.SEGMENTS_LIMIT, p["max_segments"]))
+    return p
+
+
 def _checked_flags(**kw):
     """main()'s keyword arguments as a namespace, after every rule that ties one flag to another: the first broken rule raises
     its ValueError, before a device, a model or a file is touched.  Normalised on the way: icp_iters, hypotheses, centre_peaks
@@ -593,6 +637,7 @@ def _checked_flags(**kw):
     f.clean_masks = bool(f.clean_masks) or bool(f.clean_mask)
     if f.mask_jump is not None and not (float(f.mask_jump) >= 0.0 and np.isfinite(float(f.mask_jump))):
         raise ValueError("--mask_jump is a distance in metres >= 0, not %r" % (f.mask_jump,))
+    f.propose = _propose_flags(f)
     if bop_mode and not (f.bop_root and f.out_csv):
         raise ValueError("--data=bop needs --bop_root (the dataset folder) and --out_csv (the results file to write)")
     if not bop_mode and f.detections is not None:
@@ -720,11 +765,30 @@ def main_synthetic(setups, categories, vote, num_scenes=8, num_points=4096, debu
     return _finish(report, acc, categories, debug, out, out_pkl)
 
 
+def _score_against_gt(item, bop_obj, d, K, gt_R, gt_t, r, b, reported, ver, icp_stats):
+    """The BOP errors of instance b's reported pose (of its first hypothesis; of its pose before ICP) against --gt_pose, on the
+    depth image d and K, into item[`bop`] ([`bop_first`], [`bop_before_icp`]); an instance without an estimate scores +inf.
+    Returns the reported pose's errors, for the run's average recall."""
+    from cppf2_amd import bop
+    poses = [reported[b]] + ([ver["hypotheses"][b, 0]] if ver is not None else [])
+    poses += [r["records"][r["pick"][b]][b]] if icp_stats is not None else []
+    nan = (np.full((3, 3), np.nan), np.full(3, np.nan))
+    poses = [(p_["R"], p_["t"]) if r["pick"][b] >= 0 else nan for p_ in poses]
+    err = bop.pose_errors(bop_obj, d, np.zeros(len(poses), dtype=np.int64), [p_[0] for p_ in poses],
+                          [p_[1] for p_ in poses], [gt_R] * len(poses), [gt_t] * len(poses), K)
+    keys = ["bop"] + (["bop_first"] if ver is not None else []) + (["bop_before_icp"] if icp_stats is not None else [])
+    for j, k_ in enumerate(keys):
+        item[k_] = dict(vsd=[float(x) for x in err["vsd"][j]], mssd=float(err["mssd"][j]), mspd=float(err["mspd"][j]))
+    return {k_: v_[:1] for k_, v_ in err.items()}
+
+
 def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_scale=1000.0, mesh=None, mesh_scale=1.0, icp_iters=0,
                icp_depth=False, icp_model_weight=1.0, gt_pose=None, models_info=None, hypotheses=1, verify_tau=None,
-               centre_peaks=1, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None):
+               centre_peaks=1, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None, propose=None):
     """One depth + mask PNG pair (example_data layout): one instance, evaluated once per category of `categories`; with `mesh`
-    its pose is refined (icp_iters), verified (hypotheses) and scored against gt_pose (BOP errors), see the module docstring."""
+    its pose is refined (icp_iters), verified (hypotheses) and scored against gt_pose (BOP errors), see the module docstring.
+    propose: segment.propose's keyword arguments; the proposed masks then stand where the one of `mask` stood, one instance
+    each in one batch per category."""
     from PIL import Image
     from cppf2_amd import bop, icp, masks, render, verify
     dev = ops._dev()
@@ -742,6 +806,11 @@ def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_sca
         verify_tau = verify.TAU if verify_tau is None else float(verify_tau)
         verify_obj = bop_obj if bop_obj is not None else bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale))
     d = np.array(Image.open(depth)).astype(np.float64) / float(depth_scale)
+    K = np.array(intrinsics if intrinsics is not None else REAL_INTRINSICS, dtype=np.float64).reshape(3, 3)
+    if propose is not None:
+        return _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj, verify_obj,
+                                (gt_R, gt_t) if bop_obj is not None else None, os.path.basename(mesh or ""), icp_iters, icp_depth,
+                                icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl)
     m = np.array(Image.open(mask))
     m = (m[..., 0] if m.ndim == 3 else m) > 0
     cleaning = None
@@ -753,7 +822,6 @@ def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_sca
         cleaning = dict(components=stats[0], kept_pixels=stats[2], valid_pixels=stats[3])
         if not m.any():
             raise ValueError("--clean_mask: no depth-connected component of the mask has %d pixels" % masks.MIN_PIXELS)
-    K = np.array(intrinsics if intrinsics is not None else REAL_INTRINSICS, dtype=np.float64).reshape(3, 3)
     acc = Results([], [], [], [], [], [])
     for ci, cat in enumerate(categories):           # the instance is scene `ci` of the run: its tuple / uniform streams' seed
         cfg = setups[cat][0]
@@ -771,24 +839,91 @@ def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_sca
         item = acc.summary[-1]
         item.update(instance_items(r, 0, icp_stats, ver, centre_peaks))
         if bop_obj is not None:
-            # the BOP errors of the reported pose (of the first hypothesis; of the pose before ICP) against --gt_pose, on the
-            # depth image and K loaded above; an instance without an estimate scores +inf
-            poses = [reported[0]] + ([ver["hypotheses"][0, 0]] if ver is not None else [])
-            poses += [r["records"][r["pick"][0]][0]] if icp_stats is not None else []
-            nan = (np.full((3, 3), np.nan), np.full(3, np.nan))
-            poses = [(p_["R"], p_["t"]) if r["pick"][0] >= 0 else nan for p_ in poses]
-            err = bop.pose_errors(bop_obj, d, np.zeros(len(poses), dtype=np.int64), [p_[0] for p_ in poses],
-                                  [p_[1] for p_ in poses], [gt_R] * len(poses), [gt_t] * len(poses), K)
-            keys = ["bop"] + (["bop_first"] if ver is not None else []) + (["bop_before_icp"] if icp_stats is not None else [])
-            for j, k_ in enumerate(keys):
-                item[k_] = dict(vsd=[float(x) for x in err["vsd"][j]], mssd=float(err["mssd"][j]), mspd=float(err["mspd"][j]))
-            bop_reported.append({k_: v_[:1] for k_, v_ in err.items()})
+            bop_reported.append(_score_against_gt(item, bop_obj, d, K, gt_R, gt_t, r, 0, reported, ver, icp_stats))
     report = dict(categories=categories, instances=len(acc.summary),
                   opt_refinement="100 Adam steps (cppf_refine_pose)" if vote.opt else "off", results=acc.summary)
     if pair_table:
         report.update(pair_table=str(pair_table), table_hits=[s_["table_hits"] for s_ in acc.summary])
     report.update(stage_notes(os.path.basename(mesh or ""), icp_iters, icp_depth, icp_model_weight, hypotheses, verify_tau,
                               centre_peaks, cleaning))
+    if icp_model is not None:
+        report["icp"] = [s_["icp"] for s_ in acc.summary if "icp" in s_]
+    if bop_reported:
+        errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
+        report["bop"] = dict(bop.average_recall(errs, bop_obj.diameter, d.shape[1]), delta=bop.DELTA, taus=list(bop.TAUS))
+    return _finish(report, acc, categories, debug, out, out_pkl)
+
+
+def _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj, verify_obj, gt, against, icp_iters, icp_depth,
+                     icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl):
+    """main_depth with proposed masks (segment.propose on the depth image d, metres, with the run's seed): per category one batch
+    whose instances are the proposals that give a usable cloud, each with the cloud, scene index and tuple streams a --mask run
+    of its mask has.  gt: (R, t) of --gt_pose or None."""
+    from cppf2_amd import bop, segment
+    dev = ops._dev()
+    pm, props, plane = segment.propose(d.astype(np.float32), K, vote.seed, **propose)
+    pmasks = pm.cpu().numpy() > 0
+    acc = Results([], [], [], [], [], [])
+    skipped = dict(too_large=0, too_few_points=0)
+    proposals, best, bop_reported = [], None, []
+    for ci, cat in enumerate(categories):
+        cfg = setups[cat][0]
+        up_sym = cat in UP_SYM or bool(cfg.get("up_sym", False))
+        ranks, pcs = [], []
+        for p_, m in enumerate(pmasks):
+            pc = instance_cloud(d, K, m, cfg.res, vote.seed)
+            if pc.shape[0] < cfg.num_more + 2:
+                skipped["too_few_points"] += 1
+            elif too_wide(pc, cfg.res):                                                    # eval.py:200
+                skipped["too_large"] += 1
+            else:
+                ranks.append(p_)
+                pcs.append(pc)
+        B = len(pcs)
+        if not B:
+            continue
+        descs = [] if pair_table else [stand_in_descriptors(pc.shape[0], vote.seed + 1 + ci).numpy() for pc in pcs]
+        r, enabled = vote_batch(setups[cat], pcs, descs, [ci] * B, vote, up_sym, hypotheses=hypotheses, centre_peaks=centre_peaks,
+                                table=load_pair_table(pair_table, dev) if pair_table else None)
+        images = hypotheses > 1 or icp_depth
+        reported, icp_stats, ver = refine_and_verify(
+            r, hypotheses, enabled, verify_obj, np.broadcast_to(d.astype(np.float32), (B,) + d.shape) if images else None,
+            pmasks[ranks] if images else None, K, np.cumsum([0] + [pc.shape[0] for pc in pcs]), icp_model, icp_iters, verify_tau,
+            icp_depth, icp_model_weight)
+        _add_results(acc, cat, [ci] * B, r, reported, up_sym)
+        items = acc.summary[-B:]
+        top = None
+        for b, item in enumerate(items):
+            item.update(instance_items(r, b, icp_stats, ver, centre_peaks))
+            item.update(proposal=ranks[b], pixels=props[ranks[b]]["pixels"], bbox=props[ranks[b]]["bbox"], points=int(pcs[b].shape[0]))
+            entry = dict(proposal=ranks[b], category=cat, pixels=item["pixels"], bbox=item["bbox"], R=None, t=None)
+            if r["pick"][b] >= 0:
+                entry.update(R=np.asarray(reported[b]["R"], dtype=np.float64).reshape(3, 3).tolist(),
+                             t=np.asarray(reported[b]["t"], dtype=np.float64).tolist())
+                if ver is not None:
+                    entry["score"] = item["verify"]["score"]
+                    if top is None or entry["score"] > items[top]["verify"]["score"]:      # ties: the lower rank stays
+                        top = b
+            proposals.append(entry)
+        if top is not None and (best is None or items[top]["verify"]["score"] > best["score"]):
+            best = dict(proposal=ranks[top], category=cat, score=items[top]["verify"]["score"])
+        if bop_obj is not None:
+            # --gt_pose: the best proposal when the verification chose one, else every proposal; the keys of the --mask route
+            for b in ([top] if ver is not None else range(B)):
+                if b is not None:
+                    bop_reported.append(_score_against_gt(items[b], bop_obj, d, K, gt[0], gt[1], r, b, reported, ver, icp_stats))
+    report = dict(categories=categories, instances=len(acc.summary),
+                  opt_refinement="100 Adam steps (cppf_refine_pose)" if vote.opt else "off", results=acc.summary,
+                  plane=dict(n=plane["n"], d=plane["d"], inliers=plane["inliers"], usable_hypotheses=plane["usable_hypotheses"],
+                             valid_pixels=plane["valid_pixels"]),
+                  proposals=proposals, proposed=len(props), skipped=skipped,
+                  mask_proposals=dict(propose, seed=int(vote.seed), components=plane["components"],
+                                      large_components=plane["large_components"]))
+    if best is not None:
+        report["best"] = best
+    if pair_table:
+        report.update(pair_table=str(pair_table), table_hits=[s_["table_hits"] for s_ in acc.summary])
+    report.update(stage_notes(against, icp_iters, icp_depth, icp_model_weight, hypotheses, verify_tau, centre_peaks, None))
     if icp_model is not None:
         report["icp"] = [s_["icp"] for s_ in acc.summary if "icp" in s_]
     if bop_reported:
@@ -804,7 +939,9 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          desc_npz=None, batch_instances=16, max_images=None, mesh=None, mesh_scale=1.0, icp_iters=0, gt_pose=None,
          models_info=None, hypotheses=1, verify_tau=None, bop_root=None, split="test", targets=None, out_csv=None,
          teacher_prior=False, model_scale=0.001, centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False,
-         clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0, pair_table=None, pair_tables=None):
+         clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0, pair_table=None, pair_tables=None,
+         propose_masks=False, plane_tau=None, plane_hypotheses=None, plane_min_height=None, min_segment_pixels=None,
+         max_proposals=None):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()
@@ -843,7 +980,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                           mesh_scale=mesh_scale, icp_iters=f.icp_iters, icp_depth=f.icp_depth, icp_model_weight=f.icp_model_weight,
                           gt_pose=gt_pose, models_info=models_info, hypotheses=f.hypotheses, verify_tau=verify_tau,
                           centre_peaks=f.centre_peaks, clean_mask=f.clean_masks, mask_jump=mask_jump, pair_table=pair_table,
-                          debug=debug, out=out, out_pkl=out_pkl)
+                          debug=debug, out=out, out_pkl=out_pkl, propose=f.propose)
     return main_synthetic(setups, categories, vote, num_scenes=num_scenes, num_points=num_points, debug=debug, out=out,
                           out_pkl=out_pkl)
 

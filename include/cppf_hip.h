@@ -479,6 +479,42 @@ int cppf_mask_components(int D, int I, int H, int W, const uint8_t* masks, const
                          int min_pixels, uint8_t* out_mask, int32_t* stats, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* ---- mask proposals from depth alone: support plane, depth segments (not in the reference; cppf2_amd/segment.py) ----------
+ * Integer counts and integer maxima only: an image's outputs do not depend on the batch or the order.  I images (D masks),
+ * at most 65535 per call, 0 launches nothing; one image size H x W (<= 8192 each) per call.  The exact order of the float32
+ * operations is stated in cppf2_amd/csrc/cppf_segment.hip, the ranking in cppf2_amd/csrc/cppf_mask.hip.
+ *
+ * cppf_plane_fit: the plane with the most inliers among num_hyp (1 .. 1024) three-pixel hypotheses per image.  depths
+ * float32[I,H,W] (metres; a pixel is valid when depth > 0 && depth is finite), Kmat float32[I,4] = (fx, fy, cx, cy) (zero skew),
+ * seeds uint64[I] (device): hypothesis h of image i draws philox4x32_10 with counter (h, 0, 0, 0) and key = the two halves of
+ * seeds[i], and takes the pixels (uint64)word_j * (H * W) >> 32, j = 0, 1, 2.  Point of pixel (r, c): z = depth,
+ * x = ((float)c - cx) * z / fx, y = ((float)r - cy) * z / fy.  A hypothesis is unusable when two pixels coincide, one is not
+ * valid or the cross product of the two edges is not longer than 1e-12; otherwise n = cross / |cross|, d = -(n . a), both
+ * negated when d < 0.  Inlier: a valid pixel with fabsf(n . p + d) <= tau (tau > 0, finite, metres).  The winner has the most
+ * inliers, ties to the lowest hypothesis.  plane float32[I,4] = (n, d), zeros when no hypothesis was usable; stats int32[I,4] =
+ * (winning hypothesis or -1, its inliers, usable hypotheses, valid pixels).  workspace: cppf_plane_fit_workspace_bytes(I,
+ * num_hyp) bytes, 16-byte aligned (0 for sizes the call refuses).  Three launches behind one clear, no host synchronisation.
+ *
+ * cppf_plane_foreground: fg uint8[I,H,W] = 255 where the pixel is valid and its height n . p + d above plane[i] is
+ * > min_height and, when max_height > 0, <= max_height; else 0.  An image whose plane is four zeros: 255 on every valid pixel.
+ * No workspace, one launch.
+ *
+ * cppf_mask_segments: cppf_mask_components' labelling (same arguments, same rules), but the max_segments (1 .. 64) largest
+ * components of at least min_pixels pixels are kept, ranked by size, descending, ties to the lowest label.  out_rank
+ * uint8[D,H,W] = the rank of the pixel's component or 255 (it may be `masks` itself); seg int32[D,max_segments,6] = (label,
+ * pixels, x0, y0, x1, y1) per rank, the box inclusive, unused rows -1; stats int32[D,4] = (components, segments kept,
+ * components of at least min_pixels, valid pixels).  workspace: cppf_mask_segments_workspace_bytes(D, H, W, max_segments)
+ * bytes, 8-byte aligned.  5 + max_segments launches behind two clears, no host synchronisation. */
+int64_t cppf_plane_fit_workspace_bytes(int I, int num_hyp);
+int cppf_plane_fit(int I, int H, int W, const float* depths, const float* Kmat, const uint64_t* seeds, int num_hyp, float tau,
+                   float* plane, int32_t* stats, void* workspace, int64_t workspace_bytes, void* stream);
+int cppf_plane_foreground(int I, int H, int W, const float* depths, const float* Kmat, const float* plane, float min_height,
+                          float max_height, uint8_t* fg, void* stream);
+int64_t cppf_mask_segments_workspace_bytes(int D, int H, int W, int max_segments);
+int cppf_mask_segments(int D, int I, int H, int W, const uint8_t* masks, const float* depths, const int32_t* img_idx, float jump,
+                       int min_pixels, int max_segments, uint8_t* out_rank, int32_t* seg, int32_t* stats, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* ---- instance-level hypothesis verification: render and compare (not in the reference) -------------------------------
  * Several peaks of each rotation-bin vote become pose hypotheses; each hypothesis' render (cppf_render_depth) is counted
  * against the observed depth, and cppf2_amd/verify.py keeps the one that explains most of it.  The exact order of the
