@@ -175,26 +175,23 @@ def write_detections(path, dets, compress=True):
 # ----------------------------------------------------------------------------------------------
 # reader
 # ----------------------------------------------------------------------------------------------
-class Dataset:
-    """One split of a BOP-format dataset under `root`.  scene_ids: the scene folders found.  Ground-truth poses are converted to
-    the record convention (bop.pose_from_bop) with each object's bounding-box centre."""
+class Models:
+    """The models folder of a BOP-format dataset: obj_{id:06d}.ply in model units (`mesh_scale` to metres) and, when present,
+    models_info.json.  Dataset reads its objects through one; eval.py's multi-object form reads a folder given on its own."""
 
-    def __init__(self, root, split, mesh_scale=0.001):
-        self.root, self.split, self.mesh_scale = str(root), str(split), float(mesh_scale)
-        self.split_dir = os.path.join(self.root, self.split)
-        if not os.path.isdir(self.split_dir):
-            raise BopDataError("%s: no such split folder" % self.split_dir)
-        info = os.path.join(self.root, "models", "models_info.json")
+    def __init__(self, models_dir, mesh_scale=0.001):
+        self.dir, self.mesh_scale = str(models_dir), float(mesh_scale)
+        info = os.path.join(self.dir, "models_info.json")
         self.models_info = _int_keys(_read_json(info)) if os.path.exists(info) else {}
-        self.scene_ids = sorted(int(d) for d in os.listdir(self.split_dir)
-                                if d.isdigit() and os.path.isdir(os.path.join(self.split_dir, d)))
-        self._objects, self._scenes, self._info, self._masks = {}, {}, {}, (None, None)
+        self._objects = {}
 
-    def scene_dir(self, scene_id):
-        return os.path.join(self.split_dir, "%06d" % int(scene_id))
+    def ids(self):
+        """The object ids that have a model file, ascending."""
+        names = os.listdir(self.dir) if os.path.isdir(self.dir) else []
+        return sorted(int(n[4:10]) for n in names if len(n) == 14 and n.startswith("obj_") and n.endswith(".ply") and n[4:10].isdigit())
 
     def model_path(self, obj_id):
-        return os.path.join(self.root, "models", "obj_%06d.ply" % int(obj_id))
+        return os.path.join(self.dir, "obj_%06d.ply" % int(obj_id))
 
     def object(self, obj_id):
         """The bop.ObjectInfo of an object id (mesh and models_info entry), loaded on first use."""
@@ -210,6 +207,35 @@ class Dataset:
     def mesh(self, obj_id):
         self.object(obj_id)
         return render.load_mesh(self.model_path(obj_id), self.mesh_scale)
+
+
+class Dataset:
+    """One split of a BOP-format dataset under `root`.  scene_ids: the scene folders found.  Ground-truth poses are converted to
+    the record convention (bop.pose_from_bop) with each object's bounding-box centre."""
+
+    def __init__(self, root, split, mesh_scale=0.001):
+        self.root, self.split, self.mesh_scale = str(root), str(split), float(mesh_scale)
+        self.split_dir = os.path.join(self.root, self.split)
+        if not os.path.isdir(self.split_dir):
+            raise BopDataError("%s: no such split folder" % self.split_dir)
+        self.models = Models(os.path.join(self.root, "models"), self.mesh_scale)
+        self.models_info = self.models.models_info
+        self.scene_ids = sorted(int(d) for d in os.listdir(self.split_dir)
+                                if d.isdigit() and os.path.isdir(os.path.join(self.split_dir, d)))
+        self._scenes, self._info, self._masks = {}, {}, (None, None)
+
+    def scene_dir(self, scene_id):
+        return os.path.join(self.split_dir, "%06d" % int(scene_id))
+
+    def model_path(self, obj_id):
+        return self.models.model_path(obj_id)
+
+    def object(self, obj_id):
+        """The bop.ObjectInfo of an object id (mesh and models_info entry), loaded on first use."""
+        return self.models.object(obj_id)
+
+    def mesh(self, obj_id):
+        return self.models.mesh(obj_id)
 
     def scene(self, scene_id):
         """dict(camera {im: dict(K float64 [3,3], depth_scale)}, gt {im: [dict(obj_id, R, t (record convention), cam_R_m2c,

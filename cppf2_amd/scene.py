@@ -1,0 +1,138 @@
+"""Scene explanation (the reference has no such step): of all verified candidate poses of a depth image,
+the subset that together explains the observed depth, every observed pixel counted once (cppf_scene_explain).  verify.select
+decides per mask and in isolation; this decides per image: which candidates are instances and which are clutter.
+
+    out = explain(depth, region, cand_off, renders)           # device tensors: chosen, gain, net, static, labels, summary
+    out = explain_candidates(objs, depth, region, K, records, obj_of)
+    out["records"]                                            # the chosen records, in the order they were chosen
+
+Greedy rounds: a candidate's gain is the number of region pixels it fits within tau that no earlier winner explained, its net
+the gain minus viol_weight times its violations (pixels where it would hide a surface the camera saw); the largest net of at
+least min_gain wins, ties to the lower index, and its fit pixels are explained.  The defaults are derived, none was swept: TAU
+is verification's 2 cm, MIN_GAIN the smallest segment that can carry a pose (segment.MIN_SEGMENT_PIXELS), VIOL_WEIGHT = 1 lets
+one hidden observed pixel cancel one explained pixel, the trade verify.score makes in its denominator.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import segment as _segment
+
+TAU = 0.02                                  # verify.TAU (not imported here: this module's checks need no library)
+MIN_GAIN = _segment.MIN_SEGMENT_PIXELS
+VIOL_WEIGHT = 1
+MAX_ROUNDS = 16
+MAX_CANDIDATES = 64                         # per image: one bit of a pixel's word each
+ROUNDS_LIMIT = 64
+MAX_DIM = 8192
+
+
+def _checked(cand_off, tau, min_gain, viol_weight, max_rounds, who):
+    """The host-side arguments, checked before a device is touched: (int32 offsets, tau, min_gain, viol_weight, max_rounds)."""
+    tau, min_gain, viol_weight, max_rounds = float(tau), int(min_gain), int(viol_weight), int(max_rounds)
+    if not tau >= 0.0:
+        raise ValueError("%s: tau is a distance in metres >= 0, not %r" % (who, tau))
+    if not 1 <= min_gain < 2 ** 31:
+        raise ValueError("%s: min_gain must be >= 1, not %d" % (who, min_gain))
+    if not 0 <= viol_weight < 2 ** 31:
+        raise ValueError("%s: viol_weight must be >= 0, not %d" % (who, viol_weight))
+    if not 1 <= max_rounds <= ROUNDS_LIMIT:
+        raise ValueError("%s: max_rounds must be in 1 .. %d, not %d" % (who, ROUNDS_LIMIT, max_rounds))
+    off = np.asarray(cand_off.cpu().numpy() if hasattr(cand_off, "cpu") else cand_off).reshape(-1)
+    if off.size < 2 or not np.issubdtype(off.dtype, np.integer):
+        raise ValueError("%s: cand_off is int [I+1], I >= 1" % who)
+    off = off.astype(np.int64)
+    if off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("%s: cand_off must start at 0 and never decrease" % who)
+    if np.any(np.diff(off) > MAX_CANDIDATES):
+        raise ValueError("%s: at most %d candidates per image, not %d" % (who, MAX_CANDIDATES, int(np.diff(off).max())))
+    return np.ascontiguousarray(off, dtype=np.int32), tau, min_gain, viol_weight, max_rounds
+
+
+def explain(depth, region, cand_off, renders, tau=TAU, min_gain=MIN_GAIN, viol_weight=VIOL_WEIGHT, max_rounds=MAX_ROUNDS):
+    """cppf_scene_explain on the current stream.  depth float32 [I,H,W] or [H,W] (metres, 0 = no reading), region [I,H,W] or
+    [H,W] (non-zero: a pixel to explain), cand_off int [I+1] (host: renders cand_off[i] .. cand_off[i+1]-1 are the candidates of
+    image i, at most 64 each), renders float32 [P,H,W] (0 = nothing drawn).  Returns a dict of device tensors: chosen int32
+    [I,M] (the winner's index within its image per round, -1 past the end), gain and net int64 [I,M], static int64 [P,3]
+    (drawn, fit, violations: columns 0, 4 and 2 of verify.fit_counts), labels uint8 [I,H,W] (the round that explained the pixel,
+    255: none), summary int64 [I,3] (region pixels with a reading, explained pixels, rounds used).  No host synchronisation."""
+    off, tau, min_gain, viol_weight, M = _checked(cand_off, tau, min_gain, viol_weight, max_rounds, "scene.explain")
+    import torch
+    from . import _lib, ops
+    dev = ops._dev()
+    d = ops._t(depth, torch.float32, dev)
+    d = d[None] if d.dim() == 2 else d
+    if d.dim() != 3 or min(d.shape) < 1 or d.shape[1] > MAX_DIM or d.shape[2] > MAX_DIM:
+        raise ValueError("scene.explain: depth is [I,H,W] or [H,W] with H, W in 1 .. %d, not %s" % (MAX_DIM, tuple(d.shape)))
+    I, H, W = (int(x) for x in d.shape)
+    m = ops._t(torch.as_tensor(region) != 0 if torch.is_tensor(region) else np.asarray(region) != 0, torch.uint8, dev)
+    m = m[None] if m.dim() == 2 else m
+    if m.shape != d.shape:
+        raise ValueError("scene.explain: region %s for depth %s" % (tuple(m.shape), tuple(d.shape)))
+    if off.size != I + 1:
+        raise ValueError("scene.explain: cand_off of %d entries for %d images" % (off.size, I))
+    r = ops._t(renders, torch.float32, dev)
+    if r.numel() % (H * W):
+        raise ValueError("scene.explain: renders %s do not match the %d x %d depth image" % (tuple(r.shape), H, W))
+    P = r.numel() // (H * W)
+    r = r.reshape(P, H, W)
+    if int(off[-1]) != P:
+        raise ValueError("scene.explain: cand_off ends at %d for %d renders" % (int(off[-1]), P))
+    out = dict(chosen=torch.empty((I, M), dtype=torch.int32, device=dev), gain=torch.empty((I, M), dtype=torch.int64, device=dev),
+               net=torch.empty((I, M), dtype=torch.int64, device=dev), static=torch.empty((P, 3), dtype=torch.int64, device=dev),
+               labels=torch.empty((I, H, W), dtype=torch.uint8, device=dev),
+               summary=torch.empty((I, 3), dtype=torch.int64, device=dev))
+    L = _lib.load()
+    need = int(L.cppf_scene_explain_workspace_bytes(I, H, W, M))
+    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    _lib.check(L.cppf_scene_explain(I, H, W, ops._p(d), ops._p(m), off.ctypes.data_as(C.c_void_p), P, ops._p(r), C.c_float(tau),
+                                    min_gain, viol_weight, M, ops._p(out["chosen"]), ops._p(out["gain"]), ops._p(out["net"]),
+                                    ops._p(out["static"]), ops._p(out["labels"]), ops._p(out["summary"]), ops._p(ws), need,
+                                    ops._stream()), "cppf_scene_explain")
+    return out
+
+
+def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, min_gain=MIN_GAIN, viol_weight=VIOL_WEIGHT,
+                       max_rounds=MAX_ROUNDS, chunk=None):
+    """Explains one depth image [H,W] (metres) by candidate poses: records (RESULT_DTYPE [C], C <= 64; R, t in the record
+    convention of verify.py) of the objects objs (one bop.ObjectInfo or render.Mesh, or a list of them) with obj_of int [C] (the
+    index into objs of each record; None: all are objs[0]).  The candidates are rendered as verify.select renders its
+    hypotheses -- back faces culled; a record flagged empty, one that is not finite, or one that puts a vertex nearer than
+    render.ZNEAR is not drawn, fits nothing and is never chosen -- and given to explain() with the region [H,W].
+
+    Returns dict(records RESULT_DTYPE [n] (the chosen records, in the order they were chosen), chosen int64 [n] (their indices
+    in `records`), gain, net int64 [n], static int64 [C,3], labels uint8 [H,W] (host), region_pixels, explained_pixels)."""
+    off_check = _checked([0, len(records)], tau, min_gain, viol_weight, max_rounds, "scene.explain_candidates")
+    import torch
+    from . import bop, ops, verify
+    from .pipeline import RESULT_DTYPE
+    objs = list(objs) if isinstance(objs, (list, tuple)) else [objs]
+    objs = [o if isinstance(o, bop.ObjectInfo) else bop.ObjectInfo.from_mesh(o) for o in objs]
+    host = np.ascontiguousarray(records, dtype=RESULT_DTYPE).reshape(-1).copy()
+    Cn = host.size
+    of = np.zeros(Cn, dtype=np.int64) if obj_of is None else np.asarray(obj_of, dtype=np.int64).reshape(-1)
+    if of.size != Cn or (Cn and (of.min() < 0 or of.max() >= len(objs))):
+        raise ValueError("scene.explain_candidates: obj_of names an object of objs for each of the %d records" % Cn)
+    dev = ops._dev()
+    d = ops._t(depth, torch.float32, dev)
+    if d.dim() != 2:
+        raise ValueError("scene.explain_candidates: one depth image [H,W], not %s" % (tuple(d.shape),))
+    Hi, Wi = (int(x) for x in d.shape)
+    ren = torch.zeros((Cn, Hi, Wi), dtype=torch.float32, device=dev)
+    empty = (host["flags"] & verify.EMPTY) != 0
+    R, t = host["R"].reshape(-1, 3, 3), host["t"].reshape(-1, 3)
+    for o, obj in enumerate(objs):
+        idx = np.flatnonzero(of == o)
+        draw = verify.drawable(obj, R[idx], t[idx], ~empty[idx])
+        for a in range(0, idx.size, int(chunk or verify.RENDER_CHUNK)):
+            part = slice(a, a + int(chunk or verify.RENDER_CHUNK))
+            ren[torch.from_numpy(idx[part]).to(dev)] = verify.render_records(obj, R[idx[part]], t[idx[part]], draw[part], K, Hi, Wi, dev)
+    out = explain(d, region, off_check[0], ren, tau, min_gain, viol_weight, max_rounds)
+    summary = out["summary"][0].cpu().numpy()
+    n = int(summary[2])
+    pick = out["chosen"][0, :n].cpu().numpy().astype(np.int64)
+    return dict(records=host[pick].copy(), chosen=pick, gain=out["gain"][0, :n].cpu().numpy(), net=out["net"][0, :n].cpu().numpy(),
+                static=out["static"].cpu().numpy(), labels=out["labels"][0].cpu().numpy(), region_pixels=int(summary[0]),
+                explained_pixels=int(summary[1]))

@@ -124,6 +124,30 @@ def _as_records(records):
     return host, torch.from_numpy(raw).to(dev)
 
 
+def drawable(obj, R, t, ok):
+    """bool [P]: the poses (R float64 [P,3,3], t [P,3]) of obj (a bop.ObjectInfo) among `ok` that can be rendered: finite, and
+    no vertex nearer than render.ZNEAR (the renderer does not clip)."""
+    ok = np.asarray(ok, dtype=bool) & np.isfinite(R).all((1, 2)) & np.isfinite(t).all(1)
+    z = np.full(len(R), -np.inf)
+    if ok.any():
+        z[ok] = np.einsum("pj,vj->pv", R[ok, 2, :], obj.verts).min(1) + t[ok, 2]
+    return ok & (z >= render.ZNEAR * (1 + 1e-5))
+
+
+def render_records(obj, R, t, draw, K, Hi, Wi, dev):
+    """float32 [P,Hi,Wi] device tensor: obj at each pose with draw[p] set, back faces culled, in one cppf_render_depth call;
+    zeros (nothing drawn) for the others."""
+    dr = np.flatnonzero(draw)
+    ren = torch.zeros((len(R), Hi, Wi), dtype=torch.float32, device=dev)
+    if dr.size:
+        verts, faces, _ = obj.device(dev)
+        F = faces.shape[0]
+        poses = torch.from_numpy(np.concatenate([R[dr], t[dr, :, None]], 2).reshape(-1, 12).astype(np.float32)).to(dev)
+        ren[torch.from_numpy(dr).to(dev)] = render.render_depth(verts, faces.repeat(dr.size, 1), ops._offsets([F] * dr.size, dev),
+                                                                poses, K, Hi, Wi, cull=True)
+    return ren
+
+
 def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_model=None, icp_iters=0, tau=TAU,
            chunk=RENDER_CHUNK, icp_depth=False, icp_model_weight=1.0):
     """Verifies H pose hypotheses of each of B instances and keeps one per instance.
@@ -172,26 +196,12 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
     R = host["R"].reshape(-1, 3, 3)
     t = host["t"].reshape(-1, 3)
     P = B * Hh
-    flat_empty = empty.reshape(-1)
-    finite = np.isfinite(R).all((1, 2)) & np.isfinite(t).all(1)
-    z = np.full(P, -np.inf)
-    ok = finite & ~flat_empty
-    if ok.any():
-        z[ok] = np.einsum("pj,vj->pv", R[ok, 2, :], obj.verts).min(1) + t[ok, 2]
-    draw = ok & (z >= render.ZNEAR * (1 + 1e-5))
+    draw = drawable(obj, R, t, ~empty.reshape(-1))
     counts = np.zeros((P, N_COUNTS + 1), dtype=np.int64)
-    verts, faces, _ = obj.device(dev)
-    F = faces.shape[0]
     img_of = np.repeat(np.arange(B), Hh)
     for a in range(0, P, int(chunk)):
         idx = np.arange(a, min(P, a + int(chunk)))
-        dr = idx[draw[idx]]
-        ren = torch.zeros((idx.size, Hi, Wi), dtype=torch.float32, device=dev)
-        if dr.size:
-            poses = torch.from_numpy(np.concatenate([R[dr], t[dr, :, None]], 2).reshape(-1, 12).astype(np.float32)).to(dev)
-            ren[torch.from_numpy(dr - a).to(dev)] = render.render_depth(verts, faces.repeat(dr.size, 1),
-                                                                        ops._offsets([F] * dr.size, dev), poses, K, Hi, Wi,
-                                                                        cull=True)
+        ren = render_records(obj, R[idx], t[idx], draw[idx], K, Hi, Wi, dev)
         # the chunk's hypotheses lie on consecutive images: offsets over all B images, zero-length outside the chunk
         hyp_off = np.searchsorted(img_of[idx], np.arange(B + 1), side="left").astype(np.int32)
         counts[idx] = fit_counts(d, m, hyp_off, ren, (tau,)).cpu().numpy()

@@ -73,6 +73,16 @@ What the image cannot provide is stated, not faked:
     mask would have; proposals wider than 1000 cells or with too few points are skipped and counted.  The report gains `plane`,
     `proposals` (pixels, bbox, pose; the verification score with --hypotheses > 1) and, with --hypotheses > 1, `best`: the
     proposal with the highest score, ties to the larger one.  --gt_pose scores `best` when it exists, else every proposal.
+  * `--data=depth --propose_masks --explain_scene [--explain_min_score=0.5 --explain_min_gain=200 --explain_viol_weight=1
+    --explain_max=16]` (with --hypotheses > 1 and a mesh) decides per image, not per mask (cppf2_amd.scene, cppf_scene_explain,
+    DESIGN.md section 22; not in the reference): the verified pose of every proposal with a verification score of at least
+    --explain_min_score is a candidate (the 64 best when there are more), the region is the union of the proposed masks, and
+    the candidates that together explain it, each pixel counted once, are chosen greedily.  The report gains `scene`:
+    `instances` in chosen order (proposal, object, R, t, score, gain, net), `explained_pixels`, `region_pixels`, `rejected`
+    (reason `below_min_score` or `no_gain`) and `dropped`; everything else in the report stays what it is without the flag.
+    `--models_dir=<BOP models dir> --pair_tables=<dir> [--obj_ids=1,5 --model_scale=0.001]` stands in for --mesh and
+    --pair_table: obj_%06d.ply (+ models_info.json) and obj_%06d.npz per object; the proposal path runs once per object id,
+    the candidates of all objects are pooled into one explanation, and every result, proposal and instance carries `obj_id`.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import collections
@@ -611,20 +621,70 @@ def _propose_flags(f):
     return p
 
 
+_EXPLAIN_FLAGS = ("explain_min_score", "explain_min_gain", "explain_viol_weight", "explain_max")
+
+
+def _explain_flags(f):
+    """scene.explain's parameters (and min_score) from the --explain_scene flags, or None when it is off; f.obj_ids becomes a
+    list of ints or None."""
+    given = [k_ for k_ in _EXPLAIN_FLAGS if getattr(f, k_) is not None]
+    if f.obj_ids is not None and not f.models_dir:
+        raise ValueError("--obj_ids names objects of a models folder: it needs --models_dir")
+    if not f.explain_scene:
+        if given:
+            raise ValueError("--%s sets how the scene is explained: it needs --explain_scene" % given[0])
+        if f.models_dir:
+            raise ValueError("--models_dir pools the candidates of several objects into one explanation: it needs --explain_scene")
+        return None
+    if f.propose is None:
+        raise ValueError("--explain_scene explains an image by the verified poses of its proposals: it needs --propose_masks")
+    if int(f.hypotheses) <= 1:
+        raise ValueError("--explain_scene takes verified poses: it needs --hypotheses > 1")
+    if f.models_dir:
+        if f.mesh or f.pair_table:
+            raise ValueError("--models_dir and --pair_tables stand in for --mesh and --pair_table: give the one object or the folders")
+        if not f.pair_tables:
+            raise ValueError("--models_dir votes from each object's table: it needs --pair_tables=<dir> (obj_%06d.npz per object)")
+        if f.gt_pose is not None:
+            raise ValueError("--gt_pose is the pose of the one object of --mesh: not with --models_dir")
+        if f.obj_ids is not None:
+            try:
+                ids = f.obj_ids if isinstance(f.obj_ids, (list, tuple)) else str(f.obj_ids).split(",")
+                f.obj_ids = [int(str(x_).strip()) for x_ in ids if str(x_).strip()]
+            except ValueError:
+                raise ValueError("--obj_ids is a comma-separated list of object ids, not %r" % (f.obj_ids,)) from None
+            if not f.obj_ids or len(set(f.obj_ids)) != len(f.obj_ids):
+                raise ValueError("--obj_ids names each object once, not %r" % (f.obj_ids,))
+    from cppf2_amd import scene
+    e = dict(min_score=0.5 if f.explain_min_score is None else float(f.explain_min_score),
+             min_gain=scene.MIN_GAIN if f.explain_min_gain is None else int(f.explain_min_gain),
+             viol_weight=scene.VIOL_WEIGHT if f.explain_viol_weight is None else int(f.explain_viol_weight),
+             max_rounds=scene.MAX_ROUNDS if f.explain_max is None else int(f.explain_max))
+    if not 0.0 <= e["min_score"] <= 1.0:
+        raise ValueError("--explain_min_score is a verification score in [0, 1], not %r" % (f.explain_min_score,))
+    if e["min_gain"] < 1:
+        raise ValueError("--explain_min_gain must be >= 1, not %d" % e["min_gain"])
+    if e["viol_weight"] < 0:
+        raise ValueError("--explain_viol_weight must be >= 0, not %d" % e["viol_weight"])
+    if not 1 <= e["max_rounds"] <= scene.ROUNDS_LIMIT:
+        raise ValueError("--explain_max must be in 1 .. %d, not %d" % (scene.ROUNDS_LIMIT, e["max_rounds"]))
+    return e
+
+
 def _checked_flags(**kw):
     """main()'s keyword arguments as a namespace, after every rule that ties one flag to another: the first broken rule raises
     its ValueError, before a device, a model or a file is touched.  Normalised on the way: icp_iters, hypotheses, centre_peaks
     ints; icp_depth, icp_model_weight; clean_masks true under either spelling."""
     f = types.SimpleNamespace(**kw)
     bop_mode = f.data == "bop"
-    on_mesh = f.data == "depth" and f.mesh
+    on_mesh = f.data == "depth" and (f.mesh or f.models_dir)
     if f.pair_table or f.pair_tables:
         # a known object's pair-feature table stands where the two models stood (run_table): no prior, no checkpoints
         flag = "--pair_table" if f.pair_table else "--pair_tables"
         if f.pair_table and f.data != "depth":
             raise ValueError("--pair_table is the table of the one object of --data=depth (--data=bop: --pair_tables=<dir>); "
                              "the synthetic and NOCS modes have no table")
-        if f.pair_tables and not bop_mode:
+        if f.pair_tables and not bop_mode and not f.models_dir:
             raise ValueError("--pair_tables is a folder of obj_%06d.npz tables for --data=bop (--data=depth: --pair_table=<npz>)")
         if f.teacher_prior:
             raise ValueError("%s votes from the table: it cannot be combined with --teacher_prior" % flag)
@@ -638,6 +698,7 @@ def _checked_flags(**kw):
     if f.mask_jump is not None and not (float(f.mask_jump) >= 0.0 and np.isfinite(float(f.mask_jump))):
         raise ValueError("--mask_jump is a distance in metres >= 0, not %r" % (f.mask_jump,))
     f.propose = _propose_flags(f)
+    f.explain = _explain_flags(f)
     if bop_mode and not (f.bop_root and f.out_csv):
         raise ValueError("--data=bop needs --bop_root (the dataset folder) and --out_csv (the results file to write)")
     if not bop_mode and f.detections is not None:
@@ -784,14 +845,23 @@ def _score_against_gt(item, bop_obj, d, K, gt_R, gt_t, r, b, reported, ver, icp_
 
 def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_scale=1000.0, mesh=None, mesh_scale=1.0, icp_iters=0,
                icp_depth=False, icp_model_weight=1.0, gt_pose=None, models_info=None, hypotheses=1, verify_tau=None,
-               centre_peaks=1, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None, propose=None):
+               centre_peaks=1, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None, propose=None,
+               explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001):
     """One depth + mask PNG pair (example_data layout): one instance, evaluated once per category of `categories`; with `mesh`
     its pose is refined (icp_iters), verified (hypotheses) and scored against gt_pose (BOP errors), see the module docstring.
     propose: segment.propose's keyword arguments; the proposed masks then stand where the one of `mask` stood, one instance
-    each in one batch per category."""
+    each in one batch per category.  explain: _explain_flags' dict (the report's `scene`); models_dir, pair_tables, obj_ids,
+    model_scale: the objects of the multi-object form, which stand where mesh and pair_table stood."""
     from PIL import Image
     from cppf2_amd import bop, icp, masks, render, verify
     dev = ops._dev()
+    if models_dir:
+        objects = _scene_objects(models_dir, pair_tables, obj_ids, model_scale, icp_iters)
+        d = np.array(Image.open(depth)).astype(np.float64) / float(depth_scale)
+        K = np.array(intrinsics if intrinsics is not None else REAL_INTRINSICS, dtype=np.float64).reshape(3, 3)
+        return _depth_proposals(setups, categories, vote, d, K, propose, None, None, None, None, "each object's model", icp_iters,
+                                icp_depth, icp_model_weight, hypotheses, verify.TAU if verify_tau is None else float(verify_tau),
+                                centre_peaks, None, debug, out, out_pkl, explain=explain, objects=objects, pair_tables=pair_tables)
     icp_model = icp.ModelPoints.from_mesh(render.load_mesh(mesh, mesh_scale)) if icp_iters > 0 else None
     bop_obj, bop_reported = None, []
     if gt_pose is not None:
@@ -810,7 +880,7 @@ def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_sca
     if propose is not None:
         return _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj, verify_obj,
                                 (gt_R, gt_t) if bop_obj is not None else None, os.path.basename(mesh or ""), icp_iters, icp_depth,
-                                icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl)
+                                icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl, explain=explain)
     m = np.array(Image.open(mask))
     m = (m[..., 0] if m.ndim == 3 else m) > 0
     cleaning = None
@@ -854,64 +924,121 @@ def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_sca
     return _finish(report, acc, categories, debug, out, out_pkl)
 
 
+def _scene_objects(models_dir, pair_tables, obj_ids, model_scale, icp_iters):
+    """The objects of the multi-object form, read through bop_data.Models as a BOP dataset's are: obj_%06d.ply of models_dir
+    (all of them without obj_ids) with their models_info.json entries, and obj_%06d.npz of pair_tables.  A list of dicts (obj_id,
+    obj: bop.ObjectInfo, icp_model, pair_table: the file's path; a missing table is an error when it is loaded)."""
+    from cppf2_amd import bop_data, icp
+    models = bop_data.Models(models_dir, model_scale)
+    if obj_ids is None:
+        obj_ids = models.ids()
+        if not obj_ids:
+            raise FileNotFoundError("--models_dir=%s holds no obj_%%06d.ply" % models_dir)
+    return [dict(obj_id=int(o), obj=models.object(o), icp_model=icp.ModelPoints.from_mesh(models.mesh(o)) if icp_iters > 0 else None,
+                 pair_table=os.path.join(str(pair_tables), "obj_%06d.npz" % int(o))) for o in obj_ids]
+
+
+def _explain_scene(cands, objs, d, region, K, tau, explain):
+    """The report's `scene` entry: the candidates (dicts with proposal, category, score, record, obj: index into objs, and
+    obj_id in the multi-object form) with a score of at least min_score, the 64 best of them when there are more (ties to the
+    lower index), explained over `region` by scene.explain_candidates."""
+    from cppf2_amd import scene
+    from cppf2_amd.pipeline import RESULT_DTYPE
+
+    def entry(c_, **more):
+        e = {k_: c_[k_] for k_ in ("proposal", "category", "obj_id") if k_ in c_}
+        e.update(score=c_["score"], **more)
+        return e
+    rejected = [entry(c_, reason="below_min_score") for c_ in cands if not c_["score"] >= explain["min_score"]]
+    kept = [c_ for c_ in cands if c_["score"] >= explain["min_score"]]
+    order = sorted(range(len(kept)), key=lambda j: (-kept[j]["score"], j))[:scene.MAX_CANDIDATES]
+    dropped = len(kept) - len(order)
+    kept = [kept[j] for j in sorted(order)]
+    recs = np.array([c_["record"] for c_ in kept], dtype=RESULT_DTYPE).reshape(-1)
+    ex = scene.explain_candidates(objs, d.astype(np.float32), region, K, recs, [c_["obj"] for c_ in kept], tau=tau,
+                                  min_gain=explain["min_gain"], viol_weight=explain["viol_weight"], max_rounds=explain["max_rounds"])
+    instances = []
+    for j, g, n in zip(ex["chosen"], ex["gain"], ex["net"]):
+        rec = kept[int(j)]["record"]
+        instances.append(entry(kept[int(j)], R=np.asarray(rec["R"], dtype=np.float64).reshape(3, 3).tolist(),
+                               t=np.asarray(rec["t"], dtype=np.float64).tolist(), gain=int(g), net=int(n)))
+    taken = {int(j) for j in ex["chosen"]}
+    rejected += [entry(c_, reason="no_gain") for j, c_ in enumerate(kept) if j not in taken]
+    return dict(instances=instances, explained_pixels=ex["explained_pixels"], region_pixels=ex["region_pixels"], rejected=rejected,
+                dropped=dropped, candidates=len(kept),
+                parameters=dict(explain, tau=float(tau)))
+
+
 def _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj, verify_obj, gt, against, icp_iters, icp_depth,
-                     icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl):
+                     icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl, explain=None,
+                     objects=None, pair_tables=None):
     """main_depth with proposed masks (segment.propose on the depth image d, metres, with the run's seed): per category one batch
     whose instances are the proposals that give a usable cloud, each with the cloud, scene index and tuple streams a --mask run
-    of its mask has.  gt: (R, t) of --gt_pose or None."""
+    of its mask has.  gt: (R, t) of --gt_pose or None.  explain: _explain_flags' dict: the verified poses become the candidates
+    of _explain_scene.  objects: _scene_objects' list (the multi-object form): the batches run once per object, with its mesh
+    and table where verify_obj, icp_model and pair_table stood, and every item carries obj_id."""
     from cppf2_amd import bop, segment
     dev = ops._dev()
     pm, props, plane = segment.propose(d.astype(np.float32), K, vote.seed, **propose)
     pmasks = pm.cpu().numpy() > 0
     acc = Results([], [], [], [], [], [])
     skipped = dict(too_large=0, too_few_points=0)
-    proposals, best, bop_reported = [], None, []
-    for ci, cat in enumerate(categories):
-        cfg = setups[cat][0]
-        up_sym = cat in UP_SYM or bool(cfg.get("up_sym", False))
-        ranks, pcs = [], []
-        for p_, m in enumerate(pmasks):
-            pc = instance_cloud(d, K, m, cfg.res, vote.seed)
-            if pc.shape[0] < cfg.num_more + 2:
-                skipped["too_few_points"] += 1
-            elif too_wide(pc, cfg.res):                                                    # eval.py:200
-                skipped["too_large"] += 1
-            else:
-                ranks.append(p_)
-                pcs.append(pc)
-        B = len(pcs)
-        if not B:
-            continue
-        descs = [] if pair_table else [stand_in_descriptors(pc.shape[0], vote.seed + 1 + ci).numpy() for pc in pcs]
-        r, enabled = vote_batch(setups[cat], pcs, descs, [ci] * B, vote, up_sym, hypotheses=hypotheses, centre_peaks=centre_peaks,
-                                table=load_pair_table(pair_table, dev) if pair_table else None)
-        images = hypotheses > 1 or icp_depth
-        reported, icp_stats, ver = refine_and_verify(
-            r, hypotheses, enabled, verify_obj, np.broadcast_to(d.astype(np.float32), (B,) + d.shape) if images else None,
-            pmasks[ranks] if images else None, K, np.cumsum([0] + [pc.shape[0] for pc in pcs]), icp_model, icp_iters, verify_tau,
-            icp_depth, icp_model_weight)
-        _add_results(acc, cat, [ci] * B, r, reported, up_sym)
-        items = acc.summary[-B:]
-        top = None
-        for b, item in enumerate(items):
-            item.update(instance_items(r, b, icp_stats, ver, centre_peaks))
-            item.update(proposal=ranks[b], pixels=props[ranks[b]]["pixels"], bbox=props[ranks[b]]["bbox"], points=int(pcs[b].shape[0]))
-            entry = dict(proposal=ranks[b], category=cat, pixels=item["pixels"], bbox=item["bbox"], R=None, t=None)
-            if r["pick"][b] >= 0:
-                entry.update(R=np.asarray(reported[b]["R"], dtype=np.float64).reshape(3, 3).tolist(),
-                             t=np.asarray(reported[b]["t"], dtype=np.float64).tolist())
-                if ver is not None:
-                    entry["score"] = item["verify"]["score"]
-                    if top is None or entry["score"] > items[top]["verify"]["score"]:      # ties: the lower rank stays
-                        top = b
-            proposals.append(entry)
-        if top is not None and (best is None or items[top]["verify"]["score"] > best["score"]):
-            best = dict(proposal=ranks[top], category=cat, score=items[top]["verify"]["score"])
-        if bop_obj is not None:
-            # --gt_pose: the best proposal when the verification chose one, else every proposal; the keys of the --mask route
-            for b in ([top] if ver is not None else range(B)):
-                if b is not None:
-                    bop_reported.append(_score_against_gt(items[b], bop_obj, d, K, gt[0], gt[1], r, b, reported, ver, icp_stats))
+    proposals, best, bop_reported, cands = [], None, [], []
+    multi = objects is not None
+    if not multi:
+        objects = [dict(obj=verify_obj, icp_model=icp_model, pair_table=pair_table)]
+    for oi, ob in enumerate(objects):
+        tag = dict(obj_id=ob["obj_id"]) if multi else {}
+        verify_obj, icp_model, pair_table = ob["obj"], ob["icp_model"], ob["pair_table"]
+        for ci, cat in enumerate(categories):
+            cfg = setups[cat][0]
+            up_sym = cat in UP_SYM or bool(cfg.get("up_sym", False))
+            ranks, pcs = [], []
+            for p_, m in enumerate(pmasks):
+                pc = instance_cloud(d, K, m, cfg.res, vote.seed)
+                if pc.shape[0] < cfg.num_more + 2:
+                    skipped["too_few_points"] += 1
+                elif too_wide(pc, cfg.res):                                                    # eval.py:200
+                    skipped["too_large"] += 1
+                else:
+                    ranks.append(p_)
+                    pcs.append(pc)
+            B = len(pcs)
+            if not B:
+                continue
+            descs = [] if pair_table else [stand_in_descriptors(pc.shape[0], vote.seed + 1 + ci).numpy() for pc in pcs]
+            r, enabled = vote_batch(setups[cat], pcs, descs, [ci] * B, vote, up_sym, hypotheses=hypotheses, centre_peaks=centre_peaks,
+                                    table=load_pair_table(pair_table, dev) if pair_table else None)
+            images = hypotheses > 1 or icp_depth
+            reported, icp_stats, ver = refine_and_verify(
+                r, hypotheses, enabled, verify_obj, np.broadcast_to(d.astype(np.float32), (B,) + d.shape) if images else None,
+                pmasks[ranks] if images else None, K, np.cumsum([0] + [pc.shape[0] for pc in pcs]), icp_model, icp_iters, verify_tau,
+                icp_depth, icp_model_weight)
+            _add_results(acc, cat, [ci] * B, r, reported, up_sym)
+            items = acc.summary[-B:]
+            top = None
+            for b, item in enumerate(items):
+                item.update(instance_items(r, b, icp_stats, ver, centre_peaks))
+                item.update(proposal=ranks[b], pixels=props[ranks[b]]["pixels"], bbox=props[ranks[b]]["bbox"], points=int(pcs[b].shape[0]),
+                            **tag)
+                entry = dict(proposal=ranks[b], category=cat, pixels=item["pixels"], bbox=item["bbox"], R=None, t=None, **tag)
+                if r["pick"][b] >= 0:
+                    entry.update(R=np.asarray(reported[b]["R"], dtype=np.float64).reshape(3, 3).tolist(),
+                                 t=np.asarray(reported[b]["t"], dtype=np.float64).tolist())
+                    if ver is not None:
+                        entry["score"] = item["verify"]["score"]
+                        if top is None or entry["score"] > items[top]["verify"]["score"]:      # ties: the lower rank stays
+                            top = b
+                        cands.append(dict(proposal=ranks[b], category=cat, score=entry["score"], record=reported[b].copy(), obj=oi,
+                                          **tag))
+                proposals.append(entry)
+            if top is not None and (best is None or items[top]["verify"]["score"] > best["score"]):
+                best = dict(proposal=ranks[top], category=cat, score=items[top]["verify"]["score"], **tag)
+            if bop_obj is not None:
+                # --gt_pose: the best proposal when the verification chose one, else every proposal; the keys of the --mask route
+                for b in ([top] if ver is not None else range(B)):
+                    if b is not None:
+                        bop_reported.append(_score_against_gt(items[b], bop_obj, d, K, gt[0], gt[1], r, b, reported, ver, icp_stats))
     report = dict(categories=categories, instances=len(acc.summary),
                   opt_refinement="100 Adam steps (cppf_refine_pose)" if vote.opt else "off", results=acc.summary,
                   plane=dict(n=plane["n"], d=plane["d"], inliers=plane["inliers"], usable_hypotheses=plane["usable_hypotheses"],
@@ -921,14 +1048,19 @@ def _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj
                                       large_components=plane["large_components"]))
     if best is not None:
         report["best"] = best
-    if pair_table:
+    if multi:
+        report.update(obj_ids=[ob["obj_id"] for ob in objects], pair_tables=str(pair_tables),
+                      table_hits=[s_["table_hits"] for s_ in acc.summary])
+    elif pair_table:
         report.update(pair_table=str(pair_table), table_hits=[s_["table_hits"] for s_ in acc.summary])
     report.update(stage_notes(against, icp_iters, icp_depth, icp_model_weight, hypotheses, verify_tau, centre_peaks, None))
-    if icp_model is not None:
+    if icp_iters > 0:
         report["icp"] = [s_["icp"] for s_ in acc.summary if "icp" in s_]
     if bop_reported:
         errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
         report["bop"] = dict(bop.average_recall(errs, bop_obj.diameter, d.shape[1]), delta=bop.DELTA, taus=list(bop.TAUS))
+    if explain is not None:
+        report["scene"] = _explain_scene(cands, [ob["obj"] for ob in objects], d, pmasks.any(0), K, verify_tau, explain)
     return _finish(report, acc, categories, debug, out, out_pkl)
 
 
@@ -941,7 +1073,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          teacher_prior=False, model_scale=0.001, centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False,
          clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0, pair_table=None, pair_tables=None,
          propose_masks=False, plane_tau=None, plane_hypotheses=None, plane_min_height=None, min_segment_pixels=None,
-         max_proposals=None):
+         max_proposals=None, explain_scene=False, explain_min_score=None, explain_min_gain=None, explain_viol_weight=None,
+         explain_max=None, models_dir=None, obj_ids=None):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()
@@ -968,7 +1101,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
     categories = [c for c in categories if c in WHITELIST or custom]
     # eval.py:84-101: models and cfgs of every category up front
     if custom:
-        setups = {"custom": load_custom(ckpt_shot, ckpt_dino, device=dev, models=not pair_table)}
+        setups = {"custom": load_custom(ckpt_shot, ckpt_dino, device=dev, models=not (pair_table or models_dir))}
     else:
         setups = {c: load_category(c, ckpt_dir, ckpt_shot, ckpt_dino, device=dev) for c in categories}
     if data == "nocs":
@@ -980,7 +1113,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                           mesh_scale=mesh_scale, icp_iters=f.icp_iters, icp_depth=f.icp_depth, icp_model_weight=f.icp_model_weight,
                           gt_pose=gt_pose, models_info=models_info, hypotheses=f.hypotheses, verify_tau=verify_tau,
                           centre_peaks=f.centre_peaks, clean_mask=f.clean_masks, mask_jump=mask_jump, pair_table=pair_table,
-                          debug=debug, out=out, out_pkl=out_pkl, propose=f.propose)
+                          debug=debug, out=out, out_pkl=out_pkl, propose=f.propose, explain=f.explain, models_dir=models_dir,
+                          pair_tables=pair_tables, obj_ids=f.obj_ids, model_scale=float(model_scale))
     return main_synthetic(setups, categories, vote, num_scenes=num_scenes, num_points=num_points, debug=debug, out=out,
                           out_pkl=out_pkl)
 

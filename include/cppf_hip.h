@@ -545,6 +545,31 @@ int cppf_pose_hypotheses(int B, int S, const float* counts_up, const float* coun
 int cppf_depth_fit_counts(int I, int H, int W, const float* depth, const uint8_t* mask, const int32_t* h_hyp_off, int P,
                           const float* renders, const float* taus, int n_taus, int64_t* counts, void* stream);
 
+/* ---- scene explanation: a consistent set of verified poses per depth image (not in the reference; cppf2_amd/scene.py) ---
+ * Of the candidate renders of an image, the subset that together explains the observed depth, each pixel counted once,
+ * chosen greedily.  The exact rules are stated in cppf2_amd/csrc/cppf_scene.hip.  Integer counts and integer maxima only: an
+ * image's outputs do not depend on the batch or the order.
+ *
+ * cppf_scene_explain: I >= 1 observed images depth float32[I,H,W] (metres, 0 = no reading) with the regions to explain
+ * uint8[I,H,W] (!= 0), H, W <= 8192; P renders float32[P,H,W] (0 = nothing drawn), h_cand_off int32[I+1] on the HOST as
+ * cppf_depth_fit_counts' h_hyp_off (0 = h_cand_off[0] <= ... <= h_cand_off[I] = P <= 2^24), at most 64 candidates per image.  Per pixel and candidate c, with cppf_depth_fit_counts'
+ * predicates at the one tau (>= 0, metres): drawn, fit (region && d_o > 0 && d_c > 0 && |d_c - d_o| <= tau) and violation.
+ * stat int64[P,3] = (drawn, fit, violations) per render.  Round k = 0 .. max_rounds-1 (1 <= max_rounds <= 64): gain_c = the
+ * pixels no earlier winner explained that c fits, net_c = gain_c - viol_weight * violations_c (int64; viol_weight >= 0); the
+ * winner is the candidate with the largest net_c >= min_gain (>= 1), ties to the lowest c; its fit pixels become explained.
+ * The rounds end when no candidate is eligible.  chosen int32[I,max_rounds] (the winner's index within its image, -1 past
+ * the end), gain, net int64[I,max_rounds] (0 past the end), labels uint8[I,H,W] (the round that explained the pixel, 255:
+ * none), summary int64[I,3] = (pixels with region && d_o > 0, explained pixels, rounds used).  workspace:
+ * cppf_scene_explain_workspace_bytes(I, H, W, max_rounds) bytes (8 per pixel plus 256 per image and round; 0 for sizes the call
+ * refuses), 8-byte aligned.  max_rounds + 2 launches per 128 images behind the clears of the outputs, no host synchronisation.
+ * Returns CPPF_EUNSUPPORTED for more than 64 candidates on an image, CPPF_ECAPACITY for a workspace that is too small and
+ * CPPF_EINVAL for every other broken rule, all before any device work. */
+int64_t cppf_scene_explain_workspace_bytes(int I, int H, int W, int max_rounds);
+int cppf_scene_explain(int I, int H, int W, const float* depth, const uint8_t* region, const int32_t* h_cand_off, int P,
+                       const float* renders, float tau, int min_gain, int viol_weight, int max_rounds, int32_t* chosen,
+                       int64_t* gain, int64_t* net, int64_t* stat, uint8_t* labels, int64_t* summary, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+
 /* DINO-branch feature plumbing: replaces interpolate_features (dataset.py:40-59) = grid_sample
  * (bilinear, zeros padding, align_corners=False) of the patch-token map desc at the pixel centres of pts float32[n,2]
  * (x, y), then L2 normalisation over the C channels.  desc is addressed as desc[c*stride_c + y*stride_y + x*stride_x]
