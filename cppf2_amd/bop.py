@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops, render
+from . import _lib, hostargs, ops, render
 from ._lib import CppfError
 
 _L = _lib.load()
@@ -155,36 +155,25 @@ def load_pose(path):
     return M[:3, :3].copy(), M[:3, 3].copy()
 
 
-def _hK(K):
-    K = np.asarray(K, dtype=np.float64).reshape(3, 3)
-    return (C.c_double * 4)(K[0, 0], K[1, 1], K[0, 2], K[1, 2])
-
-
-def _depth3(depth, dev):
-    d = ops._t(depth, torch.float32, dev)
-    return d[None] if d.dim() == 2 else d
-
-
 def vsd_counts(depth_test, test_idx, depth_est, depth_gt, K, diam, delta=DELTA, taus=TAUS):
     """cppf_vsd_counts: int64 [P, 2 + n_taus] device tensor (union, intersection, cost_1 .. cost_n) of P pairs.  depth_test
     [I,H,W] or [H,W] (metres, 0 = no reading), test_idx int [P], depth_est / depth_gt [P,H,W] (renders, 0 = nothing drawn),
     diam: one diameter or one per pair (metres), taus: fractions of the diameter (at most 32)."""
     dev = ops._dev()
-    dt = _depth3(depth_test, dev)
+    dt = hostargs.image_batch(depth_test, dev, "bop.vsd_counts")
     I, H, W = dt.shape
     de = ops._t(depth_est, torch.float32, dev).reshape(-1, H, W)
     dg = ops._t(depth_gt, torch.float32, dev).reshape(-1, H, W)
     P = de.shape[0]
-    ti = ops._t(np.broadcast_to(np.asarray(test_idx, dtype=np.int32), (P,)) if not torch.is_tensor(test_idx) else test_idx,
-                torch.int32, dev).reshape(-1)
-    if dg.shape[0] != P or ti.numel() != P:
-        raise CppfError("bop.vsd_counts: %d estimate renders, %d ground-truth renders, %d test indices" % (P, dg.shape[0], ti.numel()))
-    dm = ops._t(np.broadcast_to(np.asarray(diam, dtype=np.float32), (P,)) if not torch.is_tensor(diam) else diam,
-                torch.float32, dev).reshape(-1)
+    if dg.shape[0] != P:
+        raise CppfError("bop.vsd_counts: %d estimate renders, %d ground-truth renders" % (P, dg.shape[0]))
+    ti = hostargs.per_item(test_idx, P, torch.int32, dev, "bop.vsd_counts", "test indices", CppfError)
+    dm = hostargs.per_item(diam, P, torch.float32, dev, "bop.vsd_counts", "diameters", CppfError)
     tau = ops._t(np.asarray(taus, dtype=np.float32).reshape(-1), torch.float32, dev)
     counts = torch.empty((P, 2 + tau.numel()), dtype=torch.int64, device=dev)
-    _lib.check(_L.cppf_vsd_counts(P, I, H, W, ops._p(dt), ops._p(ti), ops._p(de), ops._p(dg), _hK(K), C.c_double(float(delta)),
-                                  ops._p(dm), ops._p(tau), tau.numel(), ops._p(counts), ops._stream()), "cppf_vsd_counts")
+    _lib.check(_L.cppf_vsd_counts(P, I, H, W, ops._p(dt), ops._p(ti), ops._p(de), ops._p(dg), hostargs.camera4(K),
+                                  C.c_double(float(delta)), ops._p(dm), ops._p(tau), tau.numel(), ops._p(counts), ops._stream()),
+               "cppf_vsd_counts")
     return counts
 
 
@@ -213,8 +202,8 @@ def mssd_mspd(verts, syms, pose_est, pose_gt, K):
     mspd = torch.empty((P,), dtype=torch.float32, device=dev)
     for a in range(0, max(P, 1), MAX_PAIRS):
         n = min(MAX_PAIRS, P - a)
-        _lib.check(_L.cppf_mssd_mspd(n, ops._p(v), v.shape[0], ops._p(S_), S_.shape[0], ops._p(pe[a:]), ops._p(pg[a:]), _hK(K),
-                                     ops._p(mssd[a:]), ops._p(mspd[a:]), ops._stream()), "cppf_mssd_mspd")
+        _lib.check(_L.cppf_mssd_mspd(n, ops._p(v), v.shape[0], ops._p(S_), S_.shape[0], ops._p(pe[a:]), ops._p(pg[a:]),
+                                     hostargs.camera4(K), ops._p(mssd[a:]), ops._p(mspd[a:]), ops._stream()), "cppf_mssd_mspd")
     return mssd, mspd
 
 
@@ -223,22 +212,19 @@ def gt_visibility_counts(depth_test, img_idx, renders, K, delta=DELTA, masks=Fal
     mask uint8 [G,H,W] (255 = visible) or None) device tensors.  depth_test [I,H,W] or [H,W] (metres, 0 = no reading), img_idx
     int [G] (or one for all), renders [G,H,W] (each instance rendered alone, 0 = nothing drawn)."""
     dev = ops._dev()
-    dt = _depth3(depth_test, dev)
+    dt = hostargs.image_batch(depth_test, dev, "bop.gt_visibility_counts")
     I, H, W = dt.shape
     rn = ops._t(renders, torch.float32, dev).reshape(-1, H, W)
     G = rn.shape[0]
-    ii = ops._t(np.broadcast_to(np.asarray(img_idx, dtype=np.int32), (G,)) if not torch.is_tensor(img_idx) else img_idx,
-                torch.int32, dev).reshape(-1)
-    if ii.numel() != G:
-        raise CppfError("bop.gt_visibility_counts: %d renders, %d image indices" % (G, ii.numel()))
+    ii = hostargs.per_item(img_idx, G, torch.int32, dev, "bop.gt_visibility_counts", "image indices", CppfError)
     counts = torch.empty((G, 3), dtype=torch.int64, device=dev)
     bbox = torch.empty((G, 8), dtype=torch.int32, device=dev)
     mask = torch.empty((G, H, W), dtype=torch.uint8, device=dev) if masks else None
     for a in range(0, max(G, 1), MAX_PAIRS):
         n = min(MAX_PAIRS, G - a)
-        _lib.check(_L.cppf_gt_visibility(n, I, H, W, ops._p(dt), ops._p(ii[a:]), ops._p(rn[a:]), _hK(K), C.c_double(float(delta)),
-                                         ops._p(counts[a:]), ops._p(bbox[a:]), ops._p(mask[a:]) if masks else None,
-                                         ops._stream()), "cppf_gt_visibility")
+        _lib.check(_L.cppf_gt_visibility(n, I, H, W, ops._p(dt), ops._p(ii[a:]), ops._p(rn[a:]), hostargs.camera4(K),
+                                         C.c_double(float(delta)), ops._p(counts[a:]), ops._p(bbox[a:]),
+                                         ops._p(mask[a:]) if masks else None, ops._stream()), "cppf_gt_visibility")
     return counts, bbox, mask
 
 
@@ -256,7 +242,7 @@ def gt_visibility(obj_or_objs, depth_test, img_idx, R, t, K, delta=DELTA, masks=
     objs = list(obj_or_objs) if isinstance(obj_or_objs, (list, tuple)) else [obj_or_objs] * G
     if len(objs) != G:
         raise ValueError("bop.gt_visibility: %d objects for %d poses" % (len(objs), G))
-    dt = _depth3(depth_test, dev)
+    dt = hostargs.image_batch(depth_test, dev, "bop.gt_visibility")
     _, H, W = dt.shape
     ii = np.broadcast_to(np.asarray(img_idx, dtype=np.int32).reshape(-1), (G,))
     uniq, first = [], {}
@@ -321,7 +307,7 @@ def pose_errors(obj, depth_test, test_idx, R_est, t_est, R_gt, t_gt, K, delta=DE
     z_gt = np.einsum("pj,vj->pv", pg[:, 2, :3], v64).min(1) + pg[:, 2, 3]
     if not (z_gt >= render.ZNEAR).all():
         raise ValueError("bop.pose_errors: a ground-truth pose puts the model nearer than %g m" % render.ZNEAR)
-    dt = _depth3(depth_test, dev)
+    dt = hostargs.image_batch(depth_test, dev, "bop.pose_errors")
     I, H, W = dt.shape
     ti = np.broadcast_to(np.asarray(test_idx, dtype=np.int64).reshape(-1), (P,))
     if ti.min() < 0 or ti.max() >= I:

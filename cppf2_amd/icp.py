@@ -16,7 +16,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops, shot
+from . import _lib, hostargs, ops, pipeline
 from ._lib import CppfError
 
 _L = _lib.load()
@@ -65,53 +65,17 @@ class ModelPoints:
         return self._dev[key]
 
 
-_WS = {}                 # (device index, stream) -> workspace tensor
-WS_CACHE_MAX = 8
-
-
-def _workspace(B, max_n, dev):
-    key = shot._key(dev)
-    ws = _WS.pop(key, None)
-    need = _L.cppf_icp_workspace_bytes(B, max_n)
-    if need < 0:
-        raise CppfError("cppf_icp_workspace_bytes: invalid sizes B=%d max_n=%d" % (B, max_n))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    _WS[key] = ws
-    while len(_WS) > WS_CACHE_MAX:
-        del _WS[next(iter(_WS))]
-    return ws
-
-
-_WS_DEPTH = {}           # the same for cppf_icp_refine_depth
-
-
-def _workspace_depth(B, max_n, M, dev):
-    key = shot._key(dev)
-    ws = _WS_DEPTH.pop(key, None)
-    need = _L.cppf_icp_depth_workspace_bytes(B, max_n, M)
-    if need < 0:
-        raise CppfError("cppf_icp_depth_workspace_bytes: invalid sizes B=%d max_n=%d M=%d" % (B, max_n, M))
-    if ws is None or ws.numel() < need:
-        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-    _WS_DEPTH[key] = ws
-    while len(_WS_DEPTH) > WS_CACHE_MAX:
-        del _WS_DEPTH[next(iter(_WS_DEPTH))]
-    return ws
+_WS = hostargs.ScratchCache("cppf_icp_workspace_bytes", CppfError)                 # workspaces per (device index, stream)
+_WS_DEPTH = hostargs.ScratchCache("cppf_icp_depth_workspace_bytes", CppfError)
 
 
 def _depth_args(depth, img_idx, K, model_weight, B):
-    """The host side of refine's depth arguments, checked before anything touches a device: (I, H, W, img_idx int32 [B] NumPy,
-    K float64 [9], model_weight)."""
-    shape = tuple(depth.shape)
-    if len(shape) == 2:
-        shape = (1,) + shape
-    if len(shape) != 3 or min(shape) < 1:
-        raise ValueError("icp.refine: depth must be a non-empty [H,W] or [I,H,W] image batch, not %s" % (tuple(depth.shape),))
-    dt = depth.dtype
-    if dt not in (torch.float32, np.dtype(np.float32)):
-        raise ValueError("icp.refine: depth must be float32 metres, not %s" % (dt,))
-    I = shape[0]
+    """refine's depth arguments, checked before a device is asked for (a machine without one gets these errors): (depth as a
+    contiguous float32 [I,H,W] batch where it already is, img_idx int32 [B] NumPy, K float64 [9], model_weight)."""
+    if depth.dtype not in (torch.float32, np.dtype(np.float32)):
+        raise ValueError("icp.refine: depth must be float32 metres, not %s" % (depth.dtype,))
+    depth = hostargs.image_batch(depth, depth.device if torch.is_tensor(depth) else "cpu", "icp.refine")
+    I = depth.shape[0]
     if K is None:
         raise ValueError("icp.refine: depth needs K, the camera's 3x3 intrinsics")
     K = np.asarray(K, dtype=np.float64)
@@ -133,7 +97,7 @@ def _depth_args(depth, img_idx, K, model_weight, B):
         idx = (img_idx.cpu().numpy() if torch.is_tensor(img_idx) else np.asarray(img_idx)).astype(np.int32).reshape(-1)
         if idx.size != B:
             raise ValueError("icp.refine: img_idx of %d entries for %d instances" % (idx.size, B))
-    return I, shape[1], shape[2], idx, np.ascontiguousarray(K.reshape(9)), w
+    return depth, idx, np.ascontiguousarray(K.reshape(9)), w
 
 
 def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST, depth=None, img_idx=None, K=None, model_weight=1.0):
@@ -168,7 +132,7 @@ def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST, depth=No
     dev = ops._dev()
     host_records = isinstance(results, np.ndarray)
     if host_records:
-        rec = torch.from_numpy(np.frombuffer(results.tobytes(), dtype=np.uint8).reshape(-1, 160).copy()).to(dev)
+        rec = pipeline.record_bytes(results, dev)
     else:
         rec = results
         if rec.dtype != torch.uint8 or rec.dim() != 2 or rec.shape[1] != 160 or not rec.is_contiguous() or rec.device != dev:
@@ -191,20 +155,21 @@ def refine(model, pts, pt_off, results, iters=ITERS, max_dist=MAX_DIST, depth=No
     stats = torch.empty((B, ncol), dtype=torch.float32, device=dev)
     d0, d1 = (float(x) for x in max_dist)
     if depth is None:
-        ws = _workspace(B, max_n, dev)
+        ws = _WS.get(hostargs.stream_key(dev), _L.cppf_icp_workspace_bytes(B, max_n), dev)
         _lib.check(_L.cppf_icp_refine(B, ops._p(pts), ops._p(off), max_n, ops._p(mp), ops._p(mn), mp.shape[0], int(iters),
                                       C.c_float(d0), C.c_float(d1), ops._p(rec), ops._p(stats), ops._p(ws), ws.numel(),
                                       ops._stream()), "cppf_icp_refine")
     else:
-        I, H, W, idx, K9, w = dargs
-        dimg = ops._t(depth, torch.float32, dev).reshape(I, H, W).contiguous()
+        dimg, idx, K9, w = dargs
+        dimg = dimg.to(dev)
+        I, H, W = dimg.shape
         idx_d = torch.from_numpy(idx).to(dev)
-        ws = _workspace_depth(B, max_n, mp.shape[0], dev)
+        ws = _WS_DEPTH.get(hostargs.stream_key(dev), _L.cppf_icp_depth_workspace_bytes(B, max_n, mp.shape[0]), dev)
         _lib.check(_L.cppf_icp_refine_depth(B, ops._p(pts) if max_n > 0 else None, ops._p(off), max_n, ops._p(mp), ops._p(mn),
                                             mp.shape[0], ops._p(dimg), I, H, W, ops._p(idx_d), K9.ctypes.data_as(C.c_void_p),
                                             C.c_float(w), int(iters), C.c_float(d0), C.c_float(d1), ops._p(rec), ops._p(stats),
                                             ops._p(ws), ws.numel(), ops._stream()), "cppf_icp_refine_depth")
     if host_records:
-        results[...] = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=results.dtype).reshape(results.shape)
+        results[...] = pipeline.records_of(rec, results.shape)
         return stats.cpu().numpy()
     return stats

@@ -157,34 +157,23 @@ def clean(masks, depths, img_idx=0, jump=JUMP, min_pixels=MIN_PIXELS):
     pixel in row-major order comes first --, all 0 when it has fewer than min_pixels; int32 [D,4] device tensor: components,
     the kept one's lowest flat index or -1, its pixels, valid pixels).  No host synchronisation."""
     import torch
-    from . import _lib, ops
+    from . import _lib, hostargs, ops
     jump = float(jump)
     if not (jump >= 0.0 and np.isfinite(jump)):
         raise ValueError("masks.clean: jump must be a finite distance >= 0, not %r" % jump)
     dev = ops._dev()
-    dt = ops._t(depths, torch.float32, dev)
-    dt = dt.reshape((1,) + tuple(dt.shape)) if dt.dim() == 2 else dt
-    if dt.dim() != 3 or dt.shape[0] < 1:
-        raise ValueError("masks.clean: depths is [I,H,W] or [H,W], not %s" % (tuple(dt.shape),))
+    dt = hostargs.image_batch(depths, dev, "masks.clean")
     I, H, W = (int(x) for x in dt.shape)
-    if torch.is_tensor(masks):
-        mk = masks.to(dev)
-        mk = (mk.to(torch.uint8) * 255) if mk.dtype == torch.bool else mk.to(torch.uint8)
-    else:
-        mk = torch.from_numpy(np.ascontiguousarray((np.asarray(masks) != 0).astype(np.uint8) * 255)).to(dev)
-    mk = mk.reshape(-1, H, W).contiguous()
+    mk = hostargs.mask_batch(masks, dt, dev, "masks.clean")
     D = int(mk.shape[0])
-    ii = ops._t(np.broadcast_to(np.asarray(img_idx, dtype=np.int32), (D,)) if not torch.is_tensor(img_idx) else img_idx,
-                torch.int32, dev).reshape(-1)
-    if ii.numel() != D:
-        raise ValueError("masks.clean: %d masks, %d image indices" % (D, ii.numel()))
+    ii = hostargs.per_item(img_idx, D, torch.int32, dev, "masks.clean", "image indices")
     out = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
     stats = torch.empty((D, 4), dtype=torch.int32, device=dev)
     L = _lib.load()
     for a in range(0, D, MAX_MASKS):
         n = min(MAX_MASKS, D - a)
         need = int(L.cppf_mask_components_workspace_bytes(n, H, W))
-        ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.int64, device=dev)
+        ws = hostargs.scratch(need, dev, "cppf_mask_components_workspace_bytes", _lib.CppfError)
         _lib.check(L.cppf_mask_components(n, I, H, W, ops._p(mk[a:]), ops._p(dt), ops._p(ii[a:]), C.c_float(jump), int(min_pixels),
                                           ops._p(out[a:]), ops._p(stats[a:]), ops._p(ws), need, ops._stream()),
                    "cppf_mask_components")

@@ -17,7 +17,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, hostargs
 from ._lib import CppfError, SceneGrid, SceneResult
 
 _L = _lib.load()
@@ -67,10 +67,7 @@ def _sched():
 
 def _t(x, dtype, device=None):
     """torch tensor on the device with the given dtype, contiguous (accepts numpy / torch / lists)."""
-    device = device or _dev()
-    if isinstance(x, torch.Tensor):
-        return x.to(device=device, dtype=dtype).contiguous()
-    return torch.as_tensor(np.ascontiguousarray(x), device="cpu").to(device=device, dtype=dtype).contiguous()
+    return hostargs.tensor(x, dtype, device or _dev())
 
 
 def _axes9(a1, a2, a3):
@@ -920,7 +917,7 @@ def downsample(pc, res, seed=0, return_device=False):
     idx = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     cnt = torch.empty(1, dtype=torch.int32, device=dev)
     wsb = _L.cppf_voxel_downsample_workspace_bytes(n)
-    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    ws = hostargs.scratch(wsb, dev, "cppf_voxel_downsample_workspace_bytes", CppfError)
     _lib.check(_L.cppf_voxel_downsample(_p(pts), n, float(res), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(idx), _p(cnt),
                                         _p(ws), wsb, _stream()), "cppf_voxel_downsample")
     idx = idx[: int(cnt.item())].long()

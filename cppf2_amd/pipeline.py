@@ -23,6 +23,17 @@ RESULT_DTYPE = np.dtype([("argmax", "<i8"), ("t", "<f8", (3,)), ("R", "<f8", (3,
                          ("up_count", "<f4"), ("right_count", "<f4"), ("flags", "<i4"), ("ncell", "<i4"), ("pad_", "<i4", (3,))])
 assert RESULT_DTYPE.itemsize == C.sizeof(SceneResult) == 160
 
+
+def record_bytes(records, dev):
+    """Records of any shape (RESULT_DTYPE, or their bytes) as a contiguous uint8 [N,160] tensor on `dev` (a copy)."""
+    host = np.ascontiguousarray(records).reshape(-1)
+    return torch.from_numpy(host.view(np.uint8).reshape(-1, 160).copy()).to(dev)
+
+
+def records_of(raw, shape=-1):
+    """The RESULT_DTYPE array of `shape` (a host copy) that a uint8 [..., 160] tensor of records holds."""
+    return raw.cpu().numpy().reshape(-1).view(RESULT_DTYPE).reshape(shape).copy()
+
 # Suppression radius between centre-vote peaks, metres (vote(centre_peaks=C)).  The back-vote's own agreement distance is no
 # fixed length (a percentile of the batch's errors), so this is verify.TAU: centres closer than the depth tolerance of the
 # verification are the same hypothesis to it.  10 cells at res = 2e-3.  DESIGN.md section 17.
@@ -379,8 +390,7 @@ class VotingPipeline:
         return replay
 
     def results_to_numpy(self, results=None):
-        r = self.results if results is None else results
-        return np.frombuffer(r.cpu().numpy().tobytes(), dtype=RESULT_DTYPE).copy()
+        return records_of(self.results if results is None else results)
 
 
 class BatchMode:

@@ -25,7 +25,7 @@ import sys
 import numpy as np
 import torch
 
-from . import _lib, ops, shot
+from . import _lib, hostargs, ops, shot
 from ._lib import CppfError
 from .geometry import map_sym
 
@@ -189,25 +189,25 @@ def load_mesh(path, scale=1.0):
 # ----------------------------------------------------------------------------------------------
 # depth rendering
 # ----------------------------------------------------------------------------------------------
-_WS = {}                 # (device index, stream) -> [workspace tensor, list capacity]
-WS_CACHE_MAX = 8
+_CAP = {}                # (device index, stream) -> the tile lists' capacity of that stream's workspace
+
+
+class _Workspaces(hostargs.ScratchCache):
+    def __getitem__(self, key):                # the entry as one: (workspace, list capacity)
+        return self.buffers[key], _CAP[key]
+
+
+_WS = _Workspaces("cppf_render_depth_workspace_bytes", CppfError, on_drop=lambda key: _CAP.pop(key, None))
 INITIAL_CAPACITY = 1 << 16
 
 
 def _workspace(B, T, H, W, dev, capacity=None):
-    key = shot._key(dev)
-    ent = _WS.pop(key, None)
-    cap = max(int(capacity if capacity is not None else (ent[1] if ent else INITIAL_CAPACITY)), 1)
-    need = _L.cppf_render_depth_workspace_bytes(B, T, H, W, cap)
-    if need < 0:
-        raise CppfError("cppf_render_depth_workspace_bytes: invalid sizes B=%d T=%d H=%d W=%d" % (B, T, H, W))
-    if ent is None or ent[0].numel() < need:
-        ent = [torch.empty((need,), dtype=torch.uint8, device=dev), cap]
-    ent[1] = cap
-    _WS[key] = ent
-    while len(_WS) > WS_CACHE_MAX:
-        del _WS[next(iter(_WS))]
-    return ent
+    """(workspace tensor, list capacity) for the current stream: the capacity given, else the one remembered, else the initial."""
+    key = hostargs.stream_key(dev)
+    cap = max(int(capacity if capacity is not None else _CAP.get(key, INITIAL_CAPACITY)), 1)
+    ws = _WS.get(key, _L.cppf_render_depth_workspace_bytes(B, T, H, W, cap), dev)
+    _CAP[key] = cap
+    return ws, cap
 
 
 def render_depth(verts, tris, tri_off, poses, intrinsics=INTRINSICS, height=HEIGHT, width=WIDTH, cull=True, znear=ZNEAR,
@@ -225,8 +225,7 @@ def render_depth(verts, tris, tri_off, poses, intrinsics=INTRINSICS, height=HEIG
     tris = tris.to(torch.int32).contiguous()
     tri_off = tri_off.to(torch.int32).contiguous()
     poses = poses.to(device=dev, dtype=torch.float32).reshape(B, 12).contiguous()
-    K = np.asarray(intrinsics, dtype=np.float64).reshape(3, 3)
-    hK = (C.c_double * 4)(K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+    hK = hostargs.camera4(intrinsics)
     depth = torch.empty((B, height, width), dtype=torch.float32, device=dev)
     ids = torch.empty((B, height, width), dtype=torch.int32, device=dev) if with_ids else None
     status = torch.empty((2,), dtype=torch.int64, device=dev)

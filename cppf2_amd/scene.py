@@ -60,17 +60,11 @@ def explain(depth, region, cand_off, renders, tau=TAU, min_gain=MIN_GAIN, viol_w
     255: none), summary int64 [I,3] (region pixels with a reading, explained pixels, rounds used).  No host synchronisation."""
     off, tau, min_gain, viol_weight, M = _checked(cand_off, tau, min_gain, viol_weight, max_rounds, "scene.explain")
     import torch
-    from . import _lib, ops
+    from . import _lib, hostargs, ops
     dev = ops._dev()
-    d = ops._t(depth, torch.float32, dev)
-    d = d[None] if d.dim() == 2 else d
-    if d.dim() != 3 or min(d.shape) < 1 or d.shape[1] > MAX_DIM or d.shape[2] > MAX_DIM:
-        raise ValueError("scene.explain: depth is [I,H,W] or [H,W] with H, W in 1 .. %d, not %s" % (MAX_DIM, tuple(d.shape)))
+    d = hostargs.image_batch(depth, dev, "scene.explain", max_dim=MAX_DIM)
     I, H, W = (int(x) for x in d.shape)
-    m = ops._t(torch.as_tensor(region) != 0 if torch.is_tensor(region) else np.asarray(region) != 0, torch.uint8, dev)
-    m = m[None] if m.dim() == 2 else m
-    if m.shape != d.shape:
-        raise ValueError("scene.explain: region %s for depth %s" % (tuple(m.shape), tuple(d.shape)))
+    m = hostargs.mask_batch(region, d, dev, "scene.explain", same_shape=True)
     if off.size != I + 1:
         raise ValueError("scene.explain: cand_off of %d entries for %d images" % (off.size, I))
     r = ops._t(renders, torch.float32, dev)
@@ -86,7 +80,7 @@ def explain(depth, region, cand_off, renders, tau=TAU, min_gain=MIN_GAIN, viol_w
                summary=torch.empty((I, 3), dtype=torch.int64, device=dev))
     L = _lib.load()
     need = int(L.cppf_scene_explain_workspace_bytes(I, H, W, M))
-    ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    ws = hostargs.scratch(need, dev, "cppf_scene_explain_workspace_bytes", _lib.CppfError)
     _lib.check(L.cppf_scene_explain(I, H, W, ops._p(d), ops._p(m), off.ctypes.data_as(C.c_void_p), P, ops._p(r), C.c_float(tau),
                                     min_gain, viol_weight, M, ops._p(out["chosen"]), ops._p(out["gain"]), ops._p(out["net"]),
                                     ops._p(out["static"]), ops._p(out["labels"]), ops._p(out["summary"]), ops._p(ws), need,
@@ -106,7 +100,7 @@ def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, mi
     in `records`), gain, net int64 [n], static int64 [C,3], labels uint8 [H,W] (host), region_pixels, explained_pixels)."""
     off_check = _checked([0, len(records)], tau, min_gain, viol_weight, max_rounds, "scene.explain_candidates")
     import torch
-    from . import bop, ops, verify
+    from . import bop, hostargs, ops, verify
     from .pipeline import RESULT_DTYPE
     objs = list(objs) if isinstance(objs, (list, tuple)) else [objs]
     objs = [o if isinstance(o, bop.ObjectInfo) else bop.ObjectInfo.from_mesh(o) for o in objs]
@@ -116,10 +110,10 @@ def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, mi
     if of.size != Cn or (Cn and (of.min() < 0 or of.max() >= len(objs))):
         raise ValueError("scene.explain_candidates: obj_of names an object of objs for each of the %d records" % Cn)
     dev = ops._dev()
-    d = ops._t(depth, torch.float32, dev)
-    if d.dim() != 2:
-        raise ValueError("scene.explain_candidates: one depth image [H,W], not %s" % (tuple(d.shape),))
-    Hi, Wi = (int(x) for x in d.shape)
+    if len(np.shape(depth)) != 2:
+        raise ValueError("scene.explain_candidates: one depth image [H,W], not %s" % (np.shape(depth),))
+    d = hostargs.image_batch(depth, dev, "scene.explain_candidates", max_dim=MAX_DIM)
+    _, Hi, Wi = (int(x) for x in d.shape)
     ren = torch.zeros((Cn, Hi, Wi), dtype=torch.float32, device=dev)
     empty = (host["flags"] & verify.EMPTY) != 0
     R, t = host["R"].reshape(-1, 3, 3), host["t"].reshape(-1, 3)

@@ -36,18 +36,6 @@ SEGMENTS_LIMIT = 64          # cppf_mask_segments
 MAX_IMAGES = 65535           # per call of either kernel
 
 
-def _depths(depth, dev, who):
-    import torch
-    from . import ops
-    dt = ops._t(depth, torch.float32, dev)
-    dt = dt.reshape((1,) + tuple(dt.shape)) if dt.dim() == 2 else dt
-    if dt.dim() != 3 or dt.shape[0] < 1 or dt.shape[1] < 1 or dt.shape[2] < 1:
-        raise ValueError("%s: depth is [I,H,W] or [H,W], not %s" % (who, tuple(dt.shape)))
-    if dt.shape[0] > MAX_IMAGES:
-        raise ValueError("%s: at most %d images per call, not %d" % (who, MAX_IMAGES, dt.shape[0]))
-    return dt
-
-
 def intrinsics4(K, I, who="segment"):
     """float32 [I,4] = (fx, fy, cx, cy) on the host of K: a 3 x 3 matrix or I of them (zero skew, last row 0 0 1; ValueError
     otherwise), or (fx, fy, cx, cy), one for all images or one each."""
@@ -88,7 +76,7 @@ def fit_plane(depth, K, seeds, num_hyp=NUM_HYP, tau=TAU):
     hypothesis was usable; int32 [I,4] device tensor: winning hypothesis or -1, its inliers, usable hypotheses, valid pixels).
     No host synchronisation."""
     import torch
-    from . import _lib, ops
+    from . import _lib, hostargs, ops
     num_hyp, tau = int(num_hyp), float(tau)
     if not 1 <= num_hyp <= MAX_HYP:
         raise ValueError("segment.fit_plane: num_hyp must be in 1 .. %d, not %d" % (MAX_HYP, num_hyp))
@@ -101,7 +89,7 @@ def fit_plane(depth, K, seeds, num_hyp=NUM_HYP, tau=TAU):
         except (TypeError, ValueError, OverflowError):
             raise ValueError("segment.fit_plane: seeds are integers in [0, 2^64), not %r" % (seeds,)) from None
     dev = ops._dev()
-    dt = _depths(depth, dev, "segment.fit_plane")
+    dt = hostargs.image_batch(depth, dev, "segment.fit_plane", max_images=MAX_IMAGES)
     I, H, W = (int(x) for x in dt.shape)
     if sd is None:
         st = seeds.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
@@ -115,7 +103,7 @@ def fit_plane(depth, K, seeds, num_hyp=NUM_HYP, tau=TAU):
     stats = torch.empty((I, 4), dtype=torch.int32, device=dev)
     L = _lib.load()
     need = int(L.cppf_plane_fit_workspace_bytes(I, num_hyp))
-    ws = torch.empty((max(need, 16) + 7) // 8, dtype=torch.int64, device=dev)
+    ws = hostargs.scratch(need, dev, "cppf_plane_fit_workspace_bytes", _lib.CppfError)
     _lib.check(L.cppf_plane_fit(I, H, W, ops._p(dt), ops._p(km), ops._p(st), num_hyp, C.c_float(tau), ops._p(plane), ops._p(stats),
                                 ops._p(ws), need, ops._stream()), "cppf_plane_fit")
     return plane, stats
@@ -126,12 +114,12 @@ def foreground(depth, K, plane, min_height=MIN_HEIGHT, max_height=0.0):
     [I,4] or [4], fit_plane's) is > min_height and, when max_height > 0, <= max_height (cppf_plane_foreground).  An image whose
     plane is all zeros keeps every valid pixel.  No host synchronisation."""
     import torch
-    from . import _lib, ops
+    from . import _lib, hostargs, ops
     min_height, max_height = float(min_height), float(max_height)
     if np.isnan(min_height) or np.isnan(max_height):
         raise ValueError("segment.foreground: min_height and max_height are distances, not NaN")
     dev = ops._dev()
-    dt = _depths(depth, dev, "segment.foreground")
+    dt = hostargs.image_batch(depth, dev, "segment.foreground", max_images=MAX_IMAGES)
     I, H, W = (int(x) for x in dt.shape)
     pl = ops._t(plane, torch.float32, dev).reshape(-1, 4)
     if pl.shape[0] != I:
@@ -152,7 +140,7 @@ def segments(fg, depth, img_idx=0, jump=_masks.JUMP, min_pixels=MIN_SEGMENT_PIXE
     (label, pixels, x0, y0, x1, y1) per rank, the box inclusive, -1 in unused rows; int32 [D,4] = components, segments kept,
     components of at least min_pixels, valid pixels).  No host synchronisation."""
     import torch
-    from . import _lib, ops
+    from . import _lib, hostargs, ops
     jump, min_pixels, M = float(jump), int(min_pixels), int(max_segments)
     if not (jump >= 0.0 and np.isfinite(jump)):
         raise ValueError("segment.segments: jump must be a finite distance >= 0, not %r" % jump)
@@ -161,23 +149,13 @@ def segments(fg, depth, img_idx=0, jump=_masks.JUMP, min_pixels=MIN_SEGMENT_PIXE
     if not 1 <= M <= SEGMENTS_LIMIT:
         raise ValueError("segment.segments: max_segments must be in 1 .. %d, not %d" % (SEGMENTS_LIMIT, M))
     dev = ops._dev()
-    dt = _depths(depth, dev, "segment.segments")
+    dt = hostargs.image_batch(depth, dev, "segment.segments", max_images=MAX_IMAGES)
     I, H, W = (int(x) for x in dt.shape)
-    if torch.is_tensor(fg):
-        mk = fg.to(dev)
-        mk = (mk.to(torch.uint8) * 255) if mk.dtype == torch.bool else mk.to(torch.uint8)
-    else:
-        mk = torch.from_numpy(np.ascontiguousarray((np.asarray(fg) != 0).astype(np.uint8) * 255)).to(dev)
-    if mk.numel() % (H * W):
-        raise ValueError("segment.segments: masks %s do not match the %d x %d depth image" % (tuple(mk.shape), H, W))
-    mk = mk.reshape(-1, H, W).contiguous()
+    mk = hostargs.mask_batch(fg, dt, dev, "segment.segments")
     D = int(mk.shape[0])
     if D > MAX_IMAGES:
         raise ValueError("segment.segments: at most %d masks per call, not %d" % (MAX_IMAGES, D))
-    ii = ops._t(np.array(np.broadcast_to(np.asarray(img_idx, dtype=np.int32), (D,))) if not torch.is_tensor(img_idx) else img_idx,
-                torch.int32, dev).reshape(-1)
-    if ii.numel() != D:
-        raise ValueError("segment.segments: %d masks, %d image indices" % (D, ii.numel()))
+    ii = hostargs.per_item(img_idx, D, torch.int32, dev, "segment.segments", "image indices")
     rank = torch.empty((D, H, W), dtype=torch.uint8, device=dev)
     seg = torch.empty((D, M, 6), dtype=torch.int32, device=dev)
     stats = torch.empty((D, 4), dtype=torch.int32, device=dev)
@@ -185,7 +163,7 @@ def segments(fg, depth, img_idx=0, jump=_masks.JUMP, min_pixels=MIN_SEGMENT_PIXE
         return rank, seg, stats
     L = _lib.load()
     need = int(L.cppf_mask_segments_workspace_bytes(D, H, W, M))
-    ws = torch.empty((max(need, 8) + 7) // 8, dtype=torch.int64, device=dev)
+    ws = hostargs.scratch(need, dev, "cppf_mask_segments_workspace_bytes", _lib.CppfError)
     _lib.check(L.cppf_mask_segments(D, I, H, W, ops._p(mk), ops._p(dt), ops._p(ii), C.c_float(jump), min_pixels, M, ops._p(rank),
                                     ops._p(seg), ops._p(stats), ops._p(ws), need, ops._stream()), "cppf_mask_segments")
     return rank, seg, stats

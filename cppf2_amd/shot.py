@@ -15,7 +15,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, hostargs, ops
 
 _L = _lib.load()
 
@@ -33,36 +33,15 @@ def _flags(arithmetic):
     return 1 if a == "f64" else 0          # CPPF_SHOT_F64_NORMALS
 
 
-_WS = {}          # (device, stream) -> scratch buffer
 _PREPARED = {}    # (device, stream) -> (B, n, pts pointer) of the last prepare_device, checked by describe_device
-
-
-WS_CACHE_MAX = 8        # (device, stream) pairs whose scratch buffer stays alive; the least recently used one goes first
-
-
-def _key(dev):
-    dev = torch.device(dev)
-    index = dev.index if dev.index is not None else torch.cuda.current_device()     # "cuda" and "cuda:0" are one device
-    return (int(index), int(torch.cuda.current_stream(dev).cuda_stream))
+# one scratch buffer per (device index, stream), reused by every call issued on that stream; a buffer that is replaced or
+# evicted holds no prepared state
+_WS = hostargs.ScratchCache("cppf_shot352_workspace_bytes", _lib.CppfError, on_drop=lambda key: _PREPARED.pop(key, None))
+_key = hostargs.stream_key
 
 
 def _workspace(B, n, dev):
-    """One cached scratch buffer per (device index, stream): grown on demand and reused by every call issued on that stream,
-    so calls on different streams (or threads using their own streams) never share scratch memory.  At most WS_CACHE_MAX
-    buffers are kept (least recently used evicted: a process that keeps creating streams does not pin a workspace per
-    stream for its lifetime)."""
-    need = _L.cppf_shot352_workspace_bytes(B, n)
-    key = _key(dev)
-    ws = _WS.pop(key, None)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _PREPARED.pop(key, None)          # a new buffer holds no prepared state
-    _WS[key] = ws                         # (re-)inserted last: dicts keep insertion order, the first key is the oldest
-    while len(_WS) > WS_CACHE_MAX:
-        old = next(iter(_WS))
-        del _WS[old]
-        _PREPARED.pop(old, None)
-    return ws
+    return _WS.get(_key(dev), _L.cppf_shot352_workspace_bytes(B, n), dev)
 
 
 def compute_device(pts, pt_off, normal_r, shot_r, want_rf=False, arithmetic=None):
@@ -153,8 +132,7 @@ def compute_color_device(pts, colors, pt_off, normal_r, shot_r, arithmetic=None)
     B = pt_off.numel() - 1
     out = torch.empty((n, 1344), dtype=torch.float32, device=dev)
     out_normal = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    need = _L.cppf_shot1344_workspace_bytes(B, n)
-    ws = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+    ws = hostargs.scratch(_L.cppf_shot1344_workspace_bytes(B, n), dev, "cppf_shot1344_workspace_bytes", _lib.CppfError)
     _lib.check(_L.cppf_shot1344(B, ops._p(pts), ops._p(colors), ops._p(pt_off), n, C.c_float(normal_r), C.c_float(shot_r),
                                 ops._p(out), ops._p(out_normal), ops._p(ws), ws.numel(), _flags(arithmetic), ops._stream()),
                "cppf_shot1344")

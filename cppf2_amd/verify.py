@@ -18,9 +18,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, bop, icp, ops, render
+from . import _lib, bop, hostargs, icp, ops, render
 from ._lib import CppfError
-from .pipeline import RESULT_DTYPE
+from .pipeline import RESULT_DTYPE, record_bytes, records_of
 
 _L = _lib.load()
 
@@ -45,7 +45,7 @@ def hypotheses(counts_up, counts_right, sphere, base, H, up_axis, right_axis, K=
     cr = ops._t(counts_right, torch.float32, dev)
     sph = ops._t(sphere, torch.float32, dev).reshape(-1, 3)
     if isinstance(base, np.ndarray):
-        base = torch.from_numpy(np.frombuffer(np.ascontiguousarray(base).tobytes(), dtype=np.uint8).reshape(-1, 160).copy()).to(dev)
+        base = record_bytes(base, dev)
     if base.dtype != torch.uint8 or base.dim() != 2 or base.shape[1] != 160 or not base.is_contiguous():
         raise CppfError("verify.hypotheses: base must be contiguous uint8 [B,160] records")
     B, S = base.shape[0], sph.shape[0]
@@ -60,22 +60,15 @@ def hypotheses(counts_up, counts_right, sphere, base, H, up_axis, right_axis, K=
     return (out, pi, pc) if with_peaks else out
 
 
-def _images(x, dtype, dev):
-    t = ops._t(x, dtype, dev)
-    return t[None] if t.dim() == 2 else t
-
-
 def fit_counts(depth, mask, hyp_off, renders, taus=(TAU,)):
     """cppf_depth_fit_counts: int64 [P, 4 + n_taus] device tensor (drawn, observed, violations, unexplained, fit_1 .. fit_n).
     depth float32 [I,H,W] or [H,W] (metres, 0 = no reading), mask [I,H,W] or [H,W] (non-zero: the instance), hyp_off int
     [I+1] (host: renders hyp_off[i] .. hyp_off[i+1]-1 are hypotheses of image i), renders float32 [P,H,W] (0 = nothing
     drawn), taus: metres, at most 32 (taus[0] is also the violation margin)."""
     dev = ops._dev()
-    d = _images(depth, torch.float32, dev)
+    d = hostargs.image_batch(depth, dev, "verify.fit_counts")
     I, H, W = d.shape
-    m = _images(torch.as_tensor(mask) != 0 if torch.is_tensor(mask) else np.asarray(mask) != 0, torch.uint8, dev)
-    if m.shape != d.shape:
-        raise CppfError("verify.fit_counts: mask %s for depth %s" % (tuple(m.shape), tuple(d.shape)))
+    m = hostargs.mask_batch(mask, d, dev, "verify.fit_counts", same_shape=True, err=CppfError)
     off = np.ascontiguousarray((hyp_off.cpu().numpy() if torch.is_tensor(hyp_off) else np.asarray(hyp_off)).reshape(-1),
                                dtype=np.int32)
     if off.size != I + 1:
@@ -115,13 +108,11 @@ def _as_records(records):
     """(RESULT_DTYPE [B,H] host copy, device uint8 [B*H,160])."""
     dev = ops._dev()
     if torch.is_tensor(records):
-        rec = records.reshape(records.shape[0], -1, 160)
-        host = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=RESULT_DTYPE).reshape(rec.shape[:2]).copy()
+        host = records_of(records, (records.shape[0], -1))
     else:
         host = np.ascontiguousarray(records, dtype=RESULT_DTYPE)
         host = host.reshape(len(host), -1).copy()
-    raw = np.frombuffer(host.tobytes(), dtype=np.uint8).reshape(-1, 160).copy()
-    return host, torch.from_numpy(raw).to(dev)
+    return host, record_bytes(host, dev)
 
 
 def drawable(obj, R, t, ok):
@@ -168,10 +159,10 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
     dev = ops._dev()
     host, rec = _as_records(records)
     B, Hh = host.shape
-    d = _images(depth, torch.float32, dev)
-    m = _images(torch.as_tensor(mask) != 0 if torch.is_tensor(mask) else np.asarray(mask) != 0, torch.uint8, dev)
-    if d.shape[0] != B or m.shape != d.shape:
-        raise CppfError("verify.select: %d instances, depth %s, mask %s" % (B, tuple(d.shape), tuple(m.shape)))
+    d = hostargs.image_batch(depth, dev, "verify.select")
+    if d.shape[0] != B:
+        raise CppfError("verify.select: %d instances, depth %s" % (B, tuple(d.shape)))
+    m = hostargs.mask_batch(mask, d, dev, "verify.select", same_shape=True, err=CppfError)
     _, Hi, Wi = d.shape
     empty = (host["flags"] & EMPTY) != 0
     stats = None
@@ -191,7 +182,7 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
         else:
             stats = icp.refine(icp_model, p[sel].contiguous(), rep_off, rec, iters=int(icp_iters))
         stats = stats.cpu().numpy().reshape(B, Hh, -1)
-        host = np.frombuffer(rec.cpu().numpy().tobytes(), dtype=RESULT_DTYPE).reshape(B, Hh).copy()
+        host = records_of(rec, (B, Hh))
     # poses of the records (float64), drawable ones
     R = host["R"].reshape(-1, 3, 3)
     t = host["t"].reshape(-1, 3)
