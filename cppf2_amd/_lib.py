@@ -119,6 +119,8 @@ STABLE = {
     "cppf_depth_fit_counts": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _p, _i, _p, _p]),
     "cppf_scene_explain_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "cppf_scene_explain": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _f, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "cppf_scene_explain_wide_workspace_bytes": (_i64, [_i, _i, _i, _i, _i]),
+    "cppf_scene_explain_wide": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _f, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "cppf_reslayer_split_stream_bytes": (_i64, [_i, _i, _i, _i]),
     "cppf_reslayer_split": (_i, [_p, _i64, _i, _p, _i64, _i, _i64, _p, _i64, _p, _p, _i, _p, _p]),
     "cppf_reslayer_split_tap": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _i, _i64, _p, _i64, _p, _p, _i, _p, _p]),

@@ -3,7 +3,8 @@ the subset that together explains the observed depth, every observed pixel count
 decides per mask and in isolation; this decides per image: which candidates are instances and which are clutter.
 
     out = explain(depth, region, cand_off, renders)           # device tensors: chosen, gain, net, static, labels, summary
-    out = explain_candidates(objs, depth, region, K, records, obj_of)
+    out = explain_wide(depth, region, cand_off, renders)      # the same with up to 512 candidates per image (section 24)
+    out = explain_candidates(objs, depth, region, K, records, obj_of)         # wide=True: up to 512 records
     out["records"]                                            # the chosen records, in the order they were chosen
 
 Greedy rounds: a candidate's gain is the number of region pixels it fits within tau that no earlier winner explained, its net
@@ -25,11 +26,12 @@ MIN_GAIN = _segment.MIN_SEGMENT_PIXELS
 VIOL_WEIGHT = 1
 MAX_ROUNDS = 16
 MAX_CANDIDATES = 64                         # per image: one bit of a pixel's word each
+MAX_CANDIDATES_WIDE = 512                   # explain_wide: up to 8 words per pixel
 ROUNDS_LIMIT = 64
 MAX_DIM = 8192
 
 
-def _checked(cand_off, tau, min_gain, viol_weight, max_rounds, who):
+def _checked(cand_off, tau, min_gain, viol_weight, max_rounds, who, limit=MAX_CANDIDATES):
     """The host-side arguments, checked before a device is touched: (int32 offsets, tau, min_gain, viol_weight, max_rounds)."""
     tau, min_gain, viol_weight, max_rounds = float(tau), int(min_gain), int(viol_weight), int(max_rounds)
     if not tau >= 0.0:
@@ -46,8 +48,8 @@ def _checked(cand_off, tau, min_gain, viol_weight, max_rounds, who):
     off = off.astype(np.int64)
     if off[0] != 0 or np.any(np.diff(off) < 0):
         raise ValueError("%s: cand_off must start at 0 and never decrease" % who)
-    if np.any(np.diff(off) > MAX_CANDIDATES):
-        raise ValueError("%s: at most %d candidates per image, not %d" % (who, MAX_CANDIDATES, int(np.diff(off).max())))
+    if np.any(np.diff(off) > limit):
+        raise ValueError("%s: at most %d candidates per image, not %d" % (who, limit, int(np.diff(off).max())))
     return np.ascontiguousarray(off, dtype=np.int32), tau, min_gain, viol_weight, max_rounds
 
 
@@ -58,47 +60,63 @@ def explain(depth, region, cand_off, renders, tau=TAU, min_gain=MIN_GAIN, viol_w
     [I,M] (the winner's index within its image per round, -1 past the end), gain and net int64 [I,M], static int64 [P,3]
     (drawn, fit, violations: columns 0, 4 and 2 of verify.fit_counts), labels uint8 [I,H,W] (the round that explained the pixel,
     255: none), summary int64 [I,3] (region pixels with a reading, explained pixels, rounds used).  No host synchronisation."""
-    off, tau, min_gain, viol_weight, M = _checked(cand_off, tau, min_gain, viol_weight, max_rounds, "scene.explain")
+    return _explain(depth, region, cand_off, renders, tau, min_gain, viol_weight, max_rounds, "scene.explain", False)
+
+
+def explain_wide(depth, region, cand_off, renders, tau=TAU, min_gain=MIN_GAIN, viol_weight=VIOL_WEIGHT, max_rounds=MAX_ROUNDS):
+    """cppf_scene_explain_wide on the current stream: explain() with at most 512 candidates per image -- the same arguments,
+    checks and dict of device tensors, every output the same byte for byte where explain() takes the input (chosen holds
+    indices up to 511).  The call's largest image fixes the planes of 64 candidates the workspace holds.  No host
+    synchronisation."""
+    return _explain(depth, region, cand_off, renders, tau, min_gain, viol_weight, max_rounds, "scene.explain_wide", True)
+
+
+def _explain(depth, region, cand_off, renders, tau, min_gain, viol_weight, max_rounds, who, wide):
+    off, tau, min_gain, viol_weight, M = _checked(cand_off, tau, min_gain, viol_weight, max_rounds, who,
+                                                  MAX_CANDIDATES_WIDE if wide else MAX_CANDIDATES)
     import torch
     from . import _lib, hostargs, ops
     dev = ops._dev()
-    d = hostargs.image_batch(depth, dev, "scene.explain", max_dim=MAX_DIM)
+    d = hostargs.image_batch(depth, dev, who, max_dim=MAX_DIM)
     I, H, W = (int(x) for x in d.shape)
-    m = hostargs.mask_batch(region, d, dev, "scene.explain", same_shape=True)
+    m = hostargs.mask_batch(region, d, dev, who, same_shape=True)
     if off.size != I + 1:
-        raise ValueError("scene.explain: cand_off of %d entries for %d images" % (off.size, I))
+        raise ValueError("%s: cand_off of %d entries for %d images" % (who, off.size, I))
     r = ops._t(renders, torch.float32, dev)
     if r.numel() % (H * W):
-        raise ValueError("scene.explain: renders %s do not match the %d x %d depth image" % (tuple(r.shape), H, W))
+        raise ValueError("%s: renders %s do not match the %d x %d depth image" % (who, tuple(r.shape), H, W))
     P = r.numel() // (H * W)
     r = r.reshape(P, H, W)
     if int(off[-1]) != P:
-        raise ValueError("scene.explain: cand_off ends at %d for %d renders" % (int(off[-1]), P))
+        raise ValueError("%s: cand_off ends at %d for %d renders" % (who, int(off[-1]), P))
     out = dict(chosen=torch.empty((I, M), dtype=torch.int32, device=dev), gain=torch.empty((I, M), dtype=torch.int64, device=dev),
                net=torch.empty((I, M), dtype=torch.int64, device=dev), static=torch.empty((P, 3), dtype=torch.int64, device=dev),
                labels=torch.empty((I, H, W), dtype=torch.uint8, device=dev),
                summary=torch.empty((I, 3), dtype=torch.int64, device=dev))
     L = _lib.load()
-    need = int(L.cppf_scene_explain_workspace_bytes(I, H, W, M))
-    ws = hostargs.scratch(need, dev, "cppf_scene_explain_workspace_bytes", _lib.CppfError)
-    _lib.check(L.cppf_scene_explain(I, H, W, ops._p(d), ops._p(m), off.ctypes.data_as(C.c_void_p), P, ops._p(r), C.c_float(tau),
-                                    min_gain, viol_weight, M, ops._p(out["chosen"]), ops._p(out["gain"]), ops._p(out["net"]),
-                                    ops._p(out["static"]), ops._p(out["labels"]), ops._p(out["summary"]), ops._p(ws), need,
-                                    ops._stream()), "cppf_scene_explain")
+    name = "cppf_scene_explain_wide" if wide else "cppf_scene_explain"
+    most = (max(int(np.diff(off).max()), 1),) if wide else ()      # the wide form's max_candidates
+    need = int(getattr(L, name + "_workspace_bytes")(I, H, W, M, *most))
+    ws = hostargs.scratch(need, dev, name + "_workspace_bytes", _lib.CppfError)
+    _lib.check(getattr(L, name)(I, H, W, ops._p(d), ops._p(m), off.ctypes.data_as(C.c_void_p), P, ops._p(r), C.c_float(tau), min_gain,
+                                viol_weight, M, *most, ops._p(out["chosen"]), ops._p(out["gain"]), ops._p(out["net"]),
+                                ops._p(out["static"]), ops._p(out["labels"]), ops._p(out["summary"]), ops._p(ws), need, ops._stream()),
+               name)
     return out
 
 
 def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, min_gain=MIN_GAIN, viol_weight=VIOL_WEIGHT,
-                       max_rounds=MAX_ROUNDS, chunk=None):
-    """Explains one depth image [H,W] (metres) by candidate poses: records (RESULT_DTYPE [C], C <= 64; R, t in the record
-    convention of verify.py) of the objects objs (one bop.ObjectInfo or render.Mesh, or a list of them) with obj_of int [C] (the
+                       max_rounds=MAX_ROUNDS, chunk=None, wide=False):
+    """Explains one depth image [H,W] (metres) by candidate poses: records (RESULT_DTYPE [C], C <= 64, with wide C <= 512 through
+    explain_wide; R, t in the record convention of verify.py) of the objects objs (one bop.ObjectInfo or render.Mesh, or a list of them) with obj_of int [C] (the
     index into objs of each record; None: all are objs[0]).  The candidates are rendered as verify.select renders its
     hypotheses -- back faces culled; a record flagged empty, one that is not finite, or one that puts a vertex nearer than
     render.ZNEAR is not drawn, fits nothing and is never chosen -- and given to explain() with the region [H,W].
 
     Returns dict(records RESULT_DTYPE [n] (the chosen records, in the order they were chosen), chosen int64 [n] (their indices
     in `records`), gain, net int64 [n], static int64 [C,3], labels uint8 [H,W] (host), region_pixels, explained_pixels)."""
-    off_check = _checked([0, len(records)], tau, min_gain, viol_weight, max_rounds, "scene.explain_candidates")
+    off_check = _checked([0, len(records)], tau, min_gain, viol_weight, max_rounds, "scene.explain_candidates",
+                         MAX_CANDIDATES_WIDE if wide else MAX_CANDIDATES)
     import torch
     from . import bop, hostargs, ops, verify
     from .pipeline import RESULT_DTYPE
@@ -123,7 +141,7 @@ def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, mi
         for a in range(0, idx.size, int(chunk or verify.RENDER_CHUNK)):
             part = slice(a, a + int(chunk or verify.RENDER_CHUNK))
             ren[torch.from_numpy(idx[part]).to(dev)] = verify.render_records(obj, R[idx[part]], t[idx[part]], draw[part], K, Hi, Wi, dev)
-    out = explain(d, region, off_check[0], ren, tau, min_gain, viol_weight, max_rounds)
+    out = (explain_wide if wide else explain)(d, region, off_check[0], ren, tau, min_gain, viol_weight, max_rounds)
     summary = out["summary"][0].cpu().numpy()
     n = int(summary[2])
     pick = out["chosen"][0, :n].cpu().numpy().astype(np.int64)

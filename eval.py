@@ -83,6 +83,13 @@ What the image cannot provide is stated, not faked:
     `--models_dir=<BOP models dir> --pair_tables=<dir> [--obj_ids=1,5 --model_scale=0.001]` stands in for --mesh and
     --pair_table: obj_%06d.ply (+ models_info.json) and obj_%06d.npz per object; the proposal path runs once per object id,
     the candidates of all objects are pooled into one explanation, and every result, proposal and instance carries `obj_id`.
+    `--explain_hypotheses [--explain_min_support=0.5]` makes every verified hypothesis of every proposal a candidate, not only
+    the one the verification kept, so that two objects that touch -- one depth segment, one proposal -- can both be found
+    (cppf_scene_explain_wide).  The gate is the hypothesis' support, fit / drawn: the share of what the
+    pose shows the camera that the depth confirms (the per-mask score divides by the whole mask, which two objects share; 0.5
+    is "at least half", not swept), so --explain_min_score is refused beside it.  The 512 best supported are kept when there
+    are more (`dropped`); instances and rejected entries gain `hypothesis` and `support`, the reasons are `below_min_support`
+    and `no_gain`, and `parameters` gains `min_support` and `hypotheses`.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import collections
@@ -630,9 +637,13 @@ def _explain_flags(f):
     given = [k_ for k_ in _EXPLAIN_FLAGS if getattr(f, k_) is not None]
     if f.obj_ids is not None and not f.models_dir:
         raise ValueError("--obj_ids names objects of a models folder: it needs --models_dir")
+    if f.explain_min_support is not None and not f.explain_hypotheses:
+        raise ValueError("--explain_min_support gates the hypotheses of --explain_hypotheses: it needs that flag")
     if not f.explain_scene:
         if given:
             raise ValueError("--%s sets how the scene is explained: it needs --explain_scene" % given[0])
+        if f.explain_hypotheses:
+            raise ValueError("--explain_hypotheses makes every verified hypothesis a candidate of the scene: it needs --explain_scene")
         if f.models_dir:
             raise ValueError("--models_dir pools the candidates of several objects into one explanation: it needs --explain_scene")
         return None
@@ -668,6 +679,13 @@ def _explain_flags(f):
         raise ValueError("--explain_viol_weight must be >= 0, not %d" % e["viol_weight"])
     if not 1 <= e["max_rounds"] <= scene.ROUNDS_LIMIT:
         raise ValueError("--explain_max must be in 1 .. %d, not %d" % (scene.ROUNDS_LIMIT, e["max_rounds"]))
+    if f.explain_hypotheses:
+        if f.explain_min_score is not None:
+            raise ValueError("--explain_min_score gates one pose per proposal; with --explain_hypotheses the gate is "
+                             "--explain_min_support: give one of them")
+        e.update(min_support=0.5 if f.explain_min_support is None else float(f.explain_min_support), hypotheses=True)
+        if not 0.0 <= e["min_support"] <= 1.0:
+            raise ValueError("--explain_min_support is a share of the drawn pixels in [0, 1], not %r" % (f.explain_min_support,))
     return e
 
 
@@ -938,25 +956,48 @@ def _scene_objects(models_dir, pair_tables, obj_ids, model_scale, icp_iters):
                  pair_table=os.path.join(str(pair_tables), "obj_%06d.npz" % int(o))) for o in obj_ids]
 
 
+def _hypothesis_candidates(ver, b, tag):
+    """--explain_hypotheses: every hypothesis of instance b that refine_and_verify's `ver` holds and that is not an empty slot,
+    as a candidate of _explain_scene: the pose after ICP, its per-mask score, and its support fit / drawn in float64 (the share
+    of what the pose shows the camera that the depth confirms inside the mask; 0 where nothing is drawn)."""
+    from cppf2_amd import verify
+    out = []
+    for h, rec in enumerate(ver["hypotheses"][b]):
+        if rec["flags"] & verify.EMPTY:
+            continue
+        drawn, fit = int(ver["counts"][b, h, 0]), int(ver["counts"][b, h, verify.N_COUNTS])
+        out.append(dict(tag, hypothesis=h, score=float(ver["scores"][b, h]), record=rec.copy(),
+                        support=float(np.float64(fit) / np.float64(drawn)) if drawn else 0.0))
+    return out
+
+
 def _explain_scene(cands, objs, d, region, K, tau, explain):
     """The report's `scene` entry: the candidates (dicts with proposal, category, score, record, obj: index into objs, and
     obj_id in the multi-object form) with a score of at least min_score, the 64 best of them when there are more (ties to the
-    lower index), explained over `region` by scene.explain_candidates."""
+    lower index), explained over `region` by scene.explain_candidates.  With explain["hypotheses"] (--explain_hypotheses) the
+    candidates are hypotheses (they also carry hypothesis and support), the gate is a support of at least min_support, and the
+    512 best supported go through the wide form."""
     from cppf2_amd import scene
     from cppf2_amd.pipeline import RESULT_DTYPE
+    wide = bool(explain.get("hypotheses"))
+    gate, floor, limit = ("support", explain["min_support"], scene.MAX_CANDIDATES_WIDE) if wide else \
+        ("score", explain["min_score"], scene.MAX_CANDIDATES)
 
     def entry(c_, **more):
-        e = {k_: c_[k_] for k_ in ("proposal", "category", "obj_id") if k_ in c_}
+        e = {k_: c_[k_] for k_ in ("proposal", "category", "obj_id", "hypothesis") if k_ in c_}
         e.update(score=c_["score"], **more)
+        if wide:
+            e["support"] = c_["support"]
         return e
-    rejected = [entry(c_, reason="below_min_score") for c_ in cands if not c_["score"] >= explain["min_score"]]
-    kept = [c_ for c_ in cands if c_["score"] >= explain["min_score"]]
-    order = sorted(range(len(kept)), key=lambda j: (-kept[j]["score"], j))[:scene.MAX_CANDIDATES]
+    rejected = [entry(c_, reason="below_min_" + gate) for c_ in cands if not c_[gate] >= floor]
+    kept = [c_ for c_ in cands if c_[gate] >= floor]
+    order = sorted(range(len(kept)), key=lambda j: (-kept[j][gate], j))[:limit]
     dropped = len(kept) - len(order)
     kept = [kept[j] for j in sorted(order)]
     recs = np.array([c_["record"] for c_ in kept], dtype=RESULT_DTYPE).reshape(-1)
     ex = scene.explain_candidates(objs, d.astype(np.float32), region, K, recs, [c_["obj"] for c_ in kept], tau=tau,
-                                  min_gain=explain["min_gain"], viol_weight=explain["viol_weight"], max_rounds=explain["max_rounds"])
+                                  min_gain=explain["min_gain"], viol_weight=explain["viol_weight"], max_rounds=explain["max_rounds"],
+                                  wide=wide)
     instances = []
     for j, g, n in zip(ex["chosen"], ex["gain"], ex["net"]):
         rec = kept[int(j)]["record"]
@@ -1029,8 +1070,11 @@ def _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj
                         entry["score"] = item["verify"]["score"]
                         if top is None or entry["score"] > items[top]["verify"]["score"]:      # ties: the lower rank stays
                             top = b
-                        cands.append(dict(proposal=ranks[b], category=cat, score=entry["score"], record=reported[b].copy(), obj=oi,
-                                          **tag))
+                        if explain is None or not explain.get("hypotheses"):
+                            cands.append(dict(proposal=ranks[b], category=cat, score=entry["score"], record=reported[b].copy(),
+                                              obj=oi, **tag))
+                        else:
+                            cands += _hypothesis_candidates(ver, b, dict(proposal=ranks[b], category=cat, obj=oi, **tag))
                 proposals.append(entry)
             if top is not None and (best is None or items[top]["verify"]["score"] > best["score"]):
                 best = dict(proposal=ranks[top], category=cat, score=items[top]["verify"]["score"], **tag)
@@ -1074,7 +1118,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0, pair_table=None, pair_tables=None,
          propose_masks=False, plane_tau=None, plane_hypotheses=None, plane_min_height=None, min_segment_pixels=None,
          max_proposals=None, explain_scene=False, explain_min_score=None, explain_min_gain=None, explain_viol_weight=None,
-         explain_max=None, models_dir=None, obj_ids=None):
+         explain_max=None, models_dir=None, obj_ids=None, explain_hypotheses=False, explain_min_support=None):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()

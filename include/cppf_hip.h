@@ -570,6 +570,21 @@ int cppf_scene_explain(int I, int H, int W, const float* depth, const uint8_t* r
                        int64_t* gain, int64_t* net, int64_t* stat, uint8_t* labels, int64_t* summary, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
+/* cppf_scene_explain_wide: cppf_scene_explain with up to 512 candidates per image (cppf2_amd/csrc/cppf_scene_wide.hip).  The same
+ * definition and the same outputs, byte for byte (for images of at most 64 candidates: cppf_scene_explain's own); the key's
+ * candidate index goes up to 511.  max_candidates (1 .. 512): the largest per-image candidate count of the call; it fixes
+ * G = ceil(max_candidates / 64) planes of one 64-bit word per pixel.  workspace: cppf_scene_explain_wide_workspace_bytes(I, H, W,
+ * max_rounds, max_candidates) bytes (G times 8 per pixel, plus 256 G per image and round; 0 for sizes the call refuses), 8-byte
+ * aligned.  max_rounds + 2 launches per 128 images behind the clears of the outputs, no host synchronisation.  Returns
+ * CPPF_EUNSUPPORTED for max_candidates outside 1 .. 512 (more than 512 candidates per image are not supported), CPPF_EINVAL for
+ * an image with more than max_candidates candidates and for every other broken rule of cppf_scene_explain, CPPF_ECAPACITY for a
+ * workspace that is too small, all before any device work. */
+int64_t cppf_scene_explain_wide_workspace_bytes(int I, int H, int W, int max_rounds, int max_candidates);
+int cppf_scene_explain_wide(int I, int H, int W, const float* depth, const uint8_t* region, const int32_t* h_cand_off, int P,
+                            const float* renders, float tau, int min_gain, int viol_weight, int max_rounds, int max_candidates,
+                            int32_t* chosen, int64_t* gain, int64_t* net, int64_t* stat, uint8_t* labels, int64_t* summary,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* DINO-branch feature plumbing: replaces interpolate_features (dataset.py:40-59) = grid_sample
  * (bilinear, zeros padding, align_corners=False) of the patch-token map desc at the pixel centres of pts float32[n,2]
  * (x, y), then L2 normalisation over the C channels.  desc is addressed as desc[c*stride_c + y*stride_y + x*stride_x]
