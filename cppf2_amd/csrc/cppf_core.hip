@@ -174,17 +174,23 @@ __global__ __launch_bounds__(256) void scene_bounds_kernel(const float* __restri
     CppfSceneGrid g;
     int64_t cells = 1;
     g.flags = (n <= 0) ? 1 : 0;
+    bool unrep = false;                                // an axis whose cell count is no int32 (see CppfSceneGrid in cppf_hip.h)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const float lo = fminf(fminf(s_mn[0][c], s_mn[1][c]), fminf(s_mn[2][c], s_mn[3][c]));
       const float hi = fmaxf(fmaxf(s_mx[0][c], s_mx[1][c]), fmaxf(s_mx[2][c], s_mx[3][c]));
       g.c0[c] = lo;
       const float q = (hi - lo) / res;                 // float32 division, then .long() truncation
-      int gi = (n > 0 && q < 2.0e9f) ? (int)q + 1 : 0;
+      // !(0 <= q < 2e9): a quotient too large for int32, an infinite extent (q = inf, or NaN from inf - inf) or an axis
+      // without a finite coordinate (lo = +inf, hi = -inf: q = -inf) -- never through (int)
+      const bool ok = q >= 0.0f && q < 2.0e9f;
+      if (n > 0 && !ok) unrep = true;
+      int gi = (n > 0 && ok) ? (int)q + 1 : 0;
       g.g[c] = gi;
       cells *= (int64_t)gi;
     }
-    if (cells > 0x7fffffffLL) { g.flags |= 2; cells = 0; }
+    if (unrep) { g.g[0] = g.g[1] = g.g[2] = 0; }
+    if (unrep || cells > 0x7fffffffLL) { g.flags |= 2; cells = 0; }
     if (n <= 0) cells = 0;
     g.ncell = (int32_t)cells;
     out[b] = g;

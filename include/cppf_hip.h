@@ -49,12 +49,23 @@ extern "C" {
 
 #define CPPF_ABI_VERSION 11
 
-/* Per-scene voxel grid geometry: train_dino.py:172-173 (corners, grid_res). 32 bytes. */
+/* Per-scene voxel grid geometry: train_dino.py:172-173 (corners, grid_res). 32 bytes.
+ * min / max skip NaN coordinates (fminf / fmaxf); an axis without any number has min = +inf, max = -inf, and so has every axis
+ * of an empty scene.  q = (max - min) / res is a float32 division.
+ *  - empty scene (no points): c0 = +inf, g = 0, ncell = 0, flags = bit0.
+ *  - every q in [0, 2e9) and g[0]*g[1]*g[2] <= 2^31 - 1: the grid; flags = 0.
+ *  - every q in [0, 2e9) but the product exceeds 2^31 - 1: g as computed, ncell = 0, flags = bit1.
+ *  - some q outside [0, 2e9) -- a quotient of 2e9 or more, an infinite extent (q = +inf, or NaN from inf - inf), an axis
+ *    without a finite coordinate (q = -inf or NaN): g = {0, 0, 0} on all three axes, ncell = 0, flags = bit1.  c0 is still
+ *    the per-axis minimum.
+ * ncell = 0 is what every consumer gates on (cppf_vote_center and cppf_grid_peaks give such a scene no votes and index 0);
+ * bit1 tells an unrepresentable grid from an empty scene. */
 typedef struct CppfSceneGrid {
   float   c0[3];    /* pc.min(0) */
   int32_t g[3];     /* ((max-min)/res).long() + 1 */
   int32_t ncell;    /* g[0]*g[1]*g[2], 0 if empty / overflow */
-  int32_t flags;    /* bit0: empty scene; bit1: cell count overflows int32 */
+  int32_t flags;    /* bit0: empty scene; bit1: grid not representable (cell count or an axis count overflows int32,
+                       infinite or all-NaN extent) */
 } CppfSceneGrid;
 
 /* Per-scene result record gathered across ranks (one RCCL all_gather). 160 bytes. */

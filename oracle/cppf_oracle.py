@@ -143,7 +143,10 @@ def tuple_normal_inputs(normal, idx):
         s = (p[:, 0] + p[:, 1]) + p[:, 2]
         q = (-ni) * nj
         sn = (q[:, 0] + q[:, 1]) + q[:, 2]
-        cols.append(np.maximum(s, sn)[:, None])
+        m = np.maximum(s, sn)
+        # torch.max orders -0 below +0 (the golden rows hold +0 wherever a zero normal makes the sums +-0); np.maximum returns
+        # either operand of an equal pair
+        cols.append(np.where(m == 0, F32(0.0), m)[:, None])
     return np.concatenate(cols, -1)
 
 
