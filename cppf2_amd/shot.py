@@ -23,6 +23,10 @@ _L = _lib.load()
 # src_shot/shot.cpp:25-32, 66-72 runs: single-pass float32 sums of the raw coordinates in (distance, index) order, closed-form
 # eigen33, float32 viewpoint flip; "f64" = float64 covariance about the query point + Jacobi (rounds 1-3; more accurate, but not
 # what the reference's checkpoints were trained on).  Every function below takes arithmetic=None = this module default.
+# "pcl" with long lists: a query with more than 512 points inside max(normal_r, shot_r) -- the LARGER of the two radii, whatever
+# the count inside normal_r -- keeps the float64 normal (capacities; pinned by tests/test_shot_edges_gpu.py).  With
+# equal radii that is "more than 512 neighbours"; with normal_r < shot_r (the defaults of compute() below) it also takes queries
+# with few normal neighbours out of PCL's arithmetic.  normals_device / estimate_normal have one radius: its own count decides.
 ARITHMETIC = "pcl"
 
 
@@ -117,7 +121,8 @@ def describe_device(pts, pt_off, normals, shot_r, out=None, nan_to_zero=False):
 
 def compute(pc, normal_r=0.1, shot_r=0.17, arithmetic=None):
     """shot.compute (src_shot/shot.cpp:45-100): returns [float32[N*352], float32[N*3]].  The normals follow
-    pcl::NormalEstimation's arithmetic (ARITHMETIC = "pcl") unless arithmetic="f64" asks for the float64 ones."""
+    pcl::NormalEstimation's arithmetic (ARITHMETIC = "pcl") unless arithmetic="f64" asks for the float64 ones -- or the point has
+    more than 512 points inside max(normal_r, shot_r): then its normal is the float64 one (see ARITHMETIC above)."""
     dev = ops._dev()
     pts = ops._t(np.asarray(pc, dtype=np.float32).reshape(-1, 3), torch.float32, dev)
     pt_off = ops._offsets([pts.shape[0]], dev)

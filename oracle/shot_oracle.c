@@ -570,6 +570,9 @@ int shot_oracle_max_threads(void) {
 }
 void shot_oracle_set_threads(int t) { g_threads = t; }
 
+void shot_oracle_describe(const float* pts, int n, float shot_r, int mode, const float* out_normal, float* out_shot,
+                          float* out_rf, double* out_diag);
+
 void shot_oracle_compute_ex(const float* pts, int n, float normal_r, float shot_r, int mode, float* out_shot,
                             float* out_normal, float* out_rf, double* out_diag) {
   /* Every query point is independent (own neighbour list, own output rows): with -fopenmp and g_threads != 1 the two loops run
@@ -591,6 +594,16 @@ void shot_oracle_compute_ex(const float* pts, int n, float normal_r, float shot_
   } else {
     shot_oracle_normals(pts, n, normal_r, out_normal);
   }
+  shot_oracle_describe(pts, n, shot_r, mode, out_normal, out_shot, out_rf, out_diag);
+}
+
+/* The descriptor half of shot_oracle_compute_ex with the CALLER'S normals [n,3] (what cppf_shot352_from_normals computes, and
+ * the reference of a run whose normals come from both arithmetics: the kernels keep the float64 normal of a query with more
+ * than NBR_CAP neighbours).  mode picks the neighbour order and the frame routine as in shot_oracle_compute_ex. */
+void shot_oracle_describe(const float* pts, int n, float shot_r, int mode, const float* out_normal, float* out_shot,
+                          float* out_rf, double* out_diag) {
+  const int nthreads = g_threads == 1 ? 1 : (g_threads > 1 ? g_threads : shot_oracle_max_threads());
+  (void)nthreads;
 #pragma omp parallel num_threads(nthreads)
   {
   Nb* nb = (Nb*)malloc(sizeof(Nb) * (size_t)(n > 0 ? n : 1));

@@ -30,6 +30,9 @@ def _load():
         _lib.shot_oracle_compute_ex.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p]
         _lib.shot_oracle_compute_ex.restype = None
+        _lib.shot_oracle_describe.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
+        _lib.shot_oracle_describe.restype = None
         _lib.shot_oracle_compute_color.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_void_p,
                                                    C.c_void_p, C.c_void_p]
         _lib.shot_oracle_compute_color.restype = None
@@ -81,6 +84,21 @@ def compute_ex(pc, normal_r, shot_r, pcl_arithmetic=False, threads=1):
     _load().shot_oracle_compute_ex(pc.ctypes.data, n, C.c_float(normal_r), C.c_float(shot_r), int(bool(pcl_arithmetic)),
                                    shot.ctypes.data, normal.ctypes.data, rf.ctypes.data, diag.ctypes.data)
     return shot, normal, rf, diag
+
+
+def describe(pc, normal, shot_r, pcl_arithmetic=False):
+    """The descriptor half of compute_ex with the caller's normals f32[N,3] (single-threaded).  Returns (shot, rf, diag)."""
+    pc = np.ascontiguousarray(pc, dtype=np.float32).reshape(-1, 3)
+    normal = np.ascontiguousarray(normal, dtype=np.float32).reshape(-1, 3)
+    n = pc.shape[0]
+    assert normal.shape[0] == n
+    shot = np.empty((n, 352), np.float32)
+    rf = np.empty((n, 9), np.float32)
+    diag = np.empty((n, 9), np.float64)
+    _load().shot_oracle_set_threads(1)
+    _load().shot_oracle_describe(pc.ctypes.data, n, C.c_float(shot_r), int(bool(pcl_arithmetic)), normal.ctypes.data,
+                                 shot.ctypes.data, rf.ctypes.data, diag.ctypes.data)
+    return shot, rf, diag
 
 
 def compute_color(pc, pc_color, normal_r, shot_r):

@@ -1,6 +1,10 @@
 """SHOT352 / normals.  PARITY UNPINNED against PCL (absent from the image, no reference fixtures): the C
 oracle (oracle/shot_oracle.c) restates PCL 1.9.1's algorithm and is validated here by invariants and
-known-answer clouds on CPU; the HIP kernel is compared with the oracle on the GPU."""
+known-answer clouds on CPU; the HIP kernel is compared with the oracle on the GPU.
+
+The clouds here are the common case (object-sized, ~90 .. 300 neighbours, equal radii).  The kernels' edges -- list capacities,
+a coarsened cell grid, unequal radii, tiny and empty scenes, batch independence, the exact rim, the from-normals and normals-only
+entry points -- are in tests/test_shot_edges_gpu.py, with the comparison (bars, exemption, caps) in one helper."""
 import numpy as np
 import pytest
 
