@@ -1,6 +1,15 @@
 """Online alignment refinement (eval.py:319-355).  PARITY UNPINNED: lietorch is not available, so the
 oracle's restatement of its published algorithm is checked for self-consistency on the CPU (tangent gradient against
-autograd, descent from a perturbed pose) and the HIP kernel is checked against that oracle on the GPU."""
+autograd, descent from a perturbed pose) and the HIP kernel is checked against that oracle on the GPU.
+
+The 100-step bars of test_hip_refinement_matches_the_oracle (2e-4 in t, 2e-3 in R) are no property of the arithmetic.  The
+loss is L1 and its gradient a sum of signs: a residual that crosses zero one ulp apart in two evaluations sends the two
+trajectories apart.  Measured on the CPU, the float32 oracle and the float64 reference of the same 100 steps
+(tests/refine_f64.py), two exact restatements, differ by up to 1.5e-4 in t and 4.6e-3 in R on a 32-pair problem of _problem
+with the deg=2.0, shift=0.004 start of _kept_problem (over seeds 0-7 of _problem(seed, N=3000, Tf=32): up to 3.8e-4 and
+2.0e-3 at the default noise, 3.1e-3 and 1.5e-2 at noise 2e-8; most seeds stay below 1e-6).  That test passes at the sizes it
+runs and cannot be extended to edge sizes: new refinement cases belong in tests/test_refine_edges_gpu.py, at a few steps
+with their preconditions asserted, not here at new sizes."""
 import numpy as np
 import pytest
 
