@@ -96,6 +96,12 @@ __host__ __device__ constexpr int rs_tile_bytes(int pc) { return pc * RS_FRAG_BY
 // beside the MFMAs (each VALU instruction per MFMA costs ~3 % through the clock, a ds_read_b128 ~5 %): without the operand
 // split the 256-wide kernel runs 14 % faster, without the weight stream 9 %, without its global loads / stores 8 %.  Hence
 // the compiler's own order within a tile region (fewer register moves, 5 % faster on the 256-wide identity kernel, equal elsewhere).
+// The vector work beside the MFMAs, trimmed where it changes no output bit (docs/measurements.md 13: ledger and kernel times): ReLU
+// as one v_maximum3_f32 instead of compare + select (rs_relu), and the weight pieces' DMA addresses as scalar arithmetic with the
+// lane's 16 bytes in the load's 32-bit offset register (RsStream::piece) instead of a 64-bit vector add per piece: 1.61 -> 1.38
+// vector instructions per MFMA in the 256-wide kernel, every launch 1.0-1.8 % shorter.  Measured and dropped: the x-tile masks only
+// on ragged K steps (a scalar branch around them: 1-2 % slower where the first product is long; two copies of the K loop: spills),
+// the second half of an x tile through the instruction offset (no different).
 // Also measured, not kept: two tiles per region with their MFMA chains alternating between the two accumulators (3-8 % slower),
 // output halves / quarters for the 256-wide layers at two wavefronts per SIMD (equal), register-staged instead of LDS-DMA weight
 // chunks, the residual of the 256-wide identity kernel loaded before the first product (128 registers more than there are: spills).
@@ -213,9 +219,10 @@ struct RsStream {
   int64_t left;                // chunks still to fetch over the remaining row blocks of this workgroup
   int stage;                   // stage the next acquire() returns
   int wave, lane;
-  const char* p_src;           // the chunk being fetched (this lane's 16 bytes of its piece 0), its stage, its last piece
+  const char* p_src;           // the chunk being fetched (its piece 0: wave-uniform, the lane's 16 bytes are added in piece()), its stage, its last piece
   char* p_dst;
   int p_last;
+  unsigned p_lane;             // this lane's byte offset within a piece (16 lane), re-made per chunk: see plan()
 
   __device__ __forceinline__ void shape(int chain) {
     if (LIN) {                                   // `chain` column groups, each one first-product segment (ks1 steps of T0 tiles)
@@ -228,9 +235,13 @@ struct RsStream {
   }
   // selects the next chunk of the stream (destination: stage st); its pieces are then issued one by one with piece()
   __device__ __forceinline__ void plan(int st) {
+    // an opaque copy per chunk: the zero-extension of the lane offset then stays in the code of the chunk's pieces, where the load
+    // can take it as its 32-bit offset register; hoisted out of the loops it turns every piece into a 64-bit vector add again
+    p_lane = (unsigned)lane * 16;
+    asm volatile("" : "+v"(p_lane));
     p_dst = ring + st * STAGE_BYTES;
     if (left <= 0) {                             // past the end: piece() re-reads the stream's first KiB into the idle stage
-      p_src = base + lane * 16;
+      p_src = base;
       p_last = 0;
       return;
     }
@@ -240,7 +251,7 @@ struct RsStream {
     const int steps = first ? ks1 : 2 * NT;
     const int ns = steps - pos < spc ? steps - pos : spc;
     const int pieces = ns * tiles * PC;
-    p_src = base + off + lane * 16;
+    p_src = base + off;
     p_last = pieces - 1;
     off += (int64_t)pieces * RS_FRAG_BYTES;
     pos += ns;
@@ -260,7 +271,10 @@ struct RsStream {
     if (RS_DBG & 1) return;
     int j = wave + q * WAVES;
     j = j < p_last ? j : p_last;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(p_src + j * RS_FRAG_BYTES),
+    // wave, p_last, p_src and p_dst are the same for the whole wavefront: the piece's address is scalar arithmetic, and the load
+    // takes it as an SGPR base plus this lane's 32-bit byte offset (no 64-bit vector add per piece)
+    const char* src = p_src + j * RS_FRAG_BYTES;
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + p_lane),
                                      (__attribute__((address_space(3))) void*)(p_dst + j * RS_FRAG_BYTES), 16, 0, 0);
   }
   __device__ __forceinline__ void prime() {                // the very first chunk: all pieces at once
@@ -350,6 +364,9 @@ struct RsX {
     p = j == 5 ? rw.g5 : p; p = j == 6 ? rw.g6 : p; p = j == 7 ? rw.g7 : p;
     return table + ((int64_t)p << fshift) + c;
   }
+  // (The redirection in issue() and the eight selects in read() are needed only by a K step that is ragged or past the end.  Skipping
+  // them elsewhere was measured and not kept -- a wave-uniform branch around them: the launches with long first products 1-2 %
+  // slower; the K loop in a masked and an unmasked copy: spills.  docs/measurements.md 13.)
   __device__ __forceinline__ void issue(int s, int slot, const RsRow rw) const {   // always exactly two vector-memory operations
     if (RS_DBG & 16) return;
     int f = 16 * s + 8 * g;
@@ -440,6 +457,12 @@ __device__ __forceinline__ void rs_product_h(f32x16 (&dst)[NTILES], const f32x16
     }
   }
 }
+
+// ReLU in ONE instruction per element (v_maximum3_f32 v, v, 0, 0: the NaN-propagating maximum, so NaN stays NaN like torch.relu)
+// instead of the compare + select of (h < 0) ? 0 : h.  The two differ for h = -0.0 only (+0.0 now, -0.0 before).  h is never
+// stored; it is split and multiplied: the pieces of -0 are (-0, +0, +0), those of +0 (+0, +0, +0), so only the SIGN of exact-zero
+// products changes, and a sum that holds any nonzero term, or starts from a nonzero (or +0) skip value, does not see it.
+__device__ __forceinline__ float rs_relu(float h) { return __builtin_elementwise_maximum(h, 0.0f); }
 
 // accumulator tile registers <- per-feature values v[32 tile + 8 q + 4 g + c] (bias vectors, rows of x)
 __device__ __forceinline__ void rs_load_tile(f32x16& acc, const float* v, int g) {
@@ -907,7 +930,7 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), 1) void reslayer_spli
 #pragma unroll
     for (int u = 0; u < NT; ++u) {
 #pragma unroll
-      for (int e = 0; e < 16; ++e) h[u][e] = (h[u][e] < 0.0f) ? 0.0f : h[u][e];        // NaN stays NaN like torch.relu
+      for (int e = 0; e < 16; ++e) h[u][e] = rs_relu(h[u][e]);
     }
     if (!PROJ && WAVES == 4) {                           // (measured alternative: after it; re-reads 1.2 GB per launch from HBM)
       if (PC == 2) {
@@ -959,7 +982,7 @@ __global__ __launch_bounds__(64 * rs_waves_mode(NT, MODE), 1) void reslayer_spli
 #pragma unroll
       for (int u = 0; u < NT; ++u) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) h[u][e] = (h[u][e] < 0.0f) ? 0.0f : h[u][e];
+        for (int e = 0; e < 16; ++e) h[u][e] = rs_relu(h[u][e]);
       }
       rs_product_h<NT, NT, PC>(o, h, ws, bs);
     }
