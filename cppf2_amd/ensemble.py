@@ -2,6 +2,7 @@
 both models (run_ensemble) or through an object's pair-feature table (run_table), the pipeline cache they share, and the stages
 every data mode repeats -- an instance's cloud from its mask, the stand-in descriptors, hypothesis verification and ICP after
 the vote, and the report items they leave."""
+import collections
 import os
 
 import numpy as np
@@ -38,6 +39,17 @@ def instance_cloud(depth_m, K, mask, res, seed, pixels=False):
         sub = np.random.RandomState(seed).randint(pc.shape[0], size=50000)
         pc, idxs = pc[sub], idxs[sub] if pixels else None
     return (pc, idxs) if pixels else pc
+
+
+def usable_cloud(depth_m, K, mask, cfg, seed, min_points=True):
+    """instance_cloud at cfg.res as (cloud, None), or (None, why it cannot be voted on): `too_few_points` for fewer than a tuple
+    takes (min_points=False: not checked, as the reference's own route), `too_large` for one that is too_wide (eval.py:200)."""
+    pc = instance_cloud(depth_m, K, mask, cfg.res, seed)
+    if min_points and pc.shape[0] < cfg.num_more + 2:
+        return None, "too_few_points"
+    if too_wide(pc, cfg.res):
+        return None, "too_large"
+    return pc, None
 
 
 def stand_in_descriptors(n, gen):
@@ -392,6 +404,10 @@ def _instance_hypotheses(selected, pick, hyps, enabled, H):
     return recs, centre
 
 
+# the settings of the stages after the vote, resolved once from the flags (eval._checked_flags)
+Stages = collections.namedtuple("Stages", "icp_iters icp_depth icp_model_weight hypotheses verify_tau centre_peaks")
+
+
 def _icp_item(st):
     """The ICP stats of one instance as the report carries them; the model-side figures when cppf_icp_refine_depth ran."""
     item = dict(inliers=int(st[0]), rms=float(st[1]), inlier_frac=float(st[2]), updates=int(st[3]))
@@ -400,54 +416,53 @@ def _icp_item(st):
     return item
 
 
-def _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, icp_iters, tau, icp_depth=False,
-                      icp_model_weight=1.0):
-    """The hypotheses of each instance in _instance_hypotheses' order, cut at H (empty slots past the end; an instance without a
-    pick gets only empty slots), then verify.select (ICP first when icp_iters > 0) on the instance's image.  The result also
-    carries centre int64 [B,H] (the centre-vote peak of each hypothesis, -1 for empty slots) and centre_peak int64 [B] (that of
-    the chosen one)."""
+def _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages):
+    """The hypotheses of each instance in _instance_hypotheses' order, cut at stages.hypotheses (empty slots past the end; an
+    instance without a pick gets only empty slots), then verify.select (ICP first when stages.icp_iters > 0) on the instance's
+    image.  The result also carries centre int64 [B,H] (the centre-vote peak of each hypothesis, -1 for empty slots) and
+    centre_peak int64 [B] (that of the chosen one)."""
     from cppf2_amd import verify
     from cppf2_amd.pipeline import RESULT_DTYPE
+    B, H = len(r["pick"]), stages.hypotheses
     recs = np.zeros((B, H), dtype=RESULT_DTYPE)
     centre = np.full((B, H), -1, dtype=np.int64)
     per_pass = r.get("centre_hypotheses") or [h_[None] for h_ in r["hypotheses"]]
     for b in range(B):
         recs[b], centre[b] = _instance_hypotheses(r["selected"][b], r["pick"][b], [pp_[:, b] for pp_ in per_pass], enabled, H)
-    if np.ndim(depth) == 3:                        # one image and mask per instance (main_bop)
-        img, msk = np.asarray(depth, dtype=np.float32), np.asarray(mask, dtype=bool)
-    else:
-        img = np.broadcast_to(np.asarray(depth, dtype=np.float32), (B,) + np.shape(depth))
-        msk = np.broadcast_to(np.asarray(mask, dtype=bool), (B,) + np.shape(mask))
-    extra = dict(icp_depth=True, icp_model_weight=icp_model_weight) if icp_depth else {}
-    out = verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=icp_iters, tau=tau,
-                        **extra)
+    img, msk = np.asarray(depth, dtype=np.float32), np.asarray(mask, dtype=bool)
+    if img.ndim == 2:                              # one image for the whole batch (the depth mode)
+        img = np.broadcast_to(img, (B,) + img.shape)
+    if msk.ndim == 2:
+        msk = np.broadcast_to(msk, (B,) + msk.shape)
+    extra = dict(icp_depth=True, icp_model_weight=stages.icp_model_weight) if stages.icp_depth else {}
+    out = verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=stages.icp_iters,
+                        tau=stages.verify_tau, **extra)
     out["centre"] = centre
     out["centre_peak"] = centre[np.arange(B), np.maximum(out["chosen"], 0)]
     return out
 
 
-def refine_and_verify(r, H, enabled, obj, depth, mask, K, pt_off, icp_model, icp_iters, tau, icp_depth=False, icp_model_weight=1.0):
-    """What follows the vote r of a batch whose instances have a mesh.  H > 1: H hypotheses per instance verified against
-    depth / mask ([H_img,W_img] for the whole batch or [B,H_img,W_img]), each refined by icp_iters first (_verify_instances);
-    else, with icp_iters > 0, the selected records refined against icp_model (after the ensemble selection and `opt`).
+def refine_and_verify(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages):
+    """What follows the vote r of a batch whose instances have a mesh; stages: the Stages settings.  hypotheses > 1: that many
+    hypotheses per instance verified against depth / mask ([H_img,W_img] for the whole batch or [B,H_img,W_img]), each refined
+    by icp_iters first (_verify_instances); else, with icp_iters > 0, the selected records refined against icp_model (after the
+    ensemble selection and `opt`).
     Returns (the B records to report: the verified ones, else the refined selected ones, else each instance's picked pass';
     icp_stats float32 [B,4 or 8] of the reported records or None; verify.select's dict or None)."""
     from cppf2_amd import icp
     B = len(r["pick"])
-    ver = icp_stats = None
-    if H > 1:
-        ver = _verify_instances(r, B, H, enabled, obj, depth, mask, K, pt_off, icp_model, icp_iters, tau, icp_depth, icp_model_weight)
-        if icp_iters > 0:
-            icp_stats = ver["icp"][np.arange(B), np.maximum(ver["chosen"], 0)]
+    if stages.hypotheses > 1:
+        ver = _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages)
+        icp_stats = ver["icp"][np.arange(B), np.maximum(ver["chosen"], 0)] if stages.icp_iters > 0 else None
         return ver["records"], icp_stats, ver
-    if icp_iters > 0:
-        extra = dict(depth=np.asarray(depth).astype(np.float32), K=K, model_weight=icp_model_weight) if icp_depth else {}
-        icp_stats = icp.refine(icp_model, r["pts"], pt_off, r["selected"], iters=icp_iters, **extra)
+    if stages.icp_iters > 0:
+        extra = dict(depth=np.asarray(depth).astype(np.float32), K=K, model_weight=stages.icp_model_weight) if stages.icp_depth else {}
+        icp_stats = icp.refine(icp_model, r["pts"], pt_off, r["selected"], iters=stages.icp_iters, **extra)
         return r["selected"], icp_stats, None
     return [r["records"][r["pick"][b]][b] for b in range(B)], None, None
 
 
-def instance_items(r, b, icp_stats, ver, centre_peaks):
+def instance_items(r, b, icp_stats, ver, stages):
     """The report items these stages leave for instance b: `verify` and `icp` where it has a pose, `table_hits` after run_table."""
     from cppf2_amd import verify
     items = {}
@@ -455,7 +470,7 @@ def instance_items(r, b, icp_stats, ver, centre_peaks):
         k_ = int(ver["chosen"][b])
         items["verify"] = dict(hypotheses=int(np.count_nonzero((ver["hypotheses"][b]["flags"] & verify.EMPTY) == 0)),
                                chosen=k_, score=float(ver["scores"][b, k_]), score_first=float(ver["scores"][b, 0]))
-        if centre_peaks > 1:
+        if stages.centre_peaks > 1:
             items["verify"]["centre_peak"] = int(ver["centre_peak"][b])
     if r["pick"][b] >= 0 and icp_stats is not None:
         items["icp"] = _icp_item(icp_stats[b])
@@ -469,20 +484,21 @@ _ICP_DEPTH_NOTE = ("%d point-to-plane ICP iterations against %s, observed points
 _CENTRE_NOTE = "; translation hypotheses from %d separated peaks of each centre vote (cppf_grid_peaks)"
 
 
-def stage_notes(against, icp_iters, icp_depth, icp_model_weight, hypotheses, verify_tau, centre_peaks, mask_cleaning=None):
+def stage_notes(against, stages, mask_cleaning=None):
     """The report's `mask_cleaning` / `icp_refinement` / `verification` entries.  against: what the ICP refined against, in
     words; mask_cleaning: the entry itself (the modes word it differently), None: masks were not cleaned."""
     from cppf2_amd import verify
     notes = {}
     if mask_cleaning is not None:
         notes["mask_cleaning"] = mask_cleaning
-    if icp_iters > 0:
-        notes["icp_refinement"] = "%d point-to-plane ICP iterations against %s (cppf_icp_refine)" % (icp_iters, against)
-        if icp_depth:
-            notes["icp_refinement"] = _ICP_DEPTH_NOTE % (icp_iters, against, icp_model_weight)
-    if hypotheses > 1:
+    if stages.icp_iters > 0:
+        notes["icp_refinement"] = "%d point-to-plane ICP iterations against %s (cppf_icp_refine)" % (stages.icp_iters, against)
+        if stages.icp_depth:
+            notes["icp_refinement"] = _ICP_DEPTH_NOTE % (stages.icp_iters, against, stages.icp_model_weight)
+    if stages.hypotheses > 1:
         notes["verification"] = ("%d pose hypotheses per instance from %d peaks per vote, rendered and compared with the depth "
-                                 "at tau = %g m (cppf_pose_hypotheses, cppf_depth_fit_counts)" % (hypotheses, verify.PEAKS, verify_tau))
-        if centre_peaks > 1:
-            notes["verification"] += _CENTRE_NOTE % centre_peaks
+                                 "at tau = %g m (cppf_pose_hypotheses, cppf_depth_fit_counts)"
+                                 % (stages.hypotheses, verify.PEAKS, stages.verify_tau))
+        if stages.centre_peaks > 1:
+            notes["verification"] += _CENTRE_NOTE % stages.centre_peaks
     return notes

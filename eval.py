@@ -103,10 +103,11 @@ import torch
 
 from cppf2_amd import geometry, ops, synth
 from cppf2_amd.config import load_checkpoint_config, load_config
-from cppf2_amd.ensemble import (PIPE_CACHE_BYTES, PIPE_CACHE_MAX, _PIPES, _TABLES, _hypothesis_args, _icp_item,  # noqa: F401
+from cppf2_amd.ensemble import (PIPE_CACHE_BYTES, PIPE_CACHE_MAX, _PIPES, _TABLES, Stages, _hypothesis_args, _icp_item,  # noqa: F401
                                 _instance_hypotheses, _pass_hypotheses, _pass_output, _pipelines, _side_streams, _teacher_prior,
                                 _verify_instances, _vote_cap, instance_cloud, instance_items, load_pair_table, needed_cells,
-                                refine_and_verify, run_ensemble, run_table, stage_notes, stand_in_descriptors, too_wide)
+                                refine_and_verify, run_ensemble, run_table, stage_notes, stand_in_descriptors, too_wide,
+                                usable_cloud)
 from cppf2_amd.models import BeyondCPPFDino, BeyondCPPFShot, load_reference_checkpoint
 from cppf2_amd.ops import get_topk_dir  # noqa: F401  (the reference defines it in this file, eval.py:37-51; demo.py and the notebook import it from here)
 
@@ -265,12 +266,14 @@ def image_instances(res, data_root, cfgs, seed, image_index, intrinsics=REAL_INT
 Vote = collections.namedtuple("Vote", "angle_tol imp_wt_margin backproj_ratio num_pairs num_rots opt geo_branch visual_branch seed")
 
 
-def vote_batch(setup, pcs, descs, scene_ids, v, up_sym, priors=None, scale_priors=None, hypotheses=1, centre_peaks=1, table=None):
+def vote_batch(setup, pcs, descs, scene_ids, v, up_sym, priors=None, scale_priors=None, stages=None, table=None):
     """One batch of instances through both models of setup = (cfg, dino_model, shot_model) (run_ensemble: this module's, looked
-    up when called), or through the object's pair-feature table when there is one (run_table); v: the Vote parameters.
+    up when called), or through the object's pair-feature table when there is one (run_table); v: the Vote parameters; stages:
+    the Stages settings, whose hypotheses and centre_peaks the vote keeps records for (None: the vote alone).
     Returns (their dict, the (model 0, model 1) pair of passes that took part)."""
     cfg, dino_model, shot_model = setup
-    H = hypotheses if hypotheses > 1 else None
+    H = stages.hypotheses if stages is not None and stages.hypotheses > 1 else None
+    centre_peaks = 1 if stages is None else stages.centre_peaks
     if table is not None:
         return run_table(cfg, table, pcs, v.seed, scene_ids, v.num_pairs, v.num_rots, v.angle_tol, v.imp_wt_margin, v.backproj_ratio,
                          bool(v.opt), up_sym, H, centre_peaks), (True, False)
@@ -279,9 +282,21 @@ def vote_batch(setup, pcs, descs, scene_ids, v, up_sym, priors=None, scale_prior
                         scale_priors=scale_priors, hypotheses=H, centre_peaks=centre_peaks), (v.geo_branch, v.visual_branch)
 
 
-def main_nocs(setups, log_dir, data_root="NOCS/real_test", out_dir=None, desc_npz=None, angle_tol=1., imp_wt_margin=0.01,
-              backproj_ratio=.1, num_pairs=50000, num_rots=180, opt=True, geo_branch=True, visual_branch=True, seed=0,
-              batch_instances=16, intrinsics=None, max_images=None, debug=False, out=None):
+def _opt_note(vote):
+    return "100 Adam steps (cppf_refine_pose)" if vote.opt else "off"
+
+
+def _emit(report, debug, out):
+    """The report printed as one JSON line, without its per-instance `results` unless debug, and written whole to `out`."""
+    print(json.dumps(report if debug else {k_: v for k_, v in report.items() if k_ != "results"}))
+    if out:
+        with open(out, "w") as f:
+            json.dump(report, f)
+    return report
+
+
+def main_nocs(setups, vote, log_dir, data_root="NOCS/real_test", out_dir=None, desc_npz=None, batch_instances=16, intrinsics=None,
+              max_images=None, debug=False, out=None):
     """eval.py:103-412 on a directory in the reference's layout: `log_dir`/results_*.pkl (detections + ground truth per image)
     and `data_root`/<scene>/<frame>_{depth,color}.png.  Instances are collected image by image exactly as the reference
     filters them, evaluated in batches per category on the GPU (run_ensemble), and written back into their image's record
@@ -292,7 +307,7 @@ def main_nocs(setups, log_dir, data_root="NOCS/real_test", out_dir=None, desc_np
     import pickle
     from cppf2_amd import metrics
     dev = ops._dev()
-    vote = Vote(angle_tol, imp_wt_margin, backproj_ratio, num_pairs, num_rots, opt, geo_branch, visual_branch, seed)
+    seed = vote.seed
     final_results = load_result_list(log_dir)
     if max_images:
         final_results = final_results[:int(max_images)]
@@ -366,10 +381,7 @@ def main_nocs(setups, log_dir, data_root="NOCS/real_test", out_dir=None, desc_np
                   pose_AP={"%ddeg_%dcm" % (d_, s_): mean_over(lambda c, i_=i_, j_=j_: aps[c, i_, j_])
                            for i_, d_ in enumerate((5, 10, 15)) for j_, s_ in enumerate((5, 10, 15))},
                   iou_AP={"IoU%d" % t_: mean_over(lambda c, t_=t_: iou_aps[c, t_]) for t_ in (25, 50, 75)})
-    print(json.dumps(report))
-    if out:
-        with open(out, "w") as f:
-            json.dump(report, f)
+    _emit(report, debug, out)                       # (it has no `results`: the whole report either way)
     report["final_results"] = final_results
     return report
 
@@ -385,11 +397,9 @@ def _icp_depth_flag(icp_depth, icp_model_weight, icp_iters):
     return bool(icp_depth), w
 
 
-def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1,
-             num_pairs=50000, num_rots=180, opt=True, geo_branch=True, visual_branch=True, seed=0, batch_instances=16,
-             icp_iters=0, hypotheses=1, verify_tau=None, teacher_prior=False, visib_gt_min=None, debug=False, out=None,
-             centre_peaks=1, detections=None, det_score_min=0.0, clean_masks=False, mask_jump=None, icp_depth=False,
-             icp_model_weight=1.0, pair_tables=None):
+def main_bop(setup, vote, stages, bop_root, split, out_csv, targets=None, mesh_scale=0.001, batch_instances=16, teacher_prior=False,
+             visib_gt_min=None, debug=False, out=None, detections=None, det_score_min=0.0, clean_masks=False, mask_jump=None,
+             pair_tables=None):
     """The instance-level path over one split of a BOP-format dataset (cppf2_amd.bop_data.Dataset): one estimate per valid
     ground-truth instance of every target, from its visible mask; poses written to `out_csv` in BOP's frame and scored with
     bop_data.score.  Instances of one object (and one K and image size) are evaluated in batches of `batch_instances` across
@@ -401,17 +411,15 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
     clean_masks: every mask is cut down to its largest depth-connected component (masks.clean, mask_jump metres) before
     back-projection and verification.  Returns the report (report["bop"] = bop_data.score's)."""
     import time
-    from cppf2_amd import bop, bop_data, icp, masks, verify
+    from cppf2_amd import bop, bop_data, icp, masks
     dev = ops._dev()
-    cfg = setup[0]
-    vote = Vote(angle_tol, imp_wt_margin, backproj_ratio, num_pairs, num_rots, opt, geo_branch, visual_branch, seed)
-    if pair_tables and teacher_prior:              # main() has checked this; kept for callers of this function, which is public
+    cfg, seed = setup[0], vote.seed
+    if pair_tables and teacher_prior:             # main() has checked this; kept for callers of this function, which is public
         raise ValueError("--pair_tables votes from the tables: it cannot be combined with --teacher_prior")
     up_sym = bool(cfg.get("up_sym", False))
     vmin = bop_data.VISIB_GT_MIN if visib_gt_min is None else float(visib_gt_min)
     ds = bop_data.Dataset(bop_root, split, mesh_scale)
     tlist = ds.targets(targets, vmin)
-    verify_tau = verify.TAU if verify_tau is None else float(verify_tau)
     icp_models, pending, rows, summary = {}, {}, [], []
     im_time = {}
     skipped = dict(too_few_points=0, too_large=0, no_pick=0)
@@ -459,14 +467,14 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
             scale_priors = np.stack([ext] * B)
         table = load_pair_table(os.path.join(str(pair_tables), "obj_%06d.npz" % o), dev) if pair_tables else None
         r, enabled = vote_batch(setup, [c_["pc"] for c_ in chunk], descs, [c_["gid"] for c_ in chunk], vote, up_sym, priors,
-                                scale_priors, hypotheses, centre_peaks, table)
-        if icp_iters > 0 and o not in icp_models:
+                                scale_priors, stages, table)
+        if stages.icp_iters > 0 and o not in icp_models:
             icp_models[o] = icp.ModelPoints.from_mesh(ds.mesh(o))
-        images = hypotheses > 1 or icp_depth       # (the stages that read the instances' images)
+        images = stages.hypotheses > 1 or stages.icp_depth       # (the stages that read the instances' images)
         reported, icp_stats, ver = refine_and_verify(
-            r, hypotheses, enabled, obj, np.stack([c_["depth"] for c_ in chunk]) if images else None,
+            r, enabled, obj, np.stack([c_["depth"] for c_ in chunk]) if images else None,
             np.stack([c_["mask"] for c_ in chunk]) if images else None, chunk[0]["K"],
-            np.cumsum([0] + [c_["pc"].shape[0] for c_ in chunk]), icp_models.get(o), icp_iters, verify_tau, icp_depth, icp_model_weight)
+            np.cumsum([0] + [c_["pc"].shape[0] for c_ in chunk]), icp_models.get(o), stages)
         dt = (time.perf_counter() - t0) / B
         for b, c_ in enumerate(chunk):
             im_time[(c_["scene_id"], c_["im_id"])] = im_time.get((c_["scene_id"], c_["im_id"]), 0.0) + dt + c_["prep_s"]
@@ -479,7 +487,7 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
                 skipped["no_pick"] += 1
                 continue
             rec = reported[b]
-            item.update(instance_items(r, b, icp_stats, ver, centre_peaks))
+            item.update(instance_items(r, b, icp_stats, ver, stages))
             score = -float(r["best"][b])
             if ver is not None:
                 if ver["chosen"][b] < 0:           # every hypothesis empty: the CSV's score stays a number
@@ -543,12 +551,9 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
             if clean_masks and not m.any():
                 skipped["empty_after_clean"] += 1
                 continue
-            pc = instance_cloud(depth.astype(np.float64), K, m, cfg.res, (seed * 1000003 + gid[0] - 1) & 0x7FFFFFFF)   # as the depth mode does
-            if pc.shape[0] < cfg.num_more + 2:
-                skipped["too_few_points"] += 1
-                continue
-            if too_wide(pc, cfg.res):                                                      # eval.py:200
-                skipped["too_large"] += 1
+            pc, why = usable_cloud(depth.astype(np.float64), K, m, cfg, (seed * 1000003 + gid[0] - 1) & 0x7FFFFFFF)   # as the depth mode does
+            if pc is None:
+                skipped[why] += 1
                 continue
             key = (o, K.tobytes(), depth.shape)
             pending.setdefault(key, []).append(dict(scene_id=s_id, im_id=im, gt_index=c_["gt_index"], gid=gid[0] - 1, pc=pc,
@@ -566,20 +571,15 @@ def main_bop(setup, bop_root, split, out_csv, targets=None, mesh_scale=0.001, an
     scored = bop_data.score(ds, bop_data.read_results(out_csv), tlist, vmin)              # the file, as a reader of it scores it
     report = dict(data="bop", bop_root=str(bop_root), split=str(split), targets=len(tlist), instances=len(summary), rows=len(rows),
                   skipped=skipped, out_csv=str(out_csv), teacher_prior=bool(teacher_prior),
-                  opt_refinement="100 Adam steps (cppf_refine_pose)" if opt else "off", bop=scored, results=summary)
+                  opt_refinement=_opt_note(vote), bop=scored, results=summary)
     if pair_tables:
         report.update(pair_tables=str(pair_tables), table_hits=[s_.get("table_hits") for s_ in summary])
     if dets is not None:
         report.update(detections=n_detections, detections_file=str(detections), det_score_min=float(det_score_min))
     cleaning = ("largest depth-connected component of each mask, neighbours within %g m (cppf_mask_components)" % mask_jump
                 if clean_masks else None)
-    report.update(stage_notes("each object's model", icp_iters, icp_depth, icp_model_weight, hypotheses, verify_tau, centre_peaks,
-                              cleaning))
-    print(json.dumps(report if debug else {k_: v for k_, v in report.items() if k_ != "results"}))
-    if out:
-        with open(out, "w") as f:
-            json.dump(report, f)
-    return report
+    report.update(stage_notes("each object's model", stages, cleaning))
+    return _emit(report, debug, out)
 
 
 def _centre_peaks_flag(centre_peaks, hypotheses):
@@ -692,7 +692,8 @@ def _explain_flags(f):
 def _checked_flags(**kw):
     """main()'s keyword arguments as a namespace, after every rule that ties one flag to another: the first broken rule raises
     its ValueError, before a device, a model or a file is touched.  Normalised on the way: icp_iters, hypotheses, centre_peaks
-    ints; icp_depth, icp_model_weight; clean_masks true under either spelling."""
+    ints; icp_depth, icp_model_weight; clean_masks true under either spelling.  f.stages: those six settings as the Stages
+    record the drivers pass on, verify_tau resolved to its default here and nowhere else."""
     f = types.SimpleNamespace(**kw)
     bop_mode = f.data == "bop"
     on_mesh = f.data == "depth" and (f.mesh or f.models_dir)
@@ -737,6 +738,9 @@ def _checked_flags(**kw):
         raise ValueError("--icp_iters > 0 refines against the object's mesh: it needs --data=depth and --mesh")
     if not bop_mode and f.gt_pose is not None and not on_mesh:
         raise ValueError("--gt_pose scores the pose against the object's mesh (BOP metrics): it needs --data=depth and --mesh")
+    from cppf2_amd import verify
+    f.stages = Stages(f.icp_iters, f.icp_depth, f.icp_model_weight, f.hypotheses,
+                      verify.TAU if f.verify_tau is None else float(f.verify_tau), f.centre_peaks)
     return f
 
 
@@ -812,11 +816,7 @@ def _finish(report, acc, categories, debug, out, out_pkl):
         import pickle
         with open(out_pkl, "wb") as f:
             pickle.dump(record, f)
-    print(json.dumps(report if debug else {k_: v for k_, v in report.items() if k_ != "results"}))
-    if out:
-        with open(out, "w") as f:
-            json.dump(report, f)
-    return report
+    return _emit(report, debug, out)
 
 
 def main_synthetic(setups, categories, vote, num_scenes=8, num_points=4096, debug=False, out=None, out_pkl=None):
@@ -839,16 +839,16 @@ def main_synthetic(setups, categories, vote, num_scenes=8, num_points=4096, debu
         r, _ = vote_batch(setups[cat], [s["pc"] for s in scenes], descs, scene_ids, vote, up_sym, priors,
                           np.stack([s["extent"] for s in scenes]))
         _add_results(acc, cat, scene_ids, r, [r["records"][r["pick"][b]][b] for b in range(len(scenes))], up_sym, scenes)
-    report = dict(categories=categories, instances=len(acc.summary),
-                  opt_refinement="100 Adam steps (cppf_refine_pose)" if vote.opt else "off", results=acc.summary)
+    report = dict(categories=categories, instances=len(acc.summary), opt_refinement=_opt_note(vote), results=acc.summary)
     return _finish(report, acc, categories, debug, out, out_pkl)
 
 
-def _score_against_gt(item, bop_obj, d, K, gt_R, gt_t, r, b, reported, ver, icp_stats):
-    """The BOP errors of instance b's reported pose (of its first hypothesis; of its pose before ICP) against --gt_pose, on the
-    depth image d and K, into item[`bop`] ([`bop_first`], [`bop_before_icp`]); an instance without an estimate scores +inf.
-    Returns the reported pose's errors, for the run's average recall."""
+def _score_against_gt(item, gt, d, K, r, b, reported, ver, icp_stats):
+    """The BOP errors of instance b's reported pose (of its first hypothesis; of its pose before ICP) against --gt_pose, gt =
+    (the object's bop.ObjectInfo, R, t), on the depth image d and K, into item[`bop`] ([`bop_first`], [`bop_before_icp`]); an
+    instance without an estimate scores +inf.  Returns the reported pose's errors, for the run's average recall."""
     from cppf2_amd import bop
+    bop_obj, gt_R, gt_t = gt
     poses = [reported[b]] + ([ver["hypotheses"][b, 0]] if ver is not None else [])
     poses += [r["records"][r["pick"][b]][b]] if icp_stats is not None else []
     nan = (np.full((3, 3), np.nan), np.full(3, np.nan))
@@ -861,88 +861,7 @@ def _score_against_gt(item, bop_obj, d, K, gt_R, gt_t, r, b, reported, ver, icp_
     return {k_: v_[:1] for k_, v_ in err.items()}
 
 
-def main_depth(setups, categories, vote, depth, mask, intrinsics=None, depth_scale=1000.0, mesh=None, mesh_scale=1.0, icp_iters=0,
-               icp_depth=False, icp_model_weight=1.0, gt_pose=None, models_info=None, hypotheses=1, verify_tau=None,
-               centre_peaks=1, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None, propose=None,
-               explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001):
-    """One depth + mask PNG pair (example_data layout): one instance, evaluated once per category of `categories`; with `mesh`
-    its pose is refined (icp_iters), verified (hypotheses) and scored against gt_pose (BOP errors), see the module docstring.
-    propose: segment.propose's keyword arguments; the proposed masks then stand where the one of `mask` stood, one instance
-    each in one batch per category.  explain: _explain_flags' dict (the report's `scene`); models_dir, pair_tables, obj_ids,
-    model_scale: the objects of the multi-object form, which stand where mesh and pair_table stood."""
-    from PIL import Image
-    from cppf2_amd import bop, icp, masks, render, verify
-    dev = ops._dev()
-    if models_dir:
-        objects = _scene_objects(models_dir, pair_tables, obj_ids, model_scale, icp_iters)
-        d = np.array(Image.open(depth)).astype(np.float64) / float(depth_scale)
-        K = np.array(intrinsics if intrinsics is not None else REAL_INTRINSICS, dtype=np.float64).reshape(3, 3)
-        return _depth_proposals(setups, categories, vote, d, K, propose, None, None, None, None, "each object's model", icp_iters,
-                                icp_depth, icp_model_weight, hypotheses, verify.TAU if verify_tau is None else float(verify_tau),
-                                centre_peaks, None, debug, out, out_pkl, explain=explain, objects=objects, pair_tables=pair_tables)
-    icp_model = icp.ModelPoints.from_mesh(render.load_mesh(mesh, mesh_scale)) if icp_iters > 0 else None
-    bop_obj, bop_reported = None, []
-    if gt_pose is not None:
-        info = None
-        if models_info:
-            with open(models_info) as f:
-                info = json.load(f)
-        bop_obj = bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale), models_info=info, mesh_scale=mesh_scale)
-        gt_R, gt_t = bop.load_pose(gt_pose)
-    verify_obj = None
-    if hypotheses > 1:
-        verify_tau = verify.TAU if verify_tau is None else float(verify_tau)
-        verify_obj = bop_obj if bop_obj is not None else bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale))
-    d = np.array(Image.open(depth)).astype(np.float64) / float(depth_scale)
-    K = np.array(intrinsics if intrinsics is not None else REAL_INTRINSICS, dtype=np.float64).reshape(3, 3)
-    if propose is not None:
-        return _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj, verify_obj,
-                                (gt_R, gt_t) if bop_obj is not None else None, os.path.basename(mesh or ""), icp_iters, icp_depth,
-                                icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl, explain=explain)
-    m = np.array(Image.open(mask))
-    m = (m[..., 0] if m.ndim == 3 else m) > 0
-    cleaning = None
-    if clean_mask:
-        # the largest depth-connected component of the mask (cppf_mask_components): what is back-projected and verified
-        kept, stats = masks.clean(m[None], d.astype(np.float32), 0, masks.JUMP if mask_jump is None else float(mask_jump))
-        m = kept[0].cpu().numpy() > 0
-        stats = [int(x) for x in stats[0].cpu().numpy()]
-        cleaning = dict(components=stats[0], kept_pixels=stats[2], valid_pixels=stats[3])
-        if not m.any():
-            raise ValueError("--clean_mask: no depth-connected component of the mask has %d pixels" % masks.MIN_PIXELS)
-    acc = Results([], [], [], [], [], [])
-    for ci, cat in enumerate(categories):           # the instance is scene `ci` of the run: its tuple / uniform streams' seed
-        cfg = setups[cat][0]
-        up_sym = cat in UP_SYM or bool(cfg.get("up_sym", False))
-        pc = instance_cloud(d, K, m, cfg.res, vote.seed)                                   # eval.py:185-197; no guard on too few points
-        if too_wide(pc, cfg.res):                                                          # eval.py:200
-            continue
-        # (a table pass reads no descriptor)
-        descs = [] if pair_table else [stand_in_descriptors(pc.shape[0], vote.seed + 1 + ci).numpy()]
-        r, enabled = vote_batch(setups[cat], [pc], descs, [ci], vote, up_sym, hypotheses=hypotheses, centre_peaks=centre_peaks,
-                                table=load_pair_table(pair_table, dev) if pair_table else None)
-        reported, icp_stats, ver = refine_and_verify(r, hypotheses, enabled, verify_obj, d, m, K, np.cumsum([0, pc.shape[0]]),
-                                                     icp_model, icp_iters, verify_tau, icp_depth, icp_model_weight)
-        _add_results(acc, cat, [ci], r, reported, up_sym)
-        item = acc.summary[-1]
-        item.update(instance_items(r, 0, icp_stats, ver, centre_peaks))
-        if bop_obj is not None:
-            bop_reported.append(_score_against_gt(item, bop_obj, d, K, gt_R, gt_t, r, 0, reported, ver, icp_stats))
-    report = dict(categories=categories, instances=len(acc.summary),
-                  opt_refinement="100 Adam steps (cppf_refine_pose)" if vote.opt else "off", results=acc.summary)
-    if pair_table:
-        report.update(pair_table=str(pair_table), table_hits=[s_["table_hits"] for s_ in acc.summary])
-    report.update(stage_notes(os.path.basename(mesh or ""), icp_iters, icp_depth, icp_model_weight, hypotheses, verify_tau,
-                              centre_peaks, cleaning))
-    if icp_model is not None:
-        report["icp"] = [s_["icp"] for s_ in acc.summary if "icp" in s_]
-    if bop_reported:
-        errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
-        report["bop"] = dict(bop.average_recall(errs, bop_obj.diameter, d.shape[1]), delta=bop.DELTA, taus=list(bop.TAUS))
-    return _finish(report, acc, categories, debug, out, out_pkl)
-
-
-def _scene_objects(models_dir, pair_tables, obj_ids, model_scale, icp_iters):
+def _scene_objects(models_dir, pair_tables, obj_ids, model_scale, stages):
     """The objects of the multi-object form, read through bop_data.Models as a BOP dataset's are: obj_%06d.ply of models_dir
     (all of them without obj_ids) with their models_info.json entries, and obj_%06d.npz of pair_tables.  A list of dicts (obj_id,
     obj: bop.ObjectInfo, icp_model, pair_table: the file's path; a missing table is an error when it is loaded)."""
@@ -952,7 +871,7 @@ def _scene_objects(models_dir, pair_tables, obj_ids, model_scale, icp_iters):
         obj_ids = models.ids()
         if not obj_ids:
             raise FileNotFoundError("--models_dir=%s holds no obj_%%06d.ply" % models_dir)
-    return [dict(obj_id=int(o), obj=models.object(o), icp_model=icp.ModelPoints.from_mesh(models.mesh(o)) if icp_iters > 0 else None,
+    return [dict(obj_id=int(o), obj=models.object(o), icp_model=icp.ModelPoints.from_mesh(models.mesh(o)) if stages.icp_iters > 0 else None,
                  pair_table=os.path.join(str(pair_tables), "obj_%06d.npz" % int(o))) for o in obj_ids]
 
 
@@ -1010,58 +929,63 @@ def _explain_scene(cands, objs, d, region, K, tau, explain):
                 parameters=dict(explain, tau=float(tau)))
 
 
-def _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj, verify_obj, gt, against, icp_iters, icp_depth,
-                     icp_model_weight, hypotheses, verify_tau, centre_peaks, pair_table, debug, out, out_pkl, explain=None,
-                     objects=None, pair_tables=None):
-    """main_depth with proposed masks (segment.propose on the depth image d, metres, with the run's seed): per category one batch
-    whose instances are the proposals that give a usable cloud, each with the cloud, scene index and tuple streams a --mask run
-    of its mask has.  gt: (R, t) of --gt_pose or None.  explain: _explain_flags' dict: the verified poses become the candidates
-    of _explain_scene.  objects: _scene_objects' list (the multi-object form): the batches run once per object, with its mesh
-    and table where verify_obj, icp_model and pair_table stood, and every item carries obj_id."""
-    from cppf2_amd import bop, segment
+# what the instance loop of one depth image reads besides its masks and objects: the depth in metres and K, the categories'
+# setups, the Vote and Stages settings, what the ICP refined against (the report's words), and where the report goes
+DepthRun = collections.namedtuple("DepthRun", "d K setups vote stages against debug out out_pkl")
+
+
+def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, explain=None, cleaning=None, pair_tables=None):
+    """The depth mode over the masks (bool [M,H,W]) of the image of ctx, a DepthRun: per object and category one batch whose
+    instances are the masks that give a usable cloud, each with the cloud, scene index and tuple streams a --mask run of its mask
+    has; voted, refined and verified as ctx.stages says, then reported (_finish).
+    objects: dicts of obj (bop.ObjectInfo or None), icp_model and pair_table (a path or None), one per run over the masks; those
+    of the multi-object form (_scene_objects) also hold obj_id, which every item then carries, and pair_tables names their folder.
+    proposed: None for the one given mask, the reference's route: no guard on too few points (eval.py:185-197), a too-wide cloud
+    dropped silently (eval.py:200), `cleaning` as the report's mask_cleaning.  Else (props, plane, propose), what segment.propose
+    returned and its keyword arguments: unusable clouds are counted, items carry their proposal, and the report gains plane,
+    proposals, proposed, skipped, mask_proposals and best.
+    gt: (the object's bop.ObjectInfo, R, t) of --gt_pose or None: every instance of the given mask is scored; of proposals the best
+    one when the verification chose one, else every one.  explain: _explain_flags' dict: the verified poses become the candidates
+    of _explain_scene."""
+    from cppf2_amd import bop
     dev = ops._dev()
-    pm, props, plane = segment.propose(d.astype(np.float32), K, vote.seed, **propose)
-    pmasks = pm.cpu().numpy() > 0
+    d, K, vote, stages = ctx.d, ctx.K, ctx.vote, ctx.stages
+    props, plane, propose = proposed or (None, None, None)
+    multi = "obj_id" in objects[0]
     acc = Results([], [], [], [], [], [])
     skipped = dict(too_large=0, too_few_points=0)
     proposals, best, bop_reported, cands = [], None, [], []
-    multi = objects is not None
-    if not multi:
-        objects = [dict(obj=verify_obj, icp_model=icp_model, pair_table=pair_table)]
     for oi, ob in enumerate(objects):
         tag = dict(obj_id=ob["obj_id"]) if multi else {}
-        verify_obj, icp_model, pair_table = ob["obj"], ob["icp_model"], ob["pair_table"]
-        for ci, cat in enumerate(categories):
-            cfg = setups[cat][0]
+        for ci, cat in enumerate(categories):       # an instance is scene `ci` of the run: its tuple / uniform streams' seed
+            cfg = ctx.setups[cat][0]
             up_sym = cat in UP_SYM or bool(cfg.get("up_sym", False))
             ranks, pcs = [], []
-            for p_, m in enumerate(pmasks):
-                pc = instance_cloud(d, K, m, cfg.res, vote.seed)
-                if pc.shape[0] < cfg.num_more + 2:
-                    skipped["too_few_points"] += 1
-                elif too_wide(pc, cfg.res):                                                    # eval.py:200
-                    skipped["too_large"] += 1
+            for p_, m in enumerate(masks):
+                pc, why = usable_cloud(d, K, m, cfg, vote.seed, min_points=props is not None)
+                if pc is None:
+                    skipped[why] += 1
                 else:
                     ranks.append(p_)
                     pcs.append(pc)
             B = len(pcs)
             if not B:
                 continue
-            descs = [] if pair_table else [stand_in_descriptors(pc.shape[0], vote.seed + 1 + ci).numpy() for pc in pcs]
-            r, enabled = vote_batch(setups[cat], pcs, descs, [ci] * B, vote, up_sym, hypotheses=hypotheses, centre_peaks=centre_peaks,
-                                    table=load_pair_table(pair_table, dev) if pair_table else None)
-            images = hypotheses > 1 or icp_depth
-            reported, icp_stats, ver = refine_and_verify(
-                r, hypotheses, enabled, verify_obj, np.broadcast_to(d.astype(np.float32), (B,) + d.shape) if images else None,
-                pmasks[ranks] if images else None, K, np.cumsum([0] + [pc.shape[0] for pc in pcs]), icp_model, icp_iters, verify_tau,
-                icp_depth, icp_model_weight)
+            # (a table pass reads no descriptor)
+            descs = [] if ob["pair_table"] else [stand_in_descriptors(pc.shape[0], vote.seed + 1 + ci).numpy() for pc in pcs]
+            r, enabled = vote_batch(ctx.setups[cat], pcs, descs, [ci] * B, vote, up_sym, stages=stages,
+                                    table=load_pair_table(ob["pair_table"], dev) if ob["pair_table"] else None)
+            reported, icp_stats, ver = refine_and_verify(r, enabled, ob["obj"], d, masks[ranks], K,
+                                                         np.cumsum([0] + [pc.shape[0] for pc in pcs]), ob["icp_model"], stages)
             _add_results(acc, cat, [ci] * B, r, reported, up_sym)
             items = acc.summary[-B:]
             top = None
             for b, item in enumerate(items):
-                item.update(instance_items(r, b, icp_stats, ver, centre_peaks))
-                item.update(proposal=ranks[b], pixels=props[ranks[b]]["pixels"], bbox=props[ranks[b]]["bbox"], points=int(pcs[b].shape[0]),
-                            **tag)
+                item.update(instance_items(r, b, icp_stats, ver, stages))
+                if props is None:
+                    continue
+                prop = props[ranks[b]]
+                item.update(proposal=ranks[b], pixels=prop["pixels"], bbox=prop["bbox"], points=int(pcs[b].shape[0]), **tag)
                 entry = dict(proposal=ranks[b], category=cat, pixels=item["pixels"], bbox=item["bbox"], R=None, t=None, **tag)
                 if r["pick"][b] >= 0:
                     entry.update(R=np.asarray(reported[b]["R"], dtype=np.float64).reshape(3, 3).tolist(),
@@ -1078,34 +1002,80 @@ def _depth_proposals(setups, categories, vote, d, K, propose, icp_model, bop_obj
                 proposals.append(entry)
             if top is not None and (best is None or items[top]["verify"]["score"] > best["score"]):
                 best = dict(proposal=ranks[top], category=cat, score=items[top]["verify"]["score"], **tag)
-            if bop_obj is not None:
-                # --gt_pose: the best proposal when the verification chose one, else every proposal; the keys of the --mask route
-                for b in ([top] if ver is not None else range(B)):
-                    if b is not None:
-                        bop_reported.append(_score_against_gt(items[b], bop_obj, d, K, gt[0], gt[1], r, b, reported, ver, icp_stats))
-    report = dict(categories=categories, instances=len(acc.summary),
-                  opt_refinement="100 Adam steps (cppf_refine_pose)" if vote.opt else "off", results=acc.summary,
-                  plane=dict(n=plane["n"], d=plane["d"], inliers=plane["inliers"], usable_hypotheses=plane["usable_hypotheses"],
-                             valid_pixels=plane["valid_pixels"]),
-                  proposals=proposals, proposed=len(props), skipped=skipped,
-                  mask_proposals=dict(propose, seed=int(vote.seed), components=plane["components"],
-                                      large_components=plane["large_components"]))
-    if best is not None:
-        report["best"] = best
+            if gt is not None:
+                scored = range(B) if props is None or ver is None else [b for b in (top,) if b is not None]
+                bop_reported += [_score_against_gt(items[b], gt, d, K, r, b, reported, ver, icp_stats) for b in scored]
+    report = dict(categories=categories, instances=len(acc.summary), opt_refinement=_opt_note(vote), results=acc.summary)
+    if props is not None:
+        report.update(plane=dict(n=plane["n"], d=plane["d"], inliers=plane["inliers"], usable_hypotheses=plane["usable_hypotheses"],
+                                 valid_pixels=plane["valid_pixels"]),
+                      proposals=proposals, proposed=len(props), skipped=skipped,
+                      mask_proposals=dict(propose, seed=int(vote.seed), components=plane["components"],
+                                          large_components=plane["large_components"]))
+        if best is not None:
+            report["best"] = best
     if multi:
         report.update(obj_ids=[ob["obj_id"] for ob in objects], pair_tables=str(pair_tables),
                       table_hits=[s_["table_hits"] for s_ in acc.summary])
-    elif pair_table:
-        report.update(pair_table=str(pair_table), table_hits=[s_["table_hits"] for s_ in acc.summary])
-    report.update(stage_notes(against, icp_iters, icp_depth, icp_model_weight, hypotheses, verify_tau, centre_peaks, None))
-    if icp_iters > 0:
+    elif objects[0]["pair_table"]:
+        report.update(pair_table=str(objects[0]["pair_table"]), table_hits=[s_["table_hits"] for s_ in acc.summary])
+    report.update(stage_notes(ctx.against, stages, cleaning))
+    if stages.icp_iters > 0:
         report["icp"] = [s_["icp"] for s_ in acc.summary if "icp" in s_]
     if bop_reported:
         errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
-        report["bop"] = dict(bop.average_recall(errs, bop_obj.diameter, d.shape[1]), delta=bop.DELTA, taus=list(bop.TAUS))
+        report["bop"] = dict(bop.average_recall(errs, gt[0].diameter, d.shape[1]), delta=bop.DELTA, taus=list(bop.TAUS))
     if explain is not None:
-        report["scene"] = _explain_scene(cands, [ob["obj"] for ob in objects], d, pmasks.any(0), K, verify_tau, explain)
-    return _finish(report, acc, categories, debug, out, out_pkl)
+        report["scene"] = _explain_scene(cands, [ob["obj"] for ob in objects], d, masks.any(0), K, stages.verify_tau, explain)
+    return _finish(report, acc, categories, ctx.debug, ctx.out, ctx.out_pkl)
+
+
+def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=None, depth_scale=1000.0, mesh=None, mesh_scale=1.0,
+               gt_pose=None, models_info=None, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None,
+               propose=None, explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001):
+    """One depth + mask PNG pair (example_data layout): one instance, evaluated once per category of `categories`; with `mesh`
+    its pose is refined (stages.icp_iters), verified (stages.hypotheses) and scored against gt_pose (BOP errors), see the module
+    docstring.  propose: segment.propose's keyword arguments; the proposed masks then stand where the one of `mask` stood, one
+    instance each in one batch per category.  explain: _explain_flags' dict (the report's `scene`); models_dir, pair_tables,
+    obj_ids, model_scale: the objects of the multi-object form, which stand where mesh and pair_table stood.  This reads the
+    inputs; _depth_instances runs them."""
+    from PIL import Image
+    from cppf2_amd import bop, icp, masks, render, segment
+    gt = None
+    if models_dir:
+        objects, against = _scene_objects(models_dir, pair_tables, obj_ids, model_scale, stages), "each object's model"
+    else:
+        icp_model = icp.ModelPoints.from_mesh(render.load_mesh(mesh, mesh_scale)) if stages.icp_iters > 0 else None
+        obj = None
+        if gt_pose is not None:
+            info = None
+            if models_info:
+                with open(models_info) as f:
+                    info = json.load(f)
+            obj = bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale), models_info=info, mesh_scale=mesh_scale)
+            gt = (obj,) + tuple(bop.load_pose(gt_pose))
+        elif stages.hypotheses > 1:
+            obj = bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale))
+        objects, against = [dict(obj=obj, icp_model=icp_model, pair_table=pair_table)], os.path.basename(mesh or "")
+    d = np.array(Image.open(depth)).astype(np.float64) / float(depth_scale)
+    K = np.array(intrinsics if intrinsics is not None else REAL_INTRINSICS, dtype=np.float64).reshape(3, 3)
+    ctx = DepthRun(d, K, setups, vote, stages, against, debug, out, out_pkl)
+    if propose is not None:
+        pm, props, plane = segment.propose(d.astype(np.float32), K, vote.seed, **propose)
+        return _depth_instances(ctx, pm.cpu().numpy() > 0, objects, categories, (props, plane, propose), gt, explain,
+                                pair_tables=pair_tables)
+    m = np.array(Image.open(mask))
+    m = (m[..., 0] if m.ndim == 3 else m) > 0
+    cleaning = None
+    if clean_mask:
+        # the largest depth-connected component of the mask (cppf_mask_components): what is back-projected and verified
+        kept, stats = masks.clean(m[None], d.astype(np.float32), 0, masks.JUMP if mask_jump is None else float(mask_jump))
+        m = kept[0].cpu().numpy() > 0
+        stats = [int(x) for x in stats[0].cpu().numpy()]
+        cleaning = dict(components=stats[0], kept_pixels=stats[2], valid_pixels=stats[3])
+        if not m.any():
+            raise ValueError("--clean_mask: no depth-connected component of the mask has %d pixels" % masks.MIN_PIXELS)
+    return _depth_instances(ctx, m[None], objects, categories, gt=gt, cleaning=cleaning)
 
 
 def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, num_rots=180, opt=True, debug=False,
@@ -1124,12 +1094,10 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
     dev = ops._dev()
     torch.manual_seed(seed)
     if data == "bop":                               # its models come from the dataset
-        return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev, models=not pair_tables), bop_root, split, out_csv,
-                        targets=targets, mesh_scale=float(model_scale), batch_instances=batch_instances, icp_iters=f.icp_iters,
-                        hypotheses=f.hypotheses, verify_tau=verify_tau, teacher_prior=bool(teacher_prior), debug=debug, out=out,
-                        centre_peaks=f.centre_peaks, detections=detections, det_score_min=float(det_score_min),
-                        clean_masks=f.clean_masks, mask_jump=mask_jump, icp_depth=f.icp_depth,
-                        icp_model_weight=f.icp_model_weight, pair_tables=pair_tables, **vote._asdict())
+        return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev, models=not pair_tables), vote, f.stages, bop_root, split, out_csv,
+                        targets=targets, mesh_scale=float(model_scale), batch_instances=batch_instances,
+                        teacher_prior=bool(teacher_prior), debug=debug, out=out, detections=detections,
+                        det_score_min=float(det_score_min), clean_masks=f.clean_masks, mask_jump=mask_jump, pair_tables=pair_tables)
     custom = False
     if categories is None:
         if category:
@@ -1150,15 +1118,14 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         setups = {c: load_category(c, ckpt_dir, ckpt_shot, ckpt_dino, device=dev) for c in categories}
     if data == "nocs":
         assert log_dir, "--data=nocs needs --log_dir (the directory of results_*.pkl, eval.py:72-76)"
-        return main_nocs(setups, log_dir, data_root=data_root, out_dir=out_dir, desc_npz=desc_npz, batch_instances=batch_instances,
-                         intrinsics=intrinsics, max_images=max_images, debug=debug, out=out, **vote._asdict())
+        return main_nocs(setups, vote, log_dir, data_root=data_root, out_dir=out_dir, desc_npz=desc_npz,
+                         batch_instances=batch_instances, intrinsics=intrinsics, max_images=max_images, debug=debug, out=out)
     if data == "depth":
-        return main_depth(setups, categories, vote, depth=depth, mask=mask, intrinsics=intrinsics, depth_scale=depth_scale, mesh=mesh,
-                          mesh_scale=mesh_scale, icp_iters=f.icp_iters, icp_depth=f.icp_depth, icp_model_weight=f.icp_model_weight,
-                          gt_pose=gt_pose, models_info=models_info, hypotheses=f.hypotheses, verify_tau=verify_tau,
-                          centre_peaks=f.centre_peaks, clean_mask=f.clean_masks, mask_jump=mask_jump, pair_table=pair_table,
-                          debug=debug, out=out, out_pkl=out_pkl, propose=f.propose, explain=f.explain, models_dir=models_dir,
-                          pair_tables=pair_tables, obj_ids=f.obj_ids, model_scale=float(model_scale))
+        return main_depth(setups, categories, vote, f.stages, depth, mask, intrinsics=intrinsics, depth_scale=depth_scale, mesh=mesh,
+                          mesh_scale=mesh_scale, gt_pose=gt_pose, models_info=models_info, clean_mask=f.clean_masks,
+                          mask_jump=mask_jump, pair_table=pair_table, debug=debug, out=out, out_pkl=out_pkl, propose=f.propose,
+                          explain=f.explain, models_dir=models_dir, pair_tables=pair_tables, obj_ids=f.obj_ids,
+                          model_scale=float(model_scale))
     return main_synthetic(setups, categories, vote, num_scenes=num_scenes, num_points=num_points, debug=debug, out=out,
                           out_pkl=out_pkl)
 
