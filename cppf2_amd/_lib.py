@@ -153,6 +153,9 @@ EXPERIMENTAL = {
     "cppf_reslayer_split_debug_grid": (_i, [_i32]),
     "cppf_decode_bins_prior": (_i, [_i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
     "cppf_reslayer_split_decode_prior": (_i, [_p, _i64, _i, _i64, _p, _i64, _p, _p, _p, _p, C.c_float, _p, _p, _p, _p]),
+    "cppf_support_counts": (_i, [_i, _i, _i, _p, _p, _p, _i, _p, _p, _f, _p, _p]),
+    "cppf_solid_overlap_workspace_bytes": (_i64, [_i, _i, _i]),
+    "cppf_solid_overlap": (_i, [_i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _i64, _p]),
 }
 
 SIGNATURES = dict(STABLE, **EXPERIMENTAL)

@@ -123,6 +123,14 @@ class ObjectInfo:
                               torch.from_numpy(self.syms.reshape(-1, 12).copy()).to(dev))
         return self._dev[key]
 
+    def reversed_faces(self, dev):
+        """faces int32 [F,3] on `dev` with every triangle's second and third index swapped (the winding reversed: with back-face
+        culling the renderer then draws the nearest back face), made once per device and kept beside the device copy."""
+        key = str(dev) + ":reversed"
+        if key not in self._dev:
+            self._dev[key] = self.device(dev)[1][:, [0, 2, 1]].contiguous()
+        return self._dev[key]
+
 
 def pose_from_bop(R, t, mesh_scale, centre):
     """BOP scene_gt poses (x_cam = R x + t, x on the uncentred model and t in the model file's units) -> the record convention

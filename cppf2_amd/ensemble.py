@@ -416,11 +416,12 @@ def _icp_item(st):
     return item
 
 
-def _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages):
+def _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages, support=None):
     """The hypotheses of each instance in _instance_hypotheses' order, cut at stages.hypotheses (empty slots past the end; an
     instance without a pick gets only empty slots), then verify.select (ICP first when stages.icp_iters > 0) on the instance's
-    image.  The result also carries centre int64 [B,H] (the centre-vote peak of each hypothesis, -1 for empty slots) and
-    centre_peak int64 [B] (that of the chosen one)."""
+    image; support: verify.select's plane, support_tau and max_sunk (the support check of solid.py) or None.  The result also
+    carries centre int64 [B,H] (the centre-vote peak of each hypothesis, -1 for empty slots) and centre_peak int64 [B] (that of
+    the chosen one)."""
     from cppf2_amd import verify
     from cppf2_amd.pipeline import RESULT_DTYPE
     B, H = len(r["pick"]), stages.hypotheses
@@ -435,6 +436,7 @@ def _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages
     if msk.ndim == 2:
         msk = np.broadcast_to(msk, (B,) + msk.shape)
     extra = dict(icp_depth=True, icp_model_weight=stages.icp_model_weight) if stages.icp_depth else {}
+    extra.update(support or {})
     out = verify.select(obj, img, msk, K, recs, pts=r["pts"], pt_off=pt_off, icp_model=icp_model, icp_iters=stages.icp_iters,
                         tau=stages.verify_tau, **extra)
     out["centre"] = centre
@@ -442,17 +444,17 @@ def _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages
     return out
 
 
-def refine_and_verify(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages):
+def refine_and_verify(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages, support=None):
     """What follows the vote r of a batch whose instances have a mesh; stages: the Stages settings.  hypotheses > 1: that many
     hypotheses per instance verified against depth / mask ([H_img,W_img] for the whole batch or [B,H_img,W_img]), each refined
     by icp_iters first (_verify_instances); else, with icp_iters > 0, the selected records refined against icp_model (after the
-    ensemble selection and `opt`).
+    ensemble selection and `opt`).  support: the support check's arguments for verify.select (hypotheses > 1 only) or None.
     Returns (the B records to report: the verified ones, else the refined selected ones, else each instance's picked pass';
     icp_stats float32 [B,4 or 8] of the reported records or None; verify.select's dict or None)."""
     from cppf2_amd import icp
     B = len(r["pick"])
     if stages.hypotheses > 1:
-        ver = _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages)
+        ver = _verify_instances(r, enabled, obj, depth, mask, K, pt_off, icp_model, stages, support)
         icp_stats = ver["icp"][np.arange(B), np.maximum(ver["chosen"], 0)] if stages.icp_iters > 0 else None
         return ver["records"], icp_stats, ver
     if stages.icp_iters > 0:
@@ -472,6 +474,8 @@ def instance_items(r, b, icp_stats, ver, stages):
                                chosen=k_, score=float(ver["scores"][b, k_]), score_first=float(ver["scores"][b, 0]))
         if stages.centre_peaks > 1:
             items["verify"]["centre_peak"] = int(ver["centre_peak"][b])
+        if "support" in ver:                       # the support check ran: (back, sunk, solid, open) per hypothesis
+            items["verify"].update(support=ver["support"][b].tolist(), refused=[bool(x_) for x_ in ver["refused"][b]])
     if r["pick"][b] >= 0 and icp_stats is not None:
         items["icp"] = _icp_item(icp_stats[b])
     if "table_hits" in r:

@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import segment as _segment
+from . import solid as _solid
 
 TAU = 0.02                                  # verify.TAU (not imported here: this module's checks need no library)
 MIN_GAIN = _segment.MIN_SEGMENT_PIXELS
@@ -42,15 +43,7 @@ def _checked(cand_off, tau, min_gain, viol_weight, max_rounds, who, limit=MAX_CA
         raise ValueError("%s: viol_weight must be >= 0, not %d" % (who, viol_weight))
     if not 1 <= max_rounds <= ROUNDS_LIMIT:
         raise ValueError("%s: max_rounds must be in 1 .. %d, not %d" % (who, ROUNDS_LIMIT, max_rounds))
-    off = np.asarray(cand_off.cpu().numpy() if hasattr(cand_off, "cpu") else cand_off).reshape(-1)
-    if off.size < 2 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError("%s: cand_off is int [I+1], I >= 1" % who)
-    off = off.astype(np.int64)
-    if off[0] != 0 or np.any(np.diff(off) < 0):
-        raise ValueError("%s: cand_off must start at 0 and never decrease" % who)
-    if np.any(np.diff(off) > limit):
-        raise ValueError("%s: at most %d candidates per image, not %d" % (who, limit, int(np.diff(off).max())))
-    return np.ascontiguousarray(off, dtype=np.int32), tau, min_gain, viol_weight, max_rounds
+    return _solid.checked_offsets(cand_off, who, limit), tau, min_gain, viol_weight, max_rounds
 
 
 def explain(depth, region, cand_off, renders, tau=TAU, min_gain=MIN_GAIN, viol_weight=VIOL_WEIGHT, max_rounds=MAX_ROUNDS):
@@ -106,17 +99,34 @@ def _explain(depth, region, cand_off, renders, tau, min_gain, viol_weight, max_r
 
 
 def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, min_gain=MIN_GAIN, viol_weight=VIOL_WEIGHT,
-                       max_rounds=MAX_ROUNDS, chunk=None, wide=False):
+                       max_rounds=MAX_ROUNDS, chunk=None, wide=False, plane=None, support_tau=_solid.SUPPORT_TAU,
+                       max_sunk=_solid.MAX_SUNK, solid=False, solid_tau=_solid.OVERLAP_TAU, max_overlap=_solid.MAX_OVERLAP):
     """Explains one depth image [H,W] (metres) by candidate poses: records (RESULT_DTYPE [C], C <= 64, with wide C <= 512 through
     explain_wide; R, t in the record convention of verify.py) of the objects objs (one bop.ObjectInfo or render.Mesh, or a list of them) with obj_of int [C] (the
     index into objs of each record; None: all are objs[0]).  The candidates are rendered as verify.select renders its
     hypotheses -- back faces culled; a record flagged empty, one that is not finite, or one that puts a vertex nearer than
     render.ZNEAR is not drawn, fits nothing and is never chosen -- and given to explain() with the region [H,W].
 
+    With plane (float32 [4] = (n, d) of the image's support plane, segment.fit_plane's) a candidate whose nearest back faces lie
+    more than support_tau below the plane on more than max_sunk of their pixels (solid.support_counts on the reversed-winding
+    render) is removed before the explanation.  With solid=True a candidate is ineligible once more than max_overlap of the
+    smaller solid of it and an earlier winner lies inside the other by more than solid_tau (solid.overlap_counts, DESIGN.md
+    section 25): the explanation is run, the first chosen candidate that conflicts with an earlier one is dropped, and it is run
+    again until no chosen pair conflicts -- dropping a non-winner changes no earlier round, so this is the greedy selection
+    with that one more rule, in at most C passes.
+
     Returns dict(records RESULT_DTYPE [n] (the chosen records, in the order they were chosen), chosen int64 [n] (their indices
-    in `records`), gain, net int64 [n], static int64 [C,3], labels uint8 [H,W] (host), region_pixels, explained_pixels)."""
-    off_check = _checked([0, len(records)], tau, min_gain, viol_weight, max_rounds, "scene.explain_candidates",
+    in `records`), gain, net int64 [n], static int64 [C,3] (zeros for a candidate refused below the plane), labels uint8 [H,W]
+    (host), region_pixels, explained_pixels, passes (explanations run), refused_support int64 [k] (indices in `records`),
+    refused_overlap [(candidate, the earlier winner it conflicts with)], and with plane support int64 [C,4] = (back, sunk,
+    solid, open))."""
+    who = "scene.explain_candidates"
+    off_check = _checked([0, len(records)], tau, min_gain, viol_weight, max_rounds, who,
                          MAX_CANDIDATES_WIDE if wide else MAX_CANDIDATES)
+    if plane is not None:
+        support_tau, max_sunk = _solid.checked_tau(support_tau, who, "support_tau"), _solid.checked_share(max_sunk, who, "max_sunk")
+    if solid:
+        solid_tau, max_overlap = _solid.checked_tau(solid_tau, who, "solid_tau"), _solid.checked_share(max_overlap, who, "max_overlap")
     import torch
     from . import bop, hostargs, ops, verify
     from .pipeline import RESULT_DTYPE
@@ -133,6 +143,7 @@ def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, mi
     d = hostargs.image_batch(depth, dev, "scene.explain_candidates", max_dim=MAX_DIM)
     _, Hi, Wi = (int(x) for x in d.shape)
     ren = torch.zeros((Cn, Hi, Wi), dtype=torch.float32, device=dev)
+    far = torch.zeros((Cn, Hi, Wi), dtype=torch.float32, device=dev) if plane is not None or solid else None
     empty = (host["flags"] & verify.EMPTY) != 0
     R, t = host["R"].reshape(-1, 3, 3), host["t"].reshape(-1, 3)
     for o, obj in enumerate(objs):
@@ -140,11 +151,37 @@ def explain_candidates(objs, depth, region, K, records, obj_of=None, tau=TAU, mi
         draw = verify.drawable(obj, R[idx], t[idx], ~empty[idx])
         for a in range(0, idx.size, int(chunk or verify.RENDER_CHUNK)):
             part = slice(a, a + int(chunk or verify.RENDER_CHUNK))
-            ren[torch.from_numpy(idx[part]).to(dev)] = verify.render_records(obj, R[idx[part]], t[idx[part]], draw[part], K, Hi, Wi, dev)
-    out = (explain_wide if wide else explain)(d, region, off_check[0], ren, tau, min_gain, viol_weight, max_rounds)
-    summary = out["summary"][0].cpu().numpy()
-    n = int(summary[2])
-    pick = out["chosen"][0, :n].cpu().numpy().astype(np.int64)
+            where = torch.from_numpy(idx[part]).to(dev)
+            ren[where] = verify.render_records(obj, R[idx[part]], t[idx[part]], draw[part], K, Hi, Wi, dev)
+            if far is not None:
+                far[where] = verify.render_records(obj, R[idx[part]], t[idx[part]], draw[part], K, Hi, Wi, dev, back=True)
+    alive = np.arange(Cn, dtype=np.int64)
+    extra = dict(refused_support=np.zeros(0, np.int64))
+    if plane is not None:
+        sup = _solid.support_counts(ren, far, [0, Cn], plane, K, support_tau).cpu().numpy() if Cn else np.zeros((0, 4), np.int64)
+        sunk = _solid.sunk_share(sup) > max_sunk
+        extra = dict(support=sup, refused_support=alive[sunk])
+        alive = alive[~sunk]
+    static = np.zeros((Cn, 3), dtype=np.int64)
+    refused_overlap, passes = [], 0
+    while True:
+        passes += 1
+        sub = ren if alive.size == Cn else ren[torch.from_numpy(alive).to(dev)]
+        out = (explain_wide if wide else explain)(d, region, [0, alive.size], sub, tau, min_gain, viol_weight, max_rounds)
+        summary = out["summary"][0].cpu().numpy()
+        n = int(summary[2])
+        pick = alive[out["chosen"][0, :n].cpu().numpy().astype(np.int64)]
+        if passes == 1:
+            static[alive] = out["static"].cpu().numpy()
+        clash = None
+        if solid and n >= 2:                               # the chosen ones: at most ROUNDS_LIMIT = 64 of them
+            at = torch.from_numpy(pick).to(dev)
+            hit = _solid.conflicts(_solid.overlap_counts(ren[at], far[at], [0, n], solid_tau), max_overlap)
+            clash = next(((k, e) for k in range(n) for e in range(k) if hit[k, e]), None)
+        if clash is None:
+            break
+        refused_overlap.append((int(pick[clash[0]]), int(pick[clash[1]])))
+        alive = alive[alive != pick[clash[0]]]
     return dict(records=host[pick].copy(), chosen=pick, gain=out["gain"][0, :n].cpu().numpy(), net=out["net"][0, :n].cpu().numpy(),
-                static=out["static"].cpu().numpy(), labels=out["labels"][0].cpu().numpy(), region_pixels=int(summary[0]),
-                explained_pixels=int(summary[1]))
+                static=static, labels=out["labels"][0].cpu().numpy(), region_pixels=int(summary[0]),
+                explained_pixels=int(summary[1]), passes=passes, refused_overlap=refused_overlap, **extra)

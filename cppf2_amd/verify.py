@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, bop, hostargs, icp, ops, render
+from . import _lib, bop, hostargs, icp, ops, render, solid
 from ._lib import CppfError
 from .pipeline import RESULT_DTYPE, record_bytes, records_of
 
@@ -125,13 +125,16 @@ def drawable(obj, R, t, ok):
     return ok & (z >= render.ZNEAR * (1 + 1e-5))
 
 
-def render_records(obj, R, t, draw, K, Hi, Wi, dev):
+def render_records(obj, R, t, draw, K, Hi, Wi, dev, back=False):
     """float32 [P,Hi,Wi] device tensor: obj at each pose with draw[p] set, back faces culled, in one cppf_render_depth call;
-    zeros (nothing drawn) for the others."""
+    zeros (nothing drawn) for the others.  back=True draws the reversed winding instead: the nearest BACK face of a closed mesh,
+    the far end of its first solid interval along the pixel's ray (solid.py)."""
     dr = np.flatnonzero(draw)
     ren = torch.zeros((len(R), Hi, Wi), dtype=torch.float32, device=dev)
     if dr.size:
         verts, faces, _ = obj.device(dev)
+        if back:
+            faces = obj.reversed_faces(dev)
         F = faces.shape[0]
         poses = torch.from_numpy(np.concatenate([R[dr], t[dr, :, None]], 2).reshape(-1, 12).astype(np.float32)).to(dev)
         ren[torch.from_numpy(dr).to(dev)] = render.render_depth(verts, faces.repeat(dr.size, 1), ops._offsets([F] * dr.size, dev),
@@ -140,7 +143,8 @@ def render_records(obj, R, t, draw, K, Hi, Wi, dev):
 
 
 def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_model=None, icp_iters=0, tau=TAU,
-           chunk=RENDER_CHUNK, icp_depth=False, icp_model_weight=1.0):
+           chunk=RENDER_CHUNK, icp_depth=False, icp_model_weight=1.0, plane=None, support_tau=solid.SUPPORT_TAU,
+           max_sunk=solid.MAX_SUNK):
     """Verifies H pose hypotheses of each of B instances and keeps one per instance.
 
     obj_or_mesh: a bop.ObjectInfo or a render.Mesh (metres); depth [B,H_img,W_img] or [H_img,W_img] (metres, 0 = no reading) and
@@ -150,11 +154,18 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
     float32 [N,3] (camera frame), pt_off int [B+1]; with icp_depth that refinement also uses the instance's depth image (the
     model-to-depth terms of icp.refine(depth=...), weighted by icp_model_weight) and icp is float32 [B,H,8].  Each hypothesis is then rendered (back faces culled); one that is not
     finite, or puts a vertex nearer than render.ZNEAR (the renderer does not clip), is not drawn and scores 0.  score() of its
-    fit_counts at (tau,) ranks it, and choose() picks.
+    fit_counts at (tau,) ranks it, and choose() picks.  With plane (float32 [4] or [B,4] = (n, d) of the support plane, as
+    segment.fit_plane returns it) each hypothesis is also rendered with the winding reversed, and one whose nearest back faces lie
+    more than support_tau below the plane on more than max_sunk of their pixels (solid.support_counts) is refused: it scores 0
+    like one that cannot be drawn; the dict then also has support int64 [B,H,4] = (back, sunk, solid, open) and refused bool
+    [B,H].  plane=None changes nothing.
 
     Returns dict(records RESULT_DTYPE [B] (the chosen records, flags bit5, the hypothesis index in pad_[1]; an instance whose
     hypotheses are all empty keeps records[b, 0] unmarked), chosen int64 [B] (-1: none), scores float64 [B,H] (NaN for empty
     slots), counts int64 [B,H,5], hypotheses RESULT_DTYPE [B,H] (after ICP), icp float32 [B,H,4] ([B,H,8] with icp_depth) or None)."""
+    if plane is not None:
+        support_tau = solid.checked_tau(support_tau, "verify.select", "support_tau")
+        max_sunk = solid.checked_share(max_sunk, "verify.select", "max_sunk")
     obj = obj_or_mesh if isinstance(obj_or_mesh, bop.ObjectInfo) else bop.ObjectInfo.from_mesh(obj_or_mesh)
     dev = ops._dev()
     host, rec = _as_records(records)
@@ -189,6 +200,12 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
     P = B * Hh
     draw = drawable(obj, R, t, ~empty.reshape(-1))
     counts = np.zeros((P, N_COUNTS + 1), dtype=np.int64)
+    support = np.zeros((P, 4), dtype=np.int64)
+    if plane is not None:
+        pl = ops._t(plane, torch.float32, dev).reshape(-1, 4)
+        pl = pl.expand(B, 4).contiguous() if pl.shape[0] == 1 else pl
+        if pl.shape[0] != B:
+            raise CppfError("verify.select: %d instances, %d planes" % (B, pl.shape[0]))
     img_of = np.repeat(np.arange(B), Hh)
     for a in range(0, P, int(chunk)):
         idx = np.arange(a, min(P, a + int(chunk)))
@@ -196,8 +213,13 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
         # the chunk's hypotheses lie on consecutive images: offsets over all B images, zero-length outside the chunk
         hyp_off = np.searchsorted(img_of[idx], np.arange(B + 1), side="left").astype(np.int32)
         counts[idx] = fit_counts(d, m, hyp_off, ren, (tau,)).cpu().numpy()
+        if plane is not None and B:
+            far = render_records(obj, R[idx], t[idx], draw[idx], K, Hi, Wi, dev, back=True)
+            support[idx] = solid.support_counts(ren, far, hyp_off, pl, K, support_tau).cpu().numpy()
     sc = score(counts)
     sc[~draw] = 0.0
+    refused = (solid.sunk_share(support) > max_sunk) if plane is not None else np.zeros(P, dtype=bool)
+    sc[refused] = 0.0
     sc = sc.reshape(B, Hh)
     pick = choose(sc, empty)
     sc[empty] = np.nan
@@ -205,4 +227,7 @@ def select(obj_or_mesh, depth, mask, K, records, pts=None, pt_off=None, icp_mode
     hit = pick >= 0
     out["flags"][hit] |= CHOSEN
     out["pad_"][hit, 1] = pick[hit]
-    return dict(records=out, chosen=pick, scores=sc, counts=counts.reshape(B, Hh, -1), hypotheses=host, icp=stats)
+    res = dict(records=out, chosen=pick, scores=sc, counts=counts.reshape(B, Hh, -1), hypotheses=host, icp=stats)
+    if plane is not None:
+        res.update(support=support.reshape(B, Hh, 4), refused=refused.reshape(B, Hh))
+    return res

@@ -90,6 +90,13 @@ What the image cannot provide is stated, not faked:
     is "at least half", not swept), so --explain_min_score is refused beside it.  The 512 best supported are kept when there
     are more (`dropped`); instances and rejected entries gain `hypothesis` and `support`, the reasons are `below_min_support`
     and `no_gain`, and `parameters` gains `min_support` and `hypotheses`.
+    `--support_check [--support_tau=0.01 --support_max_share=0.1]` (needs --hypotheses > 1 and a mesh)
+    refuses a hypothesis whose nearest back faces lie more than support_tau under the plane the proposals were cut with on
+    more than that share of their pixels (cppf_support_counts): it scores 0 in the verification and is `below_table` in the
+    explanation.  `--explain_solid [--solid_tau=0.02 --solid_max_share=0.1]` (needs --explain_scene) makes a candidate
+    ineligible once more than that share of the smaller solid of it and an earlier instance lies inside the other by more
+    than solid_tau (cppf_solid_overlap): reason `inside`, `inside_of` the instance's index.  The report gains `support` and
+    `refused` per hypothesis under `verify`, `support_counts` per candidate of the scene, `scene.passes` and `solid_checks`.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import collections
@@ -689,6 +696,39 @@ def _explain_flags(f):
     return e
 
 
+_SOLID_FLAGS = (("support_check", ("support_tau", "support_max_share")), ("explain_solid", ("solid_tau", "solid_max_share")))
+
+
+def _solid_flags(f):
+    """The solid-interval checks' parameters (cppf2_amd/solid.py) from --support_check and --explain_solid: dict(support=dict(tau,
+    max_share) or None, overlap=dict(tau, max_share) or None), or None when both are off.  Read after f.propose, f.explain and
+    f.hypotheses."""
+    for switch, values in _SOLID_FLAGS:
+        given = [k_ for k_ in values if getattr(f, k_) is not None]
+        if given and not getattr(f, switch):
+            raise ValueError("--%s sets a threshold of --%s: it needs that flag" % (given[0], switch))
+    if not f.support_check and not f.explain_solid:
+        return None
+    from cppf2_amd import solid
+
+    def pair(tau_flag, share_flag, tau0, share0):
+        tau, share = getattr(f, tau_flag), getattr(f, share_flag)
+        return dict(tau=solid.checked_tau(tau0 if tau is None else tau, "eval.py", "--" + tau_flag),
+                    max_share=solid.checked_share(share0 if share is None else share, "eval.py", "--" + share_flag))
+    out = dict(support=None, overlap=None)
+    if f.support_check:
+        if f.propose is None:
+            raise ValueError("--support_check tests poses against the plane the proposals were cut with: it needs --propose_masks")
+        if f.hypotheses <= 1:
+            raise ValueError("--support_check refuses verified hypotheses: it needs --hypotheses > 1")
+        out["support"] = pair("support_tau", "support_max_share", solid.SUPPORT_TAU, solid.MAX_SUNK)
+    if f.explain_solid:
+        if f.explain is None:
+            raise ValueError("--explain_solid constrains the scene explanation: it needs --explain_scene")
+        out["overlap"] = pair("solid_tau", "solid_max_share", solid.OVERLAP_TAU, solid.MAX_OVERLAP)
+    return out
+
+
 def _checked_flags(**kw):
     """main()'s keyword arguments as a namespace, after every rule that ties one flag to another: the first broken rule raises
     its ValueError, before a device, a model or a file is touched.  Normalised on the way: icp_iters, hypotheses, centre_peaks
@@ -738,6 +778,7 @@ def _checked_flags(**kw):
         raise ValueError("--icp_iters > 0 refines against the object's mesh: it needs --data=depth and --mesh")
     if not bop_mode and f.gt_pose is not None and not on_mesh:
         raise ValueError("--gt_pose scores the pose against the object's mesh (BOP metrics): it needs --data=depth and --mesh")
+    f.solid = _solid_flags(f)
     from cppf2_amd import verify
     f.stages = Stages(f.icp_iters, f.icp_depth, f.icp_model_weight, f.hypotheses,
                       verify.TAU if f.verify_tau is None else float(f.verify_tau), f.centre_peaks)
@@ -890,12 +931,14 @@ def _hypothesis_candidates(ver, b, tag):
     return out
 
 
-def _explain_scene(cands, objs, d, region, K, tau, explain):
+def _explain_scene(cands, objs, d, region, K, tau, explain, solid=None):
     """The report's `scene` entry: the candidates (dicts with proposal, category, score, record, obj: index into objs, and
     obj_id in the multi-object form) with a score of at least min_score, the 64 best of them when there are more (ties to the
     lower index), explained over `region` by scene.explain_candidates.  With explain["hypotheses"] (--explain_hypotheses) the
     candidates are hypotheses (they also carry hypothesis and support), the gate is a support of at least min_support, and the
-    512 best supported go through the wide form."""
+    512 best supported go through the wide form.  solid: explain_candidates' keyword arguments of the support and overlap checks
+     or nothing: with them a candidate may be rejected as below_table, or as inside the instance whose
+    index `inside_of` gives, every entry of a run with a plane carries its support_counts, and the entry gains `passes`."""
     from cppf2_amd import scene
     from cppf2_amd.pipeline import RESULT_DTYPE
     wide = bool(explain.get("hypotheses"))
@@ -916,17 +959,31 @@ def _explain_scene(cands, objs, d, region, K, tau, explain):
     recs = np.array([c_["record"] for c_ in kept], dtype=RESULT_DTYPE).reshape(-1)
     ex = scene.explain_candidates(objs, d.astype(np.float32), region, K, recs, [c_["obj"] for c_ in kept], tau=tau,
                                   min_gain=explain["min_gain"], viol_weight=explain["viol_weight"], max_rounds=explain["max_rounds"],
-                                  wide=wide)
+                                  wide=wide, **(solid or {}))
+
+    def counts(j):
+        return dict(support_counts=[int(x_) for x_ in ex["support"][j]]) if "support" in ex else {}
     instances = []
     for j, g, n in zip(ex["chosen"], ex["gain"], ex["net"]):
         rec = kept[int(j)]["record"]
         instances.append(entry(kept[int(j)], R=np.asarray(rec["R"], dtype=np.float64).reshape(3, 3).tolist(),
-                               t=np.asarray(rec["t"], dtype=np.float64).tolist(), gain=int(g), net=int(n)))
+                               t=np.asarray(rec["t"], dtype=np.float64).tolist(), gain=int(g), net=int(n), **counts(int(j))))
     taken = {int(j) for j in ex["chosen"]}
-    rejected += [entry(c_, reason="no_gain") for j, c_ in enumerate(kept) if j not in taken]
-    return dict(instances=instances, explained_pixels=ex["explained_pixels"], region_pixels=ex["region_pixels"], rejected=rejected,
-                dropped=dropped, candidates=len(kept),
-                parameters=dict(explain, tau=float(tau)))
+    sunk = {int(j) for j in ex["refused_support"]}
+    inside = {int(j): [int(x_) for x_ in ex["chosen"]].index(int(w_)) for j, w_ in ex["refused_overlap"]}
+    for j, c_ in enumerate(kept):
+        if j in sunk:
+            rejected.append(entry(c_, reason="below_table", **counts(j)))
+        elif j in inside:
+            rejected.append(entry(c_, reason="inside", inside_of=inside[j], **counts(j)))
+        elif j not in taken:
+            rejected.append(entry(c_, reason="no_gain", **counts(j)))
+    out = dict(instances=instances, explained_pixels=ex["explained_pixels"], region_pixels=ex["region_pixels"], rejected=rejected,
+               dropped=dropped, candidates=len(kept),
+               parameters=dict(explain, tau=float(tau)))
+    if solid:
+        out["passes"] = ex["passes"]
+    return out
 
 
 # what the instance loop of one depth image reads besides its masks and objects: the depth in metres and K, the categories'
@@ -934,7 +991,8 @@ def _explain_scene(cands, objs, d, region, K, tau, explain):
 DepthRun = collections.namedtuple("DepthRun", "d K setups vote stages against debug out out_pkl")
 
 
-def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, explain=None, cleaning=None, pair_tables=None):
+def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, explain=None, cleaning=None, pair_tables=None,
+                     solid=None):
     """The depth mode over the masks (bool [M,H,W]) of the image of ctx, a DepthRun: per object and category one batch whose
     instances are the masks that give a usable cloud, each with the cloud, scene index and tuple streams a --mask run of its mask
     has; voted, refined and verified as ctx.stages says, then reported (_finish).
@@ -946,11 +1004,16 @@ def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, ex
     proposals, proposed, skipped, mask_proposals and best.
     gt: (the object's bop.ObjectInfo, R, t) of --gt_pose or None: every instance of the given mask is scored; of proposals the best
     one when the verification chose one, else every one.  explain: _explain_flags' dict: the verified poses become the candidates
-    of _explain_scene."""
+    of _explain_scene.  solid: _solid_flags' dict or None; its `support` entry makes verify.select and the explanation refuse
+    poses that sink into the proposals' plane, its `overlap` entry makes the explanation refuse a pose inside an earlier instance."""
     from cppf2_amd import bop
     dev = ops._dev()
     d, K, vote, stages = ctx.d, ctx.K, ctx.vote, ctx.stages
     props, plane, propose = proposed or (None, None, None)
+    support = None
+    if solid is not None and solid["support"] is not None:
+        support = dict(plane=np.array(list(plane["n"]) + [plane["d"]], dtype=np.float32), support_tau=solid["support"]["tau"],
+                       max_sunk=solid["support"]["max_share"])
     multi = "obj_id" in objects[0]
     acc = Results([], [], [], [], [], [])
     skipped = dict(too_large=0, too_few_points=0)
@@ -976,7 +1039,8 @@ def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, ex
             r, enabled = vote_batch(ctx.setups[cat], pcs, descs, [ci] * B, vote, up_sym, stages=stages,
                                     table=load_pair_table(ob["pair_table"], dev) if ob["pair_table"] else None)
             reported, icp_stats, ver = refine_and_verify(r, enabled, ob["obj"], d, masks[ranks], K,
-                                                         np.cumsum([0] + [pc.shape[0] for pc in pcs]), ob["icp_model"], stages)
+                                                         np.cumsum([0] + [pc.shape[0] for pc in pcs]), ob["icp_model"], stages,
+                                                         **(dict(support=support) if support else {}))
             _add_results(acc, cat, [ci] * B, r, reported, up_sym)
             items = acc.summary[-B:]
             top = None
@@ -1026,19 +1090,24 @@ def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, ex
         errs = {k_: np.concatenate([e_[k_] for e_ in bop_reported]) for k_ in ("vsd", "mssd", "mspd")}
         report["bop"] = dict(bop.average_recall(errs, gt[0].diameter, d.shape[1]), delta=bop.DELTA, taus=list(bop.TAUS))
     if explain is not None:
-        report["scene"] = _explain_scene(cands, [ob["obj"] for ob in objects], d, masks.any(0), K, stages.verify_tau, explain)
+        more = dict(support or {})
+        if solid is not None and solid["overlap"] is not None:
+            more.update(solid=True, solid_tau=solid["overlap"]["tau"], max_overlap=solid["overlap"]["max_share"])
+        report["scene"] = _explain_scene(cands, [ob["obj"] for ob in objects], d, masks.any(0), K, stages.verify_tau, explain, more)
+    if solid is not None:
+        report["solid_checks"] = solid
     return _finish(report, acc, categories, ctx.debug, ctx.out, ctx.out_pkl)
 
 
 def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=None, depth_scale=1000.0, mesh=None, mesh_scale=1.0,
                gt_pose=None, models_info=None, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None,
-               propose=None, explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001):
+               propose=None, explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001, solid=None):
     """One depth + mask PNG pair (example_data layout): one instance, evaluated once per category of `categories`; with `mesh`
     its pose is refined (stages.icp_iters), verified (stages.hypotheses) and scored against gt_pose (BOP errors), see the module
     docstring.  propose: segment.propose's keyword arguments; the proposed masks then stand where the one of `mask` stood, one
     instance each in one batch per category.  explain: _explain_flags' dict (the report's `scene`); models_dir, pair_tables,
-    obj_ids, model_scale: the objects of the multi-object form, which stand where mesh and pair_table stood.  This reads the
-    inputs; _depth_instances runs them."""
+    obj_ids, model_scale: the objects of the multi-object form, which stand where mesh and pair_table stood.  solid:
+    _solid_flags' dict (the support and overlap checks of cppf2_amd/solid.py).  This reads the inputs; _depth_instances runs them."""
     from PIL import Image
     from cppf2_amd import bop, icp, masks, render, segment
     gt = None
@@ -1063,7 +1132,7 @@ def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=No
     if propose is not None:
         pm, props, plane = segment.propose(d.astype(np.float32), K, vote.seed, **propose)
         return _depth_instances(ctx, pm.cpu().numpy() > 0, objects, categories, (props, plane, propose), gt, explain,
-                                pair_tables=pair_tables)
+                                pair_tables=pair_tables, solid=solid)
     m = np.array(Image.open(mask))
     m = (m[..., 0] if m.ndim == 3 else m) > 0
     cleaning = None
@@ -1088,7 +1157,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          clean_mask=False, mask_jump=None, icp_depth=False, icp_model_weight=1.0, pair_table=None, pair_tables=None,
          propose_masks=False, plane_tau=None, plane_hypotheses=None, plane_min_height=None, min_segment_pixels=None,
          max_proposals=None, explain_scene=False, explain_min_score=None, explain_min_gain=None, explain_viol_weight=None,
-         explain_max=None, models_dir=None, obj_ids=None, explain_hypotheses=False, explain_min_support=None):
+         explain_max=None, models_dir=None, obj_ids=None, explain_hypotheses=False, explain_min_support=None,
+         support_check=False, support_tau=None, support_max_share=None, explain_solid=False, solid_tau=None, solid_max_share=None):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()
@@ -1125,7 +1195,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                           mesh_scale=mesh_scale, gt_pose=gt_pose, models_info=models_info, clean_mask=f.clean_masks,
                           mask_jump=mask_jump, pair_table=pair_table, debug=debug, out=out, out_pkl=out_pkl, propose=f.propose,
                           explain=f.explain, models_dir=models_dir, pair_tables=pair_tables, obj_ids=f.obj_ids,
-                          model_scale=float(model_scale))
+                          model_scale=float(model_scale), solid=f.solid)
     return main_synthetic(setups, categories, vote, num_scenes=num_scenes, num_points=num_points, debug=debug, out=out,
                           out_pkl=out_pkl)
 

@@ -8,7 +8,8 @@
  *   - the logit prior of the synthetic benchmarks: THE REFERENCE HAS NO PRIOR (eval.py:225-235 draws from the network's own
  *     logits).  It exists because the reference's checkpoints are not available: random-init weights need a teacher for votes to
  *     cluster.  bench.py reports value_no_prior beside the headline;
- *   - a test hook.
+ *   - a test hook;
+ *   - the solid-interval checks on candidate poses (cppf2_amd/solid.py): opt-in and new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -141,6 +142,35 @@ int cppf_reslayer_split16(const CppfReslayerSplit16Args* args);
  * process (the kernels' results do not depend on it; tests/test_mlp_split.py runs the counted-wait protocol at 1, 7 and all
  * CUs beside a saturating copy stream); 0 restores one workgroup per CU. */
 int cppf_reslayer_split_debug_grid(int32_t workgroups);
+
+/* ---- solid-interval checks on candidate poses: below the support plane, inside one another (not in the reference;
+ * cppf2_amd/solid.py) ----
+ * Per candidate two renders of one closed mesh at one pose, float32[P,H,W] each, 0 = nothing drawn: front (back faces culled: the
+ * nearest front face) and back (the same call with every triangle's winding reversed: the nearest back face); [front, back] is
+ * the first solid interval along the pixel's ray.  h_cand_off int32[I+1] on the HOST as cppf_scene_explain's (0 = h_cand_off[0]
+ * <= ... <= h_cand_off[I] = P <= 2^24), I >= 1, H, W <= 8192, tau >= 0 (metres).  Per pixel: back_c = b > 0, solid_c = f > 0 &&
+ * b > 0, open_c = (f > 0) != (b > 0) (float32 comparisons: NaN and -0.0 are not > 0).  The exact order of the float32
+ * operations is stated in cppf2_amd/csrc/cppf_solid.hip.  Integer counts only: an image's outputs do not depend on the batch or
+ * the order.  Experimental while the checks are opt-in and young: the signatures may still change without an ABI bump.
+ *
+ * cppf_support_counts: planes float32[I,4] = (n, d) as cppf_plane_fit writes them, Kmat float32[I,4] = (fx, fy, cx, cy).  Pixel
+ * (r, c), z = b: x = ((((float)c + 0.5f) - cx) * z) / fx, y = ((((float)r + 0.5f) - cy) * z) / fy, h = ((n.x*x + n.y*y) + n.z*z)
+ * + d; sunk_c = back_c && h < -tau.  A plane of zeros or of NaN sinks nothing.  counts int64[P,4] = (back, sunk, solid, open)
+ * per candidate, any number of candidates per image.  One launch per 128 images behind one clear, no workspace.
+ *
+ * cppf_solid_overlap: at most 64 candidates per image.  inter int64[P,64]: row cand_off[i] + a, column j < C_i = the pixels
+ * where a and j are both solid and (double)fminf(b_a, b_j) - (double)fmaxf(f_a, f_j) > (double)tau; symmetric, the diagonal = the
+ * solid pixels of a, columns C_i .. 63 are 0.  workspace: cppf_solid_overlap_workspace_bytes(I, H, W) bytes (8 per pixel; 0 for
+ * sizes the call refuses), 8-byte aligned.  Two launches per 128 images behind one clear, no host synchronisation.
+ *
+ * Both return CPPF_EINVAL for a negative or NaN tau, bad offsets, H or W above 8192, P above 2^24 and null pointers;
+ * cppf_solid_overlap returns CPPF_EUNSUPPORTED for more than 64 candidates on an image and CPPF_ECAPACITY for a workspace that
+ * is too small; all before any device work. */
+int cppf_support_counts(int I, int H, int W, const float* front, const float* back, const int32_t* h_cand_off, int P,
+                        const float* planes, const float* Kmat, float tau, int64_t* counts, void* stream);
+int64_t cppf_solid_overlap_workspace_bytes(int I, int H, int W);
+int cppf_solid_overlap(int I, int H, int W, const float* front, const float* back, const int32_t* h_cand_off, int P, float tau,
+                       int64_t* inter, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
