@@ -8,6 +8,9 @@ VotingPipeline's bins with cppf_pair_table_draw, and every later stage consumes 
 
     python -m cppf2_amd.pair_table --mesh obj.ply --mesh-scale 0.001 --out obj.npz
     python -m cppf2_amd.pair_table --bop-models <dataset>/models --out-dir tables      # obj_%06d.npz for every model
+
+--sym-axis 0|1|2 canonicalises a continuous symmetry about that coordinate axis (render.make_items' sym_axis); --sym-axis auto
+takes the axis from the mesh (cppf2_amd.symmetry.detect and coordinate_axis) or exits naming the axis it detected.
 """
 from __future__ import annotations
 
@@ -246,8 +249,14 @@ def main(argv=None):
     ap.add_argument("--views", type=int, default=VIEWS)
     ap.add_argument("--tuples", type=int, default=TUPLES_PER_VIEW)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--sym-axis", type=int, default=None)
+    ap.add_argument("--sym-axis", default=None,
+                    help="0, 1 or 2: the coordinate axis of a continuous symmetry (map_sym); auto: detected (cppf2_amd.symmetry)")
     a = ap.parse_args(argv)
+    if a.sym_axis is not None and a.sym_axis != "auto":
+        try:
+            a.sym_axis = int(a.sym_axis)
+        except ValueError:
+            ap.error("--sym-axis is 0, 1, 2 or auto, not %r" % (a.sym_axis,))
     if bool(a.mesh) == bool(a.bop_models):
         ap.error("give --mesh with --out, or --bop-models with --out-dir")
     if a.mesh:
@@ -264,7 +273,15 @@ def main(argv=None):
         jobs = [(os.path.join(a.bop_models, n), os.path.join(a.out_dir, n[:-4] + ".npz")) for n in names]
     scale = a.mesh_scale if a.mesh_scale is not None else (1.0 if a.mesh else 0.001)
     for path, out in jobs:
-        t = build(render.load_mesh(path, scale), a.views, a.tuples, a.seed, sym_axis=a.sym_axis, name=os.path.basename(path))
+        sym_axis = a.sym_axis
+        if sym_axis == "auto":
+            from . import symmetry
+            try:
+                sym_axis = symmetry.coordinate_axis(symmetry.detect(render.load_mesh(path, scale)))
+            except ValueError as e:
+                raise SystemExit("%s: %s" % (os.path.basename(path), e))
+            print("%s: --sym-axis auto chose coordinate axis %d" % (os.path.basename(path), sym_axis))
+        t = build(render.load_mesh(path, scale), a.views, a.tuples, a.seed, sym_axis=sym_axis, name=os.path.basename(path))
         t.save(out)
         print("%s: %d entries in %d of %d cells, %.1f s -> %s" % (os.path.basename(path), t.E, int((np.diff(t.cell_off) > 0).sum()),
                                                                  t.ncell, t.build_seconds, out))

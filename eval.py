@@ -30,6 +30,11 @@ What the image cannot provide is stated, not faked:
     (a 3x4 or 4x4 model -> OpenCV camera matrix in the record convention, metres) with the BOP metrics VSD, MSSD and MSPD
     (cppf2_amd.bop; --models_info: the object's BOP models_info entry, for its symmetries and diameter): each result gains
     `bop` (and `bop_before_icp` with --icp_iters > 0), the report their average recall.
+  * `--data=depth --mesh=<ply|obj> --detect_symmetries [--sym_tol=0.01]` finds the mesh's rotational symmetries on the GPU
+    (cppf2_amd.symmetry, cppf_sym_deviation) where --models_info would supply them: the object scored by
+    --gt_pose is built from the detected entry, and the report gains `symmetries` (counts, continuous axes, the largest accepted
+    and the smallest refused deviation over the diameter).  --sym_tol: a symmetry deviates by at most that share of the
+    diameter.  Off by default.
   * `--data=depth --mesh=<ply|obj> --hypotheses=H [--verify_tau=0.01]` (H > 1) verifies H pose hypotheses of the instance
     against the depth image (cppf2_amd.verify, cppf_pose_hypotheses + cppf_depth_fit_counts; not in the reference): the
     selected pose first, then the other peak combinations of both votes of the picked pass and of the other enabled pass;
@@ -589,6 +594,23 @@ def main_bop(setup, vote, stages, bop_root, split, out_csv, targets=None, mesh_s
     return _emit(report, debug, out)
 
 
+def _symmetry_flags(f):
+    """The tolerance of --detect_symmetries (a share of the diameter), or None when it is off."""
+    if not f.detect_symmetries:
+        if f.sym_tol is not None:
+            raise ValueError("--sym_tol sets the tolerance of --detect_symmetries: it needs that flag")
+        return None
+    if f.models_info:
+        raise ValueError("--detect_symmetries finds the symmetries --models_info would supply: give one of them")
+    if f.data != "depth" or not f.mesh:
+        raise ValueError("--detect_symmetries finds the symmetries of the one object of --mesh: it needs --data=depth and --mesh")
+    from cppf2_amd import symmetry
+    tol = symmetry.TOL if f.sym_tol is None else float(f.sym_tol)
+    if not (tol > 0.0 and np.isfinite(tol)):
+        raise ValueError("--sym_tol is a share of the diameter > 0, not %r" % (f.sym_tol,))
+    return tol
+
+
 def _centre_peaks_flag(centre_peaks, hypotheses):
     centre_peaks = int(centre_peaks)
     if centre_peaks < 1:
@@ -778,6 +800,7 @@ def _checked_flags(**kw):
         raise ValueError("--icp_iters > 0 refines against the object's mesh: it needs --data=depth and --mesh")
     if not bop_mode and f.gt_pose is not None and not on_mesh:
         raise ValueError("--gt_pose scores the pose against the object's mesh (BOP metrics): it needs --data=depth and --mesh")
+    f.sym_tol = _symmetry_flags(f)
     f.solid = _solid_flags(f)
     from cppf2_amd import verify
     f.stages = Stages(f.icp_iters, f.icp_depth, f.icp_model_weight, f.hypotheses,
@@ -992,7 +1015,7 @@ DepthRun = collections.namedtuple("DepthRun", "d K setups vote stages against de
 
 
 def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, explain=None, cleaning=None, pair_tables=None,
-                     solid=None):
+                     solid=None, symmetries=None):
     """The depth mode over the masks (bool [M,H,W]) of the image of ctx, a DepthRun: per object and category one batch whose
     instances are the masks that give a usable cloud, each with the cloud, scene index and tuple streams a --mask run of its mask
     has; voted, refined and verified as ctx.stages says, then reported (_finish).
@@ -1005,7 +1028,8 @@ def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, ex
     gt: (the object's bop.ObjectInfo, R, t) of --gt_pose or None: every instance of the given mask is scored; of proposals the best
     one when the verification chose one, else every one.  explain: _explain_flags' dict: the verified poses become the candidates
     of _explain_scene.  solid: _solid_flags' dict or None; its `support` entry makes verify.select and the explanation refuse
-    poses that sink into the proposals' plane, its `overlap` entry makes the explanation refuse a pose inside an earlier instance."""
+    poses that sink into the proposals' plane, its `overlap` entry makes the explanation refuse a pose inside an earlier instance.
+    symmetries: symmetry.summary of --detect_symmetries' entry or None: the report's `symmetries`."""
     from cppf2_amd import bop
     dev = ops._dev()
     d, K, vote, stages = ctx.d, ctx.K, ctx.vote, ctx.stages
@@ -1096,28 +1120,35 @@ def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, ex
         report["scene"] = _explain_scene(cands, [ob["obj"] for ob in objects], d, masks.any(0), K, stages.verify_tau, explain, more)
     if solid is not None:
         report["solid_checks"] = solid
+    if symmetries is not None:
+        report["symmetries"] = symmetries
     return _finish(report, acc, categories, ctx.debug, ctx.out, ctx.out_pkl)
 
 
 def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=None, depth_scale=1000.0, mesh=None, mesh_scale=1.0,
                gt_pose=None, models_info=None, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None,
-               propose=None, explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001, solid=None):
+               propose=None, explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001, solid=None,
+               sym_tol=None):
     """One depth + mask PNG pair (example_data layout): one instance, evaluated once per category of `categories`; with `mesh`
     its pose is refined (stages.icp_iters), verified (stages.hypotheses) and scored against gt_pose (BOP errors), see the module
     docstring.  propose: segment.propose's keyword arguments; the proposed masks then stand where the one of `mask` stood, one
     instance each in one batch per category.  explain: _explain_flags' dict (the report's `scene`); models_dir, pair_tables,
     obj_ids, model_scale: the objects of the multi-object form, which stand where mesh and pair_table stood.  solid:
-    _solid_flags' dict (the support and overlap checks of cppf2_amd/solid.py).  This reads the inputs; _depth_instances runs them."""
+    _solid_flags' dict (the support and overlap checks of cppf2_amd/solid.py).  sym_tol: --detect_symmetries' tolerance or None;
+    the detected entry then stands where the one of models_info stood.  This reads the inputs; _depth_instances runs them."""
     from PIL import Image
     from cppf2_amd import bop, icp, masks, render, segment
-    gt = None
+    gt = symmetries = None
     if models_dir:
         objects, against = _scene_objects(models_dir, pair_tables, obj_ids, model_scale, stages), "each object's model"
     else:
         icp_model = icp.ModelPoints.from_mesh(render.load_mesh(mesh, mesh_scale)) if stages.icp_iters > 0 else None
-        obj = None
+        obj = info = None
+        if sym_tol is not None:
+            from cppf2_amd import symmetry
+            info = symmetry.detect(render.load_mesh(mesh, mesh_scale), tol=sym_tol)
+            symmetries = symmetry.summary(info)
         if gt_pose is not None:
-            info = None
             if models_info:
                 with open(models_info) as f:
                     info = json.load(f)
@@ -1132,7 +1163,7 @@ def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=No
     if propose is not None:
         pm, props, plane = segment.propose(d.astype(np.float32), K, vote.seed, **propose)
         return _depth_instances(ctx, pm.cpu().numpy() > 0, objects, categories, (props, plane, propose), gt, explain,
-                                pair_tables=pair_tables, solid=solid)
+                                pair_tables=pair_tables, solid=solid, symmetries=symmetries)
     m = np.array(Image.open(mask))
     m = (m[..., 0] if m.ndim == 3 else m) > 0
     cleaning = None
@@ -1144,7 +1175,7 @@ def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=No
         cleaning = dict(components=stats[0], kept_pixels=stats[2], valid_pixels=stats[3])
         if not m.any():
             raise ValueError("--clean_mask: no depth-connected component of the mask has %d pixels" % masks.MIN_PIXELS)
-    return _depth_instances(ctx, m[None], objects, categories, gt=gt, cleaning=cleaning)
+    return _depth_instances(ctx, m[None], objects, categories, gt=gt, cleaning=cleaning, symmetries=symmetries)
 
 
 def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, num_rots=180, opt=True, debug=False,
@@ -1158,7 +1189,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          propose_masks=False, plane_tau=None, plane_hypotheses=None, plane_min_height=None, min_segment_pixels=None,
          max_proposals=None, explain_scene=False, explain_min_score=None, explain_min_gain=None, explain_viol_weight=None,
          explain_max=None, models_dir=None, obj_ids=None, explain_hypotheses=False, explain_min_support=None,
-         support_check=False, support_tau=None, support_max_share=None, explain_solid=False, solid_tau=None, solid_max_share=None):
+         support_check=False, support_tau=None, support_max_share=None, explain_solid=False, solid_tau=None, solid_max_share=None,
+         detect_symmetries=False, sym_tol=None):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()
@@ -1195,7 +1227,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                           mesh_scale=mesh_scale, gt_pose=gt_pose, models_info=models_info, clean_mask=f.clean_masks,
                           mask_jump=mask_jump, pair_table=pair_table, debug=debug, out=out, out_pkl=out_pkl, propose=f.propose,
                           explain=f.explain, models_dir=models_dir, pair_tables=pair_tables, obj_ids=f.obj_ids,
-                          model_scale=float(model_scale), solid=f.solid)
+                          model_scale=float(model_scale), solid=f.solid, sym_tol=f.sym_tol)
     return main_synthetic(setups, categories, vote, num_scenes=num_scenes, num_points=num_points, debug=debug, out=out,
                           out_pkl=out_pkl)
 

@@ -9,7 +9,8 @@
  *     logits).  It exists because the reference's checkpoints are not available: random-init weights need a teacher for votes to
  *     cluster.  bench.py reports value_no_prior beside the headline;
  *   - a test hook;
- *   - the solid-interval checks on candidate poses (cppf2_amd/solid.py): opt-in and new.
+ *   - the solid-interval checks on candidate poses (cppf2_amd/solid.py): opt-in and new;
+ *   - the deviation statistic of the symmetry detection (cppf2_amd/symmetry.py): opt-in and new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -171,6 +172,20 @@ int cppf_support_counts(int I, int H, int W, const float* front, const float* ba
 int64_t cppf_solid_overlap_workspace_bytes(int I, int H, int W);
 int cppf_solid_overlap(int I, int H, int W, const float* front, const float* back, const int32_t* h_cand_off, int P, float tau,
                        int64_t* inter, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- a mesh's symmetries: deviation of a sampled surface from the mesh under candidate maps (the reference has no such step) ----
+ * cppf_sym_deviation: queries float32[nq,3] (points of the surface), tris float32[nf,9] (three vertices per row; triangles
+ * without area contribute nothing), maps float64[nc,12] (row-major 3x4 maps x -> R x + t, cppf_mssd_mspd's syms layout), all in
+ * one frame.  Out, float32[nc]: max_d2[c] = max over the queries of min over the triangles of the SQUARED distance between the
+ * mapped query and the triangle (the closest point by the vertex / edge / face regions): the one-sided Hausdorff deviation of
+ * the mapped samples from the mesh, squared.  Each map is rounded to float32 once, everything after it is float32; a NaN
+ * distance is ignored, so a non-finite query (every map) or a non-finite map (that map) gives +inf.  nq >= 1, nf >= 1,
+ * 0 <= nc <= 65535; nc = 0 launches nothing.  No workspace; one launch after the output is cleared on the stream.  An integer
+ * atomic maximum only: the output does not depend on the batch or the order.  The exact order of the operations is stated in
+ * cppf2_amd/csrc/cppf_symmetry.hip.  Experimental while the detection is opt-in and young: the stable
+ * interface keeps its 74 entry points. */
+int cppf_sym_deviation(const float* queries, int nq, const float* tris, int nf, const double* maps, int nc, float* max_d2,
+                       void* stream);
 
 #ifdef __cplusplus
 }
