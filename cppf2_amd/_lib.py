@@ -157,6 +157,7 @@ EXPERIMENTAL = {
     "cppf_solid_overlap_workspace_bytes": (_i64, [_i, _i, _i]),
     "cppf_solid_overlap": (_i, [_i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _i64, _p]),
     "cppf_sym_deviation": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
+    "cppf_box_iou": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
 }
 
 SIGNATURES = dict(STABLE, **EXPERIMENTAL)

@@ -277,47 +277,101 @@ def match_by_iou(overlaps, pred_class_ids, gt_class_ids, iou_thresholds):
     return gt_m, pred_m
 
 
+def _scorer_arrays(res):
+    """One record as compute_degree_cm_mAP reads it (utils/util.py:2610-2640): (gt_cls, gt_RTs, gt_scales, gt_vis, pr_cls, pr_RTs,
+    pr_scales, pr_sc) with the isotropic scale moved from the rotations into the scales."""
+    gt_cls = np.asarray(res["gt_class_ids"]).astype(np.int32)
+    gt_RTs = np.array(res["gt_RTs"], dtype=np.float64).reshape(-1, 4, 4)
+    gt_scales = np.array(res["gt_scales"], dtype=np.float64).reshape(-1, 3)
+    gt_vis = np.asarray(res["gt_handle_visibility"])
+    gnorm = np.array([np.cbrt(np.linalg.det(RT[:3, :3])) for RT in gt_RTs]).reshape(-1)          # util.py:2619-2621
+    gt_RTs[:, :3, :3] = gt_RTs[:, :3, :3] / (gnorm[:, None, None] + 1e-7)
+    gt_scales = gt_scales * gnorm[:, None]
+    pr_cls = np.asarray(res["pred_class_ids"])
+    pr_RTs = np.array(res["pred_RTs"], dtype=np.float64).reshape(-1, 4, 4)
+    pr_scales = np.array(res["pred_scales"], dtype=np.float64).reshape(-1, 3)
+    pr_sc = np.asarray(res["pred_scores"], dtype=np.float64)
+    if len(pr_RTs):
+        pnorm = np.array([np.cbrt(np.linalg.det(RT[:3, :3])) for RT in pr_RTs])                  # util.py:2632-2634
+        pr_RTs[:, :3, :3] = pr_RTs[:, :3, :3] / (pnorm[:, None, None] + 1e-7)
+        pr_scales = pr_scales * pnorm[:, None]
+    return gt_cls, gt_RTs, gt_scales, gt_vis, pr_cls, pr_RTs, pr_scales, pr_sc
+
+
+def _class_arrays(arrays, c, synset_names):
+    """Class c's share of _scorer_arrays' record, the predictions by descending score (utils/util.py:1688): (c_gt_cls, c_gt_RTs,
+    c_gt_scales, c_vis, c_scores, c_RTs, c_pscales)."""
+    gt_cls, gt_RTs, gt_scales, gt_vis, pr_cls, pr_RTs, pr_scales, pr_sc = arrays
+    g, p = gt_cls == c, pr_cls == c
+    c_vis = gt_vis[g] if synset_names[c] == "mug" else np.ones(int(g.sum()))
+    by_score = np.argsort(pr_sc[p])[::-1]                                                         # util.py:1688
+    return gt_cls[g], gt_RTs[g], gt_scales[g], c_vis, pr_sc[p][by_score], pr_RTs[p][by_score], pr_scales[p][by_score]
+
+
+def _device_overlaps(prepared, synset_names):
+    """{(record index, class): float32 [num_pred, num_gt]}: the IoU of every same-class (prediction, ground truth) pair of the
+    list (prepared: _scorer_arrays of every record), all of them scored by one batched box_iou.iou_3d_batch call and rounded to
+    float32 as utils/util.py:1713 stores them."""
+    from . import box_iou
+    where, RT_1, RT_2, sc_1, sc_2, sym = [], [], [], [], [], []
+    for r, arrays in enumerate(prepared):
+        if len(arrays[0]) == 0 and len(arrays[4]) == 0:
+            continue
+        for c in range(1, len(synset_names)):
+            _, c_gt_RTs, c_gt_scales, c_vis, _, c_RTs, c_pscales = _class_arrays(arrays, c, synset_names)
+            n, m = len(c_RTs), len(c_gt_RTs)
+            where.append((r, c, n, m))
+            if n * m == 0:
+                continue
+            RT_1.append(np.repeat(c_RTs, m, axis=0))
+            sc_1.append(np.repeat(c_pscales, m, axis=0))
+            RT_2.append(np.tile(c_gt_RTs, (n, 1, 1)))
+            sc_2.append(np.tile(c_gt_scales, (n, 1)))
+            name = synset_names[c]
+            sym.append(np.tile((name in _AXIS_SYMMETRIC) | ((name == "mug") & (np.asarray(c_vis) == 0)), n))
+    flat = np.zeros(0)
+    if RT_1:
+        flat = box_iou.iou_3d_batch(np.concatenate(RT_1), np.concatenate(RT_2), np.concatenate(sc_1), np.concatenate(sc_2),
+                                    np.concatenate(sym)).cpu().numpy()
+    out, at = {}, 0
+    for r, c, n, m in where:
+        out[(r, c)] = flat[at:at + n * m].reshape(n, m).astype(np.float32)
+        at += n * m
+    return out
+
+
 def degree_cm_mAP(final_results, synset_names=SYNSET_NAMES, degree_thresholds=(5, 10, 15), shift_thresholds=(5, 10, 15),
-                  iou_3d_thresholds=tuple(np.linspace(0, 1, 101)), iou_pose_thres=0.1, use_matches_for_pose=False):
+                  iou_3d_thresholds=tuple(np.linspace(0, 1, 101)), iou_pose_thres=0.1, use_matches_for_pose=False, iou="host"):
     """compute_degree_cm_mAP (utils/util.py:2736-2955) without the plots: returns (iou_3d_aps [num_classes + 1, len(iou
     thresholds)], pose_aps [num_classes + 1, len(deg) + 1, len(shift) + 1]).  With use_matches_for_pose (what eval.py:
-    400-411 passes) the pose AP is taken over the predictions / ground truths matched at 3-D IoU > iou_pose_thres."""
+    400-411 passes) the pose AP is taken over the predictions / ground truths matched at 3-D IoU > iou_pose_thres.
+    iou: "host" computes the box overlaps pair by pair with iou_3d (a convex hull each); "device" collects the same-class pairs
+    of the whole list and scores them in one cppf_box_iou call (cppf2_amd/box_iou.py) -- the matching,
+    the degree / cm overlaps and the AP run on the host either way."""
+    if iou not in ("host", "device"):
+        raise ValueError("degree_cm_mAP: iou is 'host' or 'device', not %r" % (iou,))
     degs, shifts = list(degree_thresholds) + [360], list(shift_thresholds) + [100]
     iou_thr = list(iou_3d_thresholds)
     if use_matches_for_pose:
         assert iou_pose_thres in iou_thr
     ncls = len(synset_names)
+    prepared = [_scorer_arrays(res) for res in final_results]
+    device_ov = _device_overlaps(prepared, synset_names) if iou == "device" else None
     acc = {k: [[] for _ in range(ncls)] for k in ("ipm", "ips", "igm", "ppm", "pps", "pgm")}
-    for res in final_results:
-        gt_cls = np.asarray(res["gt_class_ids"]).astype(np.int32)
-        gt_RTs = np.array(res["gt_RTs"], dtype=np.float64).reshape(-1, 4, 4)
-        gt_scales = np.array(res["gt_scales"], dtype=np.float64).reshape(-1, 3)
-        gt_vis = np.asarray(res["gt_handle_visibility"])
-        gnorm = np.array([np.cbrt(np.linalg.det(RT[:3, :3])) for RT in gt_RTs]).reshape(-1)          # util.py:2619-2621
-        gt_RTs[:, :3, :3] = gt_RTs[:, :3, :3] / (gnorm[:, None, None] + 1e-7)
-        gt_scales = gt_scales * gnorm[:, None]
-        pr_cls = np.asarray(res["pred_class_ids"])
-        pr_RTs = np.array(res["pred_RTs"], dtype=np.float64).reshape(-1, 4, 4)
-        pr_scales = np.array(res["pred_scales"], dtype=np.float64).reshape(-1, 3)
-        pr_sc = np.asarray(res["pred_scores"], dtype=np.float64)
-        if len(pr_RTs):
-            pnorm = np.array([np.cbrt(np.linalg.det(RT[:3, :3])) for RT in pr_RTs])                  # util.py:2632-2634
-            pr_RTs[:, :3, :3] = pr_RTs[:, :3, :3] / (pnorm[:, None, None] + 1e-7)
-            pr_scales = pr_scales * pnorm[:, None]
-        if len(gt_cls) == 0 and len(pr_cls) == 0:
+    for r, arrays in enumerate(prepared):
+        if len(arrays[0]) == 0 and len(arrays[4]) == 0:
             continue
         for c in range(1, ncls):
-            g, p = gt_cls == c, pr_cls == c
-            c_gt_cls, c_gt_RTs, c_gt_scales = gt_cls[g], gt_RTs[g], gt_scales[g]
-            c_vis = gt_vis[g] if synset_names[c] == "mug" else np.ones(int(g.sum()))
-            by_score = np.argsort(pr_sc[p])[::-1]                                                     # util.py:1688
-            c_scores, c_RTs, c_pscales = pr_sc[p][by_score], pr_RTs[p][by_score], pr_scales[p][by_score]
+            c_gt_cls, c_gt_RTs, c_gt_scales, c_vis, c_scores, c_RTs, c_pscales = _class_arrays(arrays, c, synset_names)
             c_pcls = np.full(len(c_RTs), c)
-            ov = np.zeros((len(c_RTs), len(c_gt_cls)), dtype=np.float32)                             # util.py:1713
-            for i in range(len(c_RTs)):
-                for j in range(len(c_gt_cls)):
-                    ov[i, j] = iou_3d(c_RTs[i], c_gt_RTs[j], c_pscales[i], c_gt_scales[j], c_vis[j], synset_names[c],
-                                      synset_names[c])
+            if device_ov is not None:
+                ov = device_ov[(r, c)]
+            else:
+                ov = np.zeros((len(c_RTs), len(c_gt_cls)), dtype=np.float32)                         # util.py:1713
+                for i in range(len(c_RTs)):
+                    for j in range(len(c_gt_cls)):
+                        ov[i, j] = iou_3d(c_RTs[i], c_gt_RTs[j], c_pscales[i], c_gt_scales[j], c_vis[j], synset_names[c],
+                                          synset_names[c])
             ig, ip = match_by_iou(ov, c_pcls, c_gt_cls, iou_thr)
             acc["ipm"][c].append(ip)
             acc["ips"][c].append(np.tile(c_scores, (len(iou_thr), 1)))
@@ -348,3 +402,78 @@ def degree_cm_mAP(final_results, synset_names=SYNSET_NAMES, degree_thresholds=(5
     iou_aps[-1] = np.mean(iou_aps[1:-1], axis=0)
     pose_aps[-1] = np.mean(pose_aps[1:-1], axis=0)
     return iou_aps, pose_aps
+
+
+# ----------------------------------------------------------------------------------------------
+# re-scoring saved records:  python -m cppf2_amd.metrics --results <dir> [--iou host|device] [--categories a,b] [--out report.json]
+# ----------------------------------------------------------------------------------------------
+def load_records(results_dir):
+    """The per-image records eval.py --out_dir (and the reference, eval.py:134, 399) pickles into a directory, by file name."""
+    import glob
+    import os
+    import pickle
+    paths = sorted(glob.glob(os.path.join(results_dir, "*.pkl")))
+    if not paths:
+        raise ValueError("no *.pkl records in %s" % results_dir)
+    out = []
+    for p in paths:
+        with open(p, "rb") as f:
+            out.append(pickle.load(f))
+    return out
+
+
+def nocs_summary(iou_aps, aps, class_ids):
+    """main_nocs' report entries from degree_cm_mAP's two arrays: the mean over the given classes (finite values only, None
+    when there is none) of the pose AP at (5, 10, 15) deg x (5, 10, 15) cm and of the IoU AP at 0.25, 0.50, 0.75 (thresholds
+    linspace(0, 1, 101))."""
+    def mean_over(fn):
+        v = [fn(c) for c in class_ids]
+        v = [x for x in v if np.isfinite(x)]
+        return float(np.mean(v)) if v else None
+    return dict(pose_AP={"%ddeg_%dcm" % (d_, s_): mean_over(lambda c, i_=i_, j_=j_: aps[c, i_, j_])
+                         for i_, d_ in enumerate((5, 10, 15)) for j_, s_ in enumerate((5, 10, 15))},
+                iou_AP={"IoU%d" % t_: mean_over(lambda c, t_=t_: iou_aps[c, t_]) for t_ in (25, 50, 75)})
+
+
+def rescore(results_dir, iou="host", categories=None):
+    """Scores a directory of saved per-image records as eval.py's main_nocs scores its list (degree_cm_mAP with the matched
+    pose AP, eval.py:400-411), without running the vote again.  The summary is the mean over `categories` (names of
+    SYNSET_NAMES; main_nocs takes the categories it evaluated), by default over the classes that occur in the records."""
+    import time
+    records = load_records(results_dir)
+    t0 = time.perf_counter()
+    iou_aps, aps = degree_cm_mAP(records, SYNSET_NAMES, (5, 10, 15), (5, 10, 15), np.linspace(0, 1, 101), 0.1, True, iou=iou)
+    seconds = time.perf_counter() - t0
+    if categories is None:
+        ids = sorted({int(c) for r in records for k in ("gt_class_ids", "pred_class_ids") for c in np.asarray(r[k]).reshape(-1)
+                      if 0 < int(c) < len(SYNSET_NAMES)})
+    else:
+        unknown = [c for c in categories if c not in SYNSET_NAMES[1:]]
+        if unknown:
+            raise ValueError("rescore: categories are among %s, not %s" % (SYNSET_NAMES[1:], unknown))
+        ids = [SYNSET_NAMES.index(c) for c in categories]
+    report = dict(data="nocs", images=len(records), iou=iou, scorer_seconds=seconds, categories=[SYNSET_NAMES[c] for c in ids])
+    report.update(nocs_summary(iou_aps, aps, ids))
+    return report
+
+
+def _main(argv=None):
+    import argparse
+    import json
+    ap = argparse.ArgumentParser(prog="python -m cppf2_amd.metrics", description="re-score saved NOCS result records")
+    ap.add_argument("--results", required=True, help="directory of the per-image *.pkl records eval.py --out_dir writes")
+    ap.add_argument("--iou", choices=("host", "device"), default="host")
+    ap.add_argument("--categories", default=None, help="comma-separated class names the summary averages over "
+                    "(default: the classes that occur in the records)")
+    ap.add_argument("--out", default=None, help="also write the report to this JSON file")
+    a = ap.parse_args(argv)
+    report = rescore(a.results, a.iou, [c for c in a.categories.split(",") if c] if a.categories else None)
+    print(json.dumps(report))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(report, f)
+    return report
+
+
+if __name__ == "__main__":
+    _main()

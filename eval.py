@@ -35,6 +35,10 @@ What the image cannot provide is stated, not faked:
     --gt_pose is built from the detected entry, and the report gains `symmetries` (counts, continuous axes, the largest accepted
     and the smallest refused deviation over the diameter).  --sym_tol: a symmetry deviates by at most that share of the
     diameter.  Off by default.
+  * `--data=nocs --iou_device` scores the 3-D box overlaps of the NOCS scorer on the GPU (cppf2_amd.box_iou, cppf_box_iou, DESIGN.md
+    section 27): metrics.degree_cm_mAP(iou="device"), every same-class (prediction, ground truth) pair of the run in one batched
+    call instead of one convex hull per pair and turn on the host; the report gains `scorer_seconds`.  Off by default.
+    `python -m cppf2_amd.metrics --results <out_dir> [--iou host|device]` scores the records --out_dir saved without voting again.
   * `--data=depth --mesh=<ply|obj> --hypotheses=H [--verify_tau=0.01]` (H > 1) verifies H pose hypotheses of the instance
     against the depth image (cppf2_amd.verify, cppf_pose_hypotheses + cppf_depth_fit_counts; not in the reference): the
     selected pose first, then the other peak combinations of both votes of the picked pass and of the other enabled pass;
@@ -108,6 +112,7 @@ import collections
 import json
 import os
 import sys
+import time
 import types
 
 import numpy as np
@@ -308,12 +313,13 @@ def _emit(report, debug, out):
 
 
 def main_nocs(setups, vote, log_dir, data_root="NOCS/real_test", out_dir=None, desc_npz=None, batch_instances=16, intrinsics=None,
-              max_images=None, debug=False, out=None):
+              max_images=None, debug=False, out=None, iou_device=False):
     """eval.py:103-412 on a directory in the reference's layout: `log_dir`/results_*.pkl (detections + ground truth per image)
     and `data_root`/<scene>/<frame>_{depth,color}.png.  Instances are collected image by image exactly as the reference
     filters them, evaluated in batches per category on the GPU (run_ensemble), and written back into their image's record
     (pred_RTs, pred_scales: eval.py:143-147, 370-372); every record is pickled under out_dir with the reference's file name
-    (eval.py:134, 399) and the list is scored with degree_cm_mAP (eval.py:400-412).
+    (eval.py:134, 399) and the list is scored with degree_cm_mAP (eval.py:400-412); iou_device: with its box overlaps from the
+    GPU (degree_cm_mAP(iou="device")), and the report gains `scorer_seconds`.
     desc_npz: optional .npz of DINOv2 patch-token maps float32 [1024, 64, 64] keyed "<image index>_<instance index>" (the
     crop of eval.py:177-183 at stride 4); without it seeded unit vectors stand in (the DINO branch then votes on noise)."""
     import pickle
@@ -380,19 +386,17 @@ def main_nocs(setups, vote, log_dir, data_root="NOCS/real_test", out_dir=None, d
             with open(os.path.join(out_dir, "_".join(image_path.split("/")[1:]) + ".pkl"), "wb") as f:     # eval.py:134,399
                 pickle.dump(res, f)
     total = sum(len(r_["pred_bboxes"]) for r_ in final_results)
+    t_scorer = time.perf_counter()
     iou_aps, aps = metrics.degree_cm_mAP(final_results, metrics.SYNSET_NAMES, (5, 10, 15), (5, 10, 15),
-                                         np.linspace(0, 1, 101), 0.1, True)                # eval.py:400-411
+                                         np.linspace(0, 1, 101), 0.1, True,                # eval.py:400-411
+                                         iou="device" if iou_device else "host")
+    t_scorer = time.perf_counter() - t_scorer
     cats = [c for c in setups if seen[c]]
-
-    def mean_over(fn):
-        v = [fn(category2id[c]) for c in cats]
-        v = [x for x in v if np.isfinite(x)]
-        return float(np.mean(v)) if v else None
     report = dict(data="nocs", images=len(final_results), detections=total, evaluated=evaluated, skipped=total - evaluated,
                   picked=picks, categories=cats, descriptors="token maps from %s" % desc_npz if desc_npz else "seeded unit vectors (no DINOv2 tokens given)",
-                  pose_AP={"%ddeg_%dcm" % (d_, s_): mean_over(lambda c, i_=i_, j_=j_: aps[c, i_, j_])
-                           for i_, d_ in enumerate((5, 10, 15)) for j_, s_ in enumerate((5, 10, 15))},
-                  iou_AP={"IoU%d" % t_: mean_over(lambda c, t_=t_: iou_aps[c, t_]) for t_ in (25, 50, 75)})
+                  **metrics.nocs_summary(iou_aps, aps, [category2id[c] for c in cats]))
+    if iou_device:
+        report["scorer_seconds"] = t_scorer
     _emit(report, debug, out)                       # (it has no `results`: the whole report either way)
     report["final_results"] = final_results
     return report
@@ -801,6 +805,8 @@ def _checked_flags(**kw):
     if not bop_mode and f.gt_pose is not None and not on_mesh:
         raise ValueError("--gt_pose scores the pose against the object's mesh (BOP metrics): it needs --data=depth and --mesh")
     f.sym_tol = _symmetry_flags(f)
+    if f.iou_device and f.data != "nocs":
+        raise ValueError("--iou_device scores the NOCS scorer's box overlaps on the GPU: it needs --data=nocs")
     f.solid = _solid_flags(f)
     from cppf2_amd import verify
     f.stages = Stages(f.icp_iters, f.icp_depth, f.icp_model_weight, f.hypotheses,
@@ -1190,7 +1196,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          max_proposals=None, explain_scene=False, explain_min_score=None, explain_min_gain=None, explain_viol_weight=None,
          explain_max=None, models_dir=None, obj_ids=None, explain_hypotheses=False, explain_min_support=None,
          support_check=False, support_tau=None, support_max_share=None, explain_solid=False, solid_tau=None, solid_max_share=None,
-         detect_symmetries=False, sym_tol=None):
+         detect_symmetries=False, sym_tol=None, iou_device=False):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()
@@ -1221,7 +1227,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
     if data == "nocs":
         assert log_dir, "--data=nocs needs --log_dir (the directory of results_*.pkl, eval.py:72-76)"
         return main_nocs(setups, vote, log_dir, data_root=data_root, out_dir=out_dir, desc_npz=desc_npz,
-                         batch_instances=batch_instances, intrinsics=intrinsics, max_images=max_images, debug=debug, out=out)
+                         batch_instances=batch_instances, intrinsics=intrinsics, max_images=max_images, debug=debug, out=out,
+                         iou_device=bool(iou_device))
     if data == "depth":
         return main_depth(setups, categories, vote, f.stages, depth, mask, intrinsics=intrinsics, depth_scale=depth_scale, mesh=mesh,
                           mesh_scale=mesh_scale, gt_pose=gt_pose, models_info=models_info, clean_mask=f.clean_masks,

@@ -10,7 +10,8 @@
  *     cluster.  bench.py reports value_no_prior beside the headline;
  *   - a test hook;
  *   - the solid-interval checks on candidate poses (cppf2_amd/solid.py): opt-in and new;
- *   - the deviation statistic of the symmetry detection (cppf2_amd/symmetry.py): opt-in and new.
+ *   - the deviation statistic of the symmetry detection (cppf2_amd/symmetry.py): opt-in and new;
+ *   - the oriented-box IoU of the NOCS scorer (cppf2_amd/box_iou.py): opt-in and new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -186,6 +187,27 @@ int cppf_solid_overlap(int I, int H, int W, const float* front, const float* bac
  * interface keeps its 74 entry points. */
 int cppf_sym_deviation(const float* queries, int nq, const float* tris, int nf, const double* maps, int nc, float* max_d2,
                        void* stream);
+
+/* ---- 3-D IoU of oriented boxes, batched (the reference computes it on the host: utils/util.py:475-547, utils/iou.py) ----
+ * cppf_box_iou: P box pairs, everything float64 on the device.  Box 1 = R1[P,9] (row-major, orthonormal: an isotropic scale is
+ * divided out by the caller), t1[P,3] (centre), s1[P,3] (full edge lengths); box 2 = R2, t2, s2 alike.  turns int32[P]:
+ * iou[p] = max over i < turns[p] of the IoU of box 1 turned by 2 pi i / turns[p] about its own y axis (R1 . Ry) with box 2;
+ * turns = 1 is the plain IoU, 36 the toolkit's rule for the classes that are symmetric about y.  turn_cs float64
+ * [max_turns (max_turns + 1) / 2, 2]: (cos, sin)(2 pi i / n) at row n (n - 1) / 2 + i for every n = 1 .. max_turns, i < n,
+ * filled by the host, so that the device's sincos plays no part in the result.  0 <= P <= 2^20 (1 048 576; callers chunk),
+ * 1 <= max_turns <= 64; P = 0 launches nothing.  A pair whose turns is outside 1 .. max_turns gets NaN.
+ * The volume of the intersection is summed over its (at most twelve) faces, each a box face clipped by the other box's six
+ * closed half-spaces.  Where a plane of box 2 nearly coincides with a face of box 1 (normals within 1e-5 of parallel, the plane
+ * within 1e-5 (|s1| + |s2| + |t1 - t2|) of the face's centre) that face's lane scores both faces, so that one decision says which
+ * plane bounds the intersection where; what this neglects is of second order, about 1e-10 relative, and planes tilted by more
+ * are met by plain clipping, whose error there is of the same size.  Checked to 1e-9: exact ties (identical boxes 1, boxes
+ * sharing faces their ratio, boxes touching in a face exactly 0.0), the same pairs turned and shifted by 1e-15 .. 1e-4, generic
+ * pairs.  Boxes thinner than 1e-5 of the pair's size are outside what was checked.  No workspace; one launch after the output is cleared on the stream.  A 64-bit integer atomic maximum
+ * only: the output does not depend on the batch or the order.  The exact order of the operations is stated in
+ * cppf2_amd/csrc/cppf_box_iou.hip.  Experimental while the device scorer is opt-in and young: the stable
+ * interface keeps its 74 entry points. */
+int cppf_box_iou(const double* R1, const double* t1, const double* s1, const double* R2, const double* t2, const double* s2,
+                 const int32_t* turns, const double* turn_cs, int max_turns, int P, double* iou, void* stream);
 
 #ifdef __cplusplus
 }
