@@ -158,6 +158,9 @@ EXPERIMENTAL = {
     "cppf_solid_overlap": (_i, [_i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _i64, _p]),
     "cppf_sym_deviation": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
     "cppf_box_iou": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
+    "cppf_tsdf_integrate": (_i, [_i, _p, _p, _p, _i, _i, _p, _f, _p, _f, _i, _i, _i, _f, _f, _p, _p, _p]),
+    "cppf_tsdf_extract_workspace_bytes": (_i64, [_i, _i, _i]),
+    "cppf_tsdf_extract": (_i, [_p, _p, _p, _f, _i, _i, _i, _i, _i64, _p, _p, _p, _p, _i64, _p]),
 }
 
 SIGNATURES = dict(STABLE, **EXPERIMENTAL)

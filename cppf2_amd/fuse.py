@@ -1,0 +1,359 @@
+"""A mesh of an object without a CAD model, from posed depth views: the views (a turntable or hand-held
+sequence with camera poses and masks, what BOP's model-free onboarding sequences provide) are fused into a truncated signed
+distance volume, and the volume's zero surface is extracted by marching tetrahedra.  The reference has no such step: its
+custom-object path starts from a mesh (train_custom.ipynb).
+
+    vol = Volume.around(depths, masks, poses, K, voxel=0.002)
+    integrate(vol, depths, poses, K, masks=masks)                   # any number of calls; images of one size and K per call
+    mesh = extract(vol)                                             # render.Mesh, vertices welded; mesh.boundary_edges
+    mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002)
+    python -m cppf2_amd.fuse --views <bop scene dir> --obj-id 15 --voxel 0.002 --out obj_000015.ply
+
+The kernels are cppf_tsdf_integrate and cppf_tsdf_extract (include/cppf_hip_experimental.h; the definitions are stated in
+cppf2_amd/csrc/cppf_fuse.hip and restated in tests/fuse_ref.py).  Not done: no weighting by viewing angle or distance, no
+colour, no hole filling (what no view saw stays open: mesh.boundary_edges counts it), no pose optimisation (the poses are trusted).
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+from . import _lib, hostargs, ops, render
+from ._lib import CppfError
+
+TRUNC_VOXELS = 3.0               # the default truncation distance, in voxels
+MAX_NODES = 1 << 27              # the entry points' limit on nx * ny * nz
+MAX_VIEWS = 65536                # views per cppf_tsdf_integrate call
+MAX_IMAGE = 16384                # H and W
+INITIAL_CAPACITY = 1 << 16       # triangles of the first cppf_tsdf_extract call
+
+_WS = hostargs.ScratchCache("cppf_tsdf_extract_workspace_bytes", CppfError)
+
+
+def _host3(x):
+    return (C.c_double * 3)(*[float(v) for v in np.asarray(x, dtype=np.float64).reshape(3)])
+
+
+class Volume:
+    """The two device arrays of a signed distance volume: acc float32 [nx,ny,nz] (sum of the observations) and wsum int32
+    [nx,ny,nz] (their number), z fastest; node (i,j,k) sits at origin + (i,j,k) * voxel in the object's frame, metres.  The sum
+    and the count are kept, not the average, so that integrating views in one call or in several gives the same bytes.
+    origin and voxel are rounded to float32 (what the kernels use); trunc defaults to 3 voxels; views counts what was integrated."""
+
+    def __init__(self, origin, voxel, dims, trunc=None, dev=None):
+        self.origin = np.asarray(origin, dtype=np.float32).astype(np.float64).reshape(3)
+        self.voxel = float(np.float32(voxel))
+        self.dims = tuple(int(d) for d in dims)
+        self.trunc = float(np.float32(TRUNC_VOXELS * self.voxel if trunc is None else trunc))
+        if len(self.dims) != 3 or min(self.dims) < 1:
+            raise ValueError("Volume: dims are three positive node counts, not %s" % (dims,))
+        if self.dims[0] * self.dims[1] * self.dims[2] > MAX_NODES:
+            raise ValueError("Volume: %d x %d x %d nodes exceed the limit of %d" % (self.dims + (MAX_NODES,)))
+        if not (np.isfinite(self.origin).all() and 0 < self.voxel < np.inf and 0 < self.trunc < np.inf):
+            raise ValueError("Volume: origin is finite, voxel and trunc are positive and finite")
+        dev = ops._dev() if dev is None else torch.device(dev)
+        self.acc = torch.zeros(self.dims, dtype=torch.float32, device=dev)
+        self.wsum = torch.zeros(self.dims, dtype=torch.int32, device=dev)
+        self.views = 0
+
+    @property
+    def device(self):
+        return self.acc.device
+
+    @staticmethod
+    def bounds(depths, masks, poses, K, pixel_offset=0.0, dev=None):
+        """float64 [2,3]: the box, in the object's frame, of the masked pixels with a reading (every pixel with one when masks is
+        None) back-projected through the ray of (c + pixel_offset, r + pixel_offset).  torch ops; not hot."""
+        dev = ops._dev() if dev is None else torch.device(dev)
+        d = hostargs.image_batch(depths, dev, "Volume.around")
+        V, H, W = d.shape
+        m = torch.ones_like(d, dtype=torch.bool) if masks is None else \
+            hostargs.mask_batch(masks, d, dev, "Volume.around", same_shape=True) != 0
+        P = hostargs.tensor(poses, torch.float64, dev).reshape(-1, 3, 4)
+        if P.shape[0] != V:
+            raise ValueError("Volume.around: %d poses for %d views" % (P.shape[0], V))
+        fx, fy, cx, cy = hostargs.camera4(K)
+        cols = torch.arange(W, dtype=torch.float64, device=dev) + float(pixel_offset)
+        rows = torch.arange(H, dtype=torch.float64, device=dev) + float(pixel_offset)
+        lo = torch.full((3,), float("inf"), dtype=torch.float64, device=dev)
+        hi = -lo
+        for v in range(V):
+            z = d[v].to(torch.float64)
+            ok = m[v] & (z > 0) & torch.isfinite(z)
+            if not bool(ok.any()):
+                continue
+            r, c = torch.nonzero(ok, as_tuple=True)
+            z = z[r, c]
+            cam = torch.stack([(cols[c] - cx) * z / fx, (rows[r] - cy) * z / fy, z], 1)
+            obj = (cam - P[v, :, 3]) @ P[v, :, :3]                    # R^T (x - t), written for row vectors
+            lo, hi = torch.minimum(lo, obj.amin(0)), torch.maximum(hi, obj.amax(0))
+        if not bool(torch.isfinite(lo).all()):
+            raise ValueError("Volume.around: no masked pixel has a depth reading")
+        return torch.stack([lo, hi]).cpu().numpy()
+
+    @classmethod
+    def around(cls, depths, masks, poses, K, voxel, margin=None, trunc=None, pixel_offset=0.0, dev=None):
+        """The Volume of node spacing `voxel` around Volume.bounds(...), padded by `margin` (default trunc + voxel) on every side."""
+        voxel = float(np.float32(voxel))
+        trunc = float(np.float32(TRUNC_VOXELS * voxel if trunc is None else trunc))
+        margin = trunc + voxel if margin is None else float(margin)
+        b = cls.bounds(depths, masks, poses, K, pixel_offset, dev)
+        lo, hi = b[0] - margin, b[1] + margin
+        dims = np.ceil((hi - lo) / voxel).astype(np.int64) + 1
+        return cls(lo, voxel, dims, trunc, dev)
+
+    @property
+    def unknown_share(self):
+        """The share of nodes no view observed."""
+        return float((self.wsum == 0).sum()) / float(self.wsum.numel())
+
+
+def _device_of(volume):
+    if volume.device.type != "cuda":
+        raise CppfError("fuse: the volume lives on %s; the kernels need a HIP device and there is no CPU fallback" % volume.device)
+    return volume.device
+
+
+def integrate(volume, depths, poses, K, masks=None, pixel_offset=0.0, znear=render.ZNEAR):
+    """cppf_tsdf_integrate: adds the views depths [V,H,W] (metres; 0 = no reading) with poses [V,12] or [V,3,4] (model -> OpenCV
+    camera), one camera matrix K and masks [V,H,W] (non-zero = the object; None: every pixel is) to the volume, in order.
+    pixel_offset: 0 for sensor images (pixel (r,c) lies on the ray through (c,r), ops.backproject's convention), 0.5 for images
+    from render.render_depth, which samples at pixel centres.  Images of another size or K go in another call."""
+    dev = _device_of(volume)
+    d = hostargs.image_batch(depths, dev, "fuse.integrate", max_dim=MAX_IMAGE)
+    V, H, W = d.shape
+    m = None if masks is None else hostargs.mask_batch(masks, d, dev, "fuse.integrate", same_shape=True)
+    P = hostargs.tensor(poses, torch.float32, dev).reshape(-1, 12)
+    if P.shape[0] != V:
+        raise ValueError("fuse.integrate: %d poses for %d views" % (P.shape[0], V))
+    hK = hostargs.camera4(K)
+    L = _lib.load()
+    nx, ny, nz = volume.dims
+    for a in range(0, V, MAX_VIEWS):
+        n = min(MAX_VIEWS, V - a)
+        _lib.check(L.cppf_tsdf_integrate(n, ops._p(d[a:]), ops._p(m[a:] if m is not None else None), ops._p(P[a:]), H, W, hK,
+                                         C.c_float(pixel_offset), _host3(volume.origin), C.c_float(volume.voxel), nx, ny, nz,
+                                         C.c_float(volume.trunc), C.c_float(znear), ops._p(volume.acc), ops._p(volume.wsum),
+                                         ops._stream()), "cppf_tsdf_integrate")
+    volume.views += V
+    return volume
+
+
+def extract_triangles(volume, min_weight=1, capacity=None):
+    """cppf_tsdf_extract: (tris float32 [T,9], keys int64 [T,3], status (triangles, cells that produced any), calls made) of the
+    volume's zero surface, in the order cell, tetrahedron, triangle.  The buffers start at `capacity` triangles (default
+    INITIAL_CAPACITY) and are grown to what status reports, once: at most two calls."""
+    dev = _device_of(volume)
+    nx, ny, nz = volume.dims
+    L = _lib.load()
+    ws = _WS.get(hostargs.stream_key(dev), int(L.cppf_tsdf_extract_workspace_bytes(nx, ny, nz)), dev)
+    status = torch.zeros((2,), dtype=torch.int64, device=dev)
+    cap = INITIAL_CAPACITY if capacity is None else int(capacity)
+    for call in (1, 2):
+        tris = torch.empty((cap, 9), dtype=torch.float32, device=dev)
+        keys = torch.empty((cap, 3), dtype=torch.int64, device=dev)
+        _lib.check(L.cppf_tsdf_extract(ops._p(volume.acc), ops._p(volume.wsum), _host3(volume.origin), C.c_float(volume.voxel), nx, ny,
+                                       nz, int(min_weight), cap, ops._p(tris) if cap else None, ops._p(keys) if cap else None,
+                                       ops._p(status), ops._p(ws), ws.numel(), ops._stream()), "cppf_tsdf_extract")
+        needed, cells = (int(x) for x in status.cpu().tolist())
+        if needed <= cap:
+            return tris[:needed], keys[:needed], (needed, cells), call
+        cap = needed
+    raise CppfError("cppf_tsdf_extract: the triangle count changed between two calls on one volume")
+
+
+def weld_by_key(tris, keys, drop_degenerate=True):
+    """(verts float32 [N,3], faces int64 [F,3], boundary_edges) of triangles [T,9] and their vertex keys [T,3] (tensors on any
+    device): one vertex per distinct key, in key order (equal keys carry equal bits, so the first occurrence stands for all);
+    drop_degenerate drops the triangles two of whose vertices coincide (the same key, or a node of exactly 0, where several
+    edges meet in one point); boundary_edges counts the undirected edges that one triangle only uses (0: a closed surface)."""
+    keys = keys.reshape(-1)
+    pos = tris.reshape(-1, 3)
+    if keys.numel() == 0:
+        return pos.new_zeros((0, 3)), keys.new_zeros((0, 3)), 0
+    uniq, inverse = torch.unique(keys, return_inverse=True)
+    first = torch.full((uniq.numel(),), keys.numel(), dtype=torch.int64, device=keys.device)
+    first.scatter_reduce_(0, inverse, torch.arange(keys.numel(), device=keys.device), reduce="amin")
+    verts = pos[first]
+    faces = inverse.reshape(-1, 3)
+    if drop_degenerate:
+        p = verts[faces]
+        same = (p[:, 0] == p[:, 1]).all(1) | (p[:, 1] == p[:, 2]).all(1) | (p[:, 2] == p[:, 0]).all(1)
+        faces = faces[~same]
+        used, faces = torch.unique(faces, return_inverse=True)         # vertices only dropped triangles used go too
+        verts, faces = verts[used], faces.reshape(-1, 3)
+    e = torch.cat([faces[:, [0, 1]], faces[:, [1, 2]], faces[:, [2, 0]]])
+    e = torch.sort(e, 1).values
+    _, counts = torch.unique(e[:, 0] * max(int(verts.shape[0]), 1) + e[:, 1], return_counts=True)
+    return verts, faces, int((counts == 1).sum())
+
+
+def extract(volume, min_weight=1, weld=True, drop_degenerate=True):
+    """The volume's zero surface as a render.Mesh (vertices float64 of the kernel's float32, metres, object frame), wound
+    counter-clockwise as seen from the outside.  weld=True merges the vertices by key and sets mesh.boundary_edges (edges used by
+    one triangle only; 0 means closed) and drops triangles without area when drop_degenerate; weld=False returns three vertices per
+    triangle, as emitted (boundary_edges None).  mesh.cells: the cells that produced triangles; mesh.extract_calls: 1 or 2."""
+    tris, keys, (needed, cells), calls = extract_triangles(volume, min_weight)
+    if weld:
+        verts, faces, boundary = weld_by_key(tris, keys, drop_degenerate)
+    else:
+        verts, faces, boundary = tris.reshape(-1, 3), torch.arange(3 * needed, device=tris.device).reshape(-1, 3), None
+    mesh = render.Mesh(verts.cpu().numpy(), faces.cpu().numpy())
+    mesh.boundary_edges, mesh.cells, mesh.extract_calls = boundary, cells, calls
+    return mesh
+
+
+def _sync(dev):
+    if torch.device(dev).type == "cuda":
+        torch.cuda.synchronize(dev)
+    return time.perf_counter()
+
+
+def _report(volume, mesh, t_volume, t_integrate, t_extract):
+    return dict(views=int(volume.views), dims=list(volume.dims), voxel=volume.voxel, trunc=volume.trunc,
+                triangles=int(mesh.faces.shape[0]), vertices=int(mesh.verts.shape[0]), boundary_edges=int(mesh.boundary_edges),
+                unknown_share=volume.unknown_share, seconds=dict(volume=t_volume, integrate=t_integrate, extract=t_extract))
+
+
+def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weight=1, pixel_offset=0.0, znear=render.ZNEAR,
+               volume=None):
+    """Both stages on one batch of views: (mesh, report).  `volume`: an existing Volume to add to (else Volume.around the views).
+    report: dict(views, dims, voxel, trunc, triangles, vertices, boundary_edges, unknown_share (nodes no view observed),
+    seconds: dict(volume, integrate, extract))."""
+    t0 = time.perf_counter()
+    if volume is None:
+        volume = Volume.around(depths, masks, poses, K, voxel, margin, trunc, pixel_offset)
+    t1 = _sync(volume.device)
+    integrate(volume, depths, poses, K, masks, pixel_offset, znear)
+    t2 = _sync(volume.device)
+    mesh = extract(volume, min_weight)
+    t3 = _sync(volume.device)
+    return mesh, _report(volume, mesh, t1 - t0, t2 - t1, t3 - t2)
+
+
+# ----------------------------------------------------------------------------------------------
+# a BOP-format scene folder of views
+# ----------------------------------------------------------------------------------------------
+class ViewsError(ValueError):
+    """A --views folder that cannot be read as one BOP-format scene."""
+
+
+def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True):
+    """The views of one object in a BOP-format scene folder: scene_camera.json (cam_K, depth_scale), scene_gt.json (cam_R_m2c,
+    cam_t_m2c in model units; read directly: no model file has to exist), depth/%06d.png and mask_visib/%06d_%06d.png.  obj_id:
+    the object (None: the scene's only one).  Returns a list of batches dict(K, depths [V,H,W] float32 metres, masks [V,H,W]
+    uint8 or None, poses [V,12] float32 model (metres) -> camera, im_ids), one per image size and K, in image order."""
+    from PIL import Image
+    gt_path, cam_path = os.path.join(views_dir, "scene_gt.json"), os.path.join(views_dir, "scene_camera.json")
+    for p in (gt_path, cam_path):
+        if not os.path.exists(p):
+            raise ViewsError("%s: not found (a BOP-format scene folder has scene_gt.json and scene_camera.json)" % p)
+    with open(gt_path) as f:
+        gt = {int(k): v for k, v in json.load(f).items()}
+    with open(cam_path) as f:
+        cam = {int(k): v for k, v in json.load(f).items()}
+    ids = sorted({int(g["obj_id"]) for lst in gt.values() for g in lst})
+    if obj_id is None:
+        if len(ids) != 1:
+            raise ViewsError("%s: the scene shows objects %s; choose one with --obj-id" % (views_dir, ids))
+        obj_id = ids[0]
+    groups = {}
+    for im in sorted(gt):
+        for g_index, g in enumerate(gt[im]):
+            if int(g["obj_id"]) != int(obj_id):
+                continue
+            if im not in cam:
+                raise ViewsError("%s: image %d is in scene_gt.json but not in scene_camera.json" % (views_dir, im))
+            dpath = os.path.join(views_dir, "depth", "%06d.png" % im)
+            if not os.path.exists(dpath):
+                raise ViewsError("%s: not found" % dpath)
+            depth = (np.array(Image.open(dpath)).astype(np.float64) * float(cam[im].get("depth_scale", 1.0)) / 1000.0).astype(np.float32)
+            mask = None
+            if use_masks:
+                mpath = os.path.join(views_dir, "mask_visib", "%06d_%06d.png" % (im, g_index))
+                if not os.path.exists(mpath):
+                    raise ViewsError("%s: not found (--no-masks fuses every pixel)" % mpath)
+                mk = np.array(Image.open(mpath))
+                mask = ((mk[..., 0] if mk.ndim == 3 else mk) > 0).astype(np.uint8)
+                if mask.shape != depth.shape:
+                    raise ViewsError("%s: mask %s for depth %s" % (mpath, mask.shape, depth.shape))
+            K = np.asarray(cam[im]["cam_K"], dtype=np.float64).reshape(3, 3)
+            R = np.asarray(g["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
+            t = np.asarray(g["cam_t_m2c"], dtype=np.float64).reshape(3, 1) * float(mesh_scale)
+            b = groups.setdefault((K.tobytes(), depth.shape), dict(K=K, depths=[], masks=[], poses=[], im_ids=[]))
+            b["depths"].append(depth)
+            b["masks"].append(mask)
+            b["poses"].append(np.hstack([R, t]).astype(np.float32).reshape(12))
+            b["im_ids"].append(im)
+    if not groups:
+        raise ViewsError("%s: no image shows object %s (objects: %s)" % (views_dir, obj_id, ids))
+    out = []
+    for b in groups.values():
+        out.append(dict(K=b["K"], depths=np.stack(b["depths"]), masks=np.stack(b["masks"]) if use_masks else None,
+                        poses=np.stack(b["poses"]), im_ids=b["im_ids"]))
+    return out
+
+
+def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001):
+    """read_views fused into one volume (one integrate call per image size and K): (mesh in metres, report)."""
+    batches = read_views(views_dir, obj_id, mesh_scale, use_masks)
+    t0 = time.perf_counter()
+    boxes = np.stack([Volume.bounds(b["depths"], b["masks"], b["poses"], b["K"], pixel_offset) for b in batches])
+    voxel = float(np.float32(voxel))
+    trunc = float(np.float32(TRUNC_VOXELS * voxel if trunc is None else trunc))
+    lo, hi = boxes[:, 0].min(0) - (trunc + voxel), boxes[:, 1].max(0) + (trunc + voxel)
+    volume = Volume(lo, voxel, np.ceil((hi - lo) / voxel).astype(np.int64) + 1, trunc)
+    t1 = _sync(volume.device)
+    for b in batches:
+        integrate(volume, b["depths"], b["poses"], b["K"], b["masks"], pixel_offset)
+    t2 = _sync(volume.device)
+    mesh = extract(volume, min_weight)
+    t3 = _sync(volume.device)
+    return mesh, _report(volume, mesh, t1 - t0, t2 - t1, t3 - t2)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cppf2_amd.fuse", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--views", required=True, help="one BOP-format scene folder: scene_camera.json, scene_gt.json, depth/, mask_visib/")
+    ap.add_argument("--obj-id", type=int, default=None, help="the object to fuse (default: the scene's only one)")
+    ap.add_argument("--voxel", type=float, required=True, help="node spacing in metres, e.g. 0.002")
+    ap.add_argument("--trunc", type=float, default=None, help="truncation distance in metres (default: 3 voxels)")
+    ap.add_argument("--min-weight", type=int, default=1, help="observations a node needs to count as known")
+    ap.add_argument("--no-masks", action="store_true", help="fuse every pixel (no mask_visib/ is read)")
+    ap.add_argument("--pixel-offset", type=float, default=0.0, help="0 for sensor images, 0.5 for images rendered at pixel centres")
+    ap.add_argument("--mesh-scale", type=float, default=0.001, help="model units to metres (0.001: a model in mm, as BOP's)")
+    ap.add_argument("--report", default=None, help="write the report as JSON here")
+    ap.add_argument("--out", required=True, help="the .ply to write, in model units")
+    a = ap.parse_args(argv)
+    if not (a.voxel > 0 and np.isfinite(a.voxel)):
+        ap.error("--voxel is a positive length in metres")
+    if a.trunc is not None and not (a.trunc > 0 and np.isfinite(a.trunc)):
+        ap.error("--trunc is a positive length in metres")
+    if a.min_weight < 1:
+        ap.error("--min-weight is at least 1")
+    if not (a.mesh_scale > 0 and np.isfinite(a.mesh_scale)):
+        ap.error("--mesh-scale is positive")
+    if not a.out.lower().endswith(".ply"):
+        ap.error("--out is a .ply file")
+    from . import bop_data
+    mesh, report = fuse_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset, a.mesh_scale)
+    if not mesh.faces.shape[0]:
+        raise CppfError("fuse: the volume has no surface (no node behind a reading); check the poses, --mesh-scale and --pixel-offset")
+    bop_data.write_ply(a.out, mesh.verts / a.mesh_scale, mesh.faces)
+    if a.report:
+        with open(a.report, "w") as f:
+            json.dump(report, f, indent=1)
+    print("fused %d views into %d x %d x %d nodes: %d triangles, %d vertices, %d boundary edges -> %s"
+          % (report["views"], *report["dims"], report["triangles"], report["vertices"], report["boundary_edges"], a.out), file=sys.stderr)
+    return report
+
+
+if __name__ == "__main__":
+    main()

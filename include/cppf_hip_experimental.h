@@ -11,7 +11,8 @@
  *   - a test hook;
  *   - the solid-interval checks on candidate poses (cppf2_amd/solid.py): opt-in and new;
  *   - the deviation statistic of the symmetry detection (cppf2_amd/symmetry.py): opt-in and new;
- *   - the oriented-box IoU of the NOCS scorer (cppf2_amd/box_iou.py): opt-in and new.
+ *   - the oriented-box IoU of the NOCS scorer (cppf2_amd/box_iou.py): opt-in and new;
+ *   - depth-view fusion into a signed distance volume and its surface mesh (cppf2_amd/fuse.py): new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -208,6 +209,43 @@ int cppf_sym_deviation(const float* queries, int nq, const float* tris, int nf, 
  * interface keeps its 74 entry points. */
 int cppf_box_iou(const double* R1, const double* t1, const double* s1, const double* R2, const double* t2, const double* s2,
                  const int32_t* turns, const double* turn_cs, int max_turns, int P, double* iou, void* stream);
+
+/* ---- a mesh from posed depth views: truncated signed distance volume, marching tetrahedra (the reference has no such step) ----
+ * The volume is two device arrays, z fastest: acc float32 [nx,ny,nz] (the sum of the observations) and wsum int32 [nx,ny,nz]
+ * (their number); node (i,j,k) sits at h_origin + (i,j,k) * voxel in the object's frame, metres.  h_origin: double[3] on the
+ * HOST, rounded to float32 once; h_K: double[4] = (fx, fy, cx, cy) on the HOST, rounded alike.  nx, ny, nz >= 1 and
+ * nx ny nz <= 2^27 (134 217 728 nodes, 512^3: 1 GiB of volume); voxel, trunc, znear > 0 and finite.  The exact order of the
+ * float32 operations is stated in cppf2_amd/csrc/cppf_fuse.hip and restated in tests/fuse_ref.py.
+ *
+ * cppf_tsdf_integrate: adds V views (0 <= V <= 65536; 0 launches nothing) to the caller's acc / wsum (zeroed by the caller
+ * before the first call) in one launch: depth float32 [V,H,W] (metres; 0, negative, NaN and infinite = no reading), masks uint8
+ * [V,H,W] or NULL (non-zero = the object), poses float32 [V,12] (row-major 3x4, model -> OpenCV camera), 1 <= H, W <= 16384.
+ * pixel_offset: 0 for images whose pixel (r, c) lies on the ray through (c, r) (cppf_backproject's convention), 0.5 for images
+ * sampled at pixel centres (cppf_render_depth).  A node at camera depth zc >= znear that projects into the image at a pixel
+ * with a reading d observes min((d - zc) / trunc, 1) when the pixel is inside the mask (or no masks are given) and
+ * d - zc >= -trunc; outside the mask it observes 1 when d - zc > 0 (free space) and nothing otherwise, so that background
+ * never becomes surface and still carves.  The views are summed in order inside the kernel: views 0..V-1 in one call give the
+ * bytes of any split into consecutive calls.
+ *
+ * cppf_tsdf_extract: the surface tsdf = acc / wsum = 0 by marching tetrahedra (six per cell around the body diagonal).  A node
+ * is known iff wsum >= min_weight (>= 1) and inside iff tsdf < 0; a cell is processed iff its 8 corners are known.  Out:
+ * tris float32 [capacity,9] (three vertices per row, counter-clockwise seen from the outside), keys int64 [capacity,3] (per
+ * vertex 8 * lo + (dx | dy << 1 | dz << 2) of the grid edge it lies on, lo = the smaller linear node index (i ny + j) nz + k of
+ * the edge's ends, (dx,dy,dz) the step to the other end: equal keys have equal bits, so welding by key is exact), status int64
+ * [2] = (triangles needed, cells that produced any).  Order: cell, tetrahedron, triangle.  If more triangles are needed than
+ * `capacity` only status is written: grow the buffers and call again (capacity 0 with tris = keys = NULL just counts).
+ * Triangles without area (a node exactly 0) are emitted like any other.  workspace: cppf_tsdf_extract_workspace_bytes(nx, ny,
+ * nz) bytes (-1 for sizes the call refuses), 8-byte aligned.  Three launches, no host synchronisation.
+ *
+ * All return CPPF_EINVAL for null pointers, dims < 1 or above the size limit, non-positive or non-finite voxel / trunc / znear,
+ * min_weight < 1, a negative capacity and a workspace that is too small; all before any device work. */
+int cppf_tsdf_integrate(int V, const float* depth, const uint8_t* masks, const float* poses, int H, int W, const double* h_K,
+                        float pixel_offset, const double* h_origin, float voxel, int nx, int ny, int nz, float trunc, float znear,
+                        float* acc, int32_t* wsum, void* stream);
+int64_t cppf_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
+int cppf_tsdf_extract(const float* acc, const int32_t* wsum, const double* h_origin, float voxel, int nx, int ny, int nz,
+                      int min_weight, int64_t capacity, float* tris, int64_t* keys, int64_t* status, void* workspace,
+                      int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
