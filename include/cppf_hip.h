@@ -370,7 +370,8 @@ int cppf_voxel_downsample(const float* pts, int n, float res, uint64_t seed, int
  *  - screen positions are snapped to 1/256 px; edge functions in int64 with the top-left rule (image y down): triangles that
  *    share an edge cover each pixel on it exactly once.  depth = camera z of the triangle's 1/z plane over the snapped
  *    positions; the nearest surface wins, equal depths go to the lower triangle id; a pixel whose z lies outside
- *    [znear, zfar] is not covered.  cull: 0 = none, 1 = back faces ((v1-v0)x(v2-v0) pointing away from the camera).
+ *    [znear, zfar] is not covered, nor is one whose float32 z is +inf (zfar = +inf would admit it; depth 0 stays "nothing
+ *    drawn").  cull: 0 = none, 1 = back faces ((v1-v0)x(v2-v0) pointing away from the camera).
  *  - out: depth float32[B,H,W] (0 where nothing is drawn), tri_id int32[B,H,W] (optional; index within the view's range,
  *    -1 where empty).  H, W <= 8192, B <= 65535.
  *  - status int64[2] (device): [0] = triangles rejected (a vertex at z < znear or NaN -- no near-plane clipping --, a snapped

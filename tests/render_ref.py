@@ -83,7 +83,7 @@ def render(verts, tris, pose, K, H, W, znear=0.05, zfar=100.0, cull=1, with_coun
                 w = w + e1.astype(F32) * g["iz1"]
                 w = w + e2.astype(F32) * g["iz2"]
                 z = g["area"] / w
-            ok = cov & (z >= znear) & (z <= zfar)
+            ok = cov & (z >= znear) & (z <= zfar) & (z < F32(np.inf))     # the kernel's minimum starts at +inf: z = +inf never wins
             zz = np.where(ok, z, F32(np.inf))
             zmin = zz.min(0)
             best = np.where(ok & (zz == zmin[None]), g["id"], np.iinfo(np.int64).max).min(0)
