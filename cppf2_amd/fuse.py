@@ -7,7 +7,10 @@ custom-object path starts from a mesh (train_custom.ipynb).
     integrate(vol, depths, poses, K, masks=masks)                   # any number of calls; images of one size and K per call
     mesh = extract(vol)                                             # render.Mesh, vertices welded; mesh.boundary_edges
     mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002)
-    python -m cppf2_amd.fuse --views <bop scene dir> --obj-id 15 --voxel 0.002 --out obj_000015.ply
+    python -m cppf2_amd.fuse --views <bop scene dir> --obj-id 15 --voxel 0.002 --out obj_000015.ply [--simplify-cell 0.006]
+
+The surface has one or two triangles per voxel it crosses; simplify_cell / --simplify-cell hands it to cppf2_amd.simplify
+ before it is returned or written.
 
 The kernels are cppf_tsdf_integrate and cppf_tsdf_extract (include/cppf_hip_experimental.h; the definitions are stated in
 cppf2_amd/csrc/cppf_fuse.hip and restated in tests/fuse_ref.py).  Not done: no weighting by viewing angle or distance, no
@@ -222,11 +225,23 @@ def _report(volume, mesh, t_volume, t_integrate, t_extract):
                 unknown_share=volume.unknown_share, seconds=dict(volume=t_volume, integrate=t_integrate, extract=t_extract))
 
 
+def _finish(volume, mesh, seconds, simplify_cell):
+    """(mesh, report) of the mesh extracted from a volume.  With simplify_cell the mesh goes through simplify.cluster first, the
+    cells on the voxel lattice (the origin is the volume's), and the report gains `simplify`, cluster's own report."""
+    if simplify_cell is None:
+        return mesh, _report(volume, mesh, *seconds)
+    from . import simplify
+    mesh, simplified = simplify.cluster(mesh, simplify_cell, origin=volume.origin)
+    return mesh, dict(_report(volume, mesh, *seconds), simplify=simplified)
+
+
 def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weight=1, pixel_offset=0.0, znear=render.ZNEAR,
-               volume=None):
+               volume=None, simplify_cell=None):
     """Both stages on one batch of views: (mesh, report).  `volume`: an existing Volume to add to (else Volume.around the views).
     report: dict(views, dims, voxel, trunc, triangles, vertices, boundary_edges, unknown_share (nodes no view observed),
-    seconds: dict(volume, integrate, extract))."""
+    seconds: dict(volume, integrate, extract)).  simplify_cell (metres; None: no such stage): the welded mesh goes through
+    simplify.cluster with cells of that edge on the voxel lattice; triangles, vertices and boundary_edges then describe the
+    simplified mesh and report["simplify"] is cluster's report (triangles_in: what was extracted)."""
     t0 = time.perf_counter()
     if volume is None:
         volume = Volume.around(depths, masks, poses, K, voxel, margin, trunc, pixel_offset)
@@ -235,7 +250,7 @@ def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weig
     t2 = _sync(volume.device)
     mesh = extract(volume, min_weight)
     t3 = _sync(volume.device)
-    return mesh, _report(volume, mesh, t1 - t0, t2 - t1, t3 - t2)
+    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -301,8 +316,10 @@ def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True):
     return out
 
 
-def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001):
-    """read_views fused into one volume (one integrate call per image size and K): (mesh in metres, report)."""
+def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
+               simplify_cell=None):
+    """read_views fused into one volume (one integrate call per image size and K): (mesh in metres, report).  simplify_cell: as
+    fuse_views'."""
     batches = read_views(views_dir, obj_id, mesh_scale, use_masks)
     t0 = time.perf_counter()
     boxes = np.stack([Volume.bounds(b["depths"], b["masks"], b["poses"], b["K"], pixel_offset) for b in batches])
@@ -316,7 +333,7 @@ def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_mask
     t2 = _sync(volume.device)
     mesh = extract(volume, min_weight)
     t3 = _sync(volume.device)
-    return mesh, _report(volume, mesh, t1 - t0, t2 - t1, t3 - t2)
+    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell)
 
 
 def main(argv=None):
@@ -329,6 +346,8 @@ def main(argv=None):
     ap.add_argument("--no-masks", action="store_true", help="fuse every pixel (no mask_visib/ is read)")
     ap.add_argument("--pixel-offset", type=float, default=0.0, help="0 for sensor images, 0.5 for images rendered at pixel centres")
     ap.add_argument("--mesh-scale", type=float, default=0.001, help="model units to metres (0.001: a model in mm, as BOP's)")
+    ap.add_argument("--simplify-cell", type=float, default=None,
+                    help="simplify the mesh by vertex clustering with cells of this edge in metres, e.g. 3 voxels (default: not at all)")
     ap.add_argument("--report", default=None, help="write the report as JSON here")
     ap.add_argument("--out", required=True, help="the .ply to write, in model units")
     a = ap.parse_args(argv)
@@ -342,8 +361,11 @@ def main(argv=None):
         ap.error("--mesh-scale is positive")
     if not a.out.lower().endswith(".ply"):
         ap.error("--out is a .ply file")
+    if a.simplify_cell is not None and not (a.simplify_cell > 0 and np.isfinite(a.simplify_cell)):
+        ap.error("--simplify-cell is a positive length in metres")
     from . import bop_data
-    mesh, report = fuse_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset, a.mesh_scale)
+    mesh, report = fuse_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset, a.mesh_scale,
+                              a.simplify_cell)
     if not mesh.faces.shape[0]:
         raise CppfError("fuse: the volume has no surface (no node behind a reading); check the poses, --mesh-scale and --pixel-offset")
     bop_data.write_ply(a.out, mesh.verts / a.mesh_scale, mesh.faces)

@@ -12,7 +12,9 @@
  *   - the solid-interval checks on candidate poses (cppf2_amd/solid.py): opt-in and new;
  *   - the deviation statistic of the symmetry detection (cppf2_amd/symmetry.py): opt-in and new;
  *   - the oriented-box IoU of the NOCS scorer (cppf2_amd/box_iou.py): opt-in and new;
- *   - depth-view fusion into a signed distance volume and its surface mesh (cppf2_amd/fuse.py): new.
+ *   - depth-view fusion into a signed distance volume and its surface mesh (cppf2_amd/fuse.py): new;
+ *   - mesh simplification by vertex clustering with quadric representatives (cppf2_amd/simplify.py):
+ *     opt-in and new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -246,6 +248,34 @@ int64_t cppf_tsdf_extract_workspace_bytes(int nx, int ny, int nz);
 int cppf_tsdf_extract(const float* acc, const int32_t* wsum, const double* h_origin, float voxel, int nx, int ny, int nz,
                       int min_weight, int64_t capacity, float* tris, int64_t* keys, int64_t* status, void* workspace,
                       int64_t workspace_bytes, void* stream);
+
+/* ---- a mesh simplified by vertex clustering with quadric representatives (the reference has no such step) ----
+ * The lattice: cell (i,j,k), 0 <= i,j,k < 2^21, is [o + i cell, o + (i+1) cell) per axis, o = h_origin (double[3] on the HOST)
+ * rounded to float32 once, cell > 0 and finite, metres.  The exact order of the operations is stated in
+ * cppf2_amd/csrc/cppf_simplify.hip and restated in tests/simplify_ref.py.
+ *
+ * cppf_cluster_keys: keys int64 [n] of verts float32 [n,3]: i << 42 | j << 21 | k of the vertex' cell, float32 arithmetic
+ * (t = (x - o) / cell per axis, inside iff 0 <= t < 2^21 on every axis, decided in float32 before any cast), -1 for a vertex
+ * outside the lattice or not finite.  A coordinate exactly on a boundary belongs to the upper cell.
+ *
+ * cppf_cluster_quadrics: pos float32 [nc,3], one representative per cluster.  verts float32 [n,3], faces int32 [nf,3]
+ * (nf <= 715 827 882), corners int32 [m] (entry 3 f + j = corner j of face f; 0 <= m <= 3 nf) sorted by cluster, seg_off int64
+ * [nc+1] (cluster c owns corners[seg_off[c] .. seg_off[c+1])), keys int64 [nc] (each cluster's cell).  Float64, one lane per
+ * cluster, the corners summed sequentially in list order (the order is part of the definition; no atomics).  The
+ * representative minimises sum over the cluster's corners' triangles of area (u . x - d)^2 + lam area |x - centroid|^2 (u, d
+ * the triangle's plane; x relative to the cell's centre), i.e. solves (A + lam w I) x = b + lam m, symmetric positive definite
+ * with condition number at most (1 + lam) / lam, by LDL^T without pivoting; a cluster of triangles without area gets the mean
+ * of its corners; the result is clamped into the cell and rounded to float32 once.  lam > 0 and finite.  A corner or vertex
+ * index outside its array skips that corner; a negative key gives NaN.
+ *
+ * Both: n, nf, nc = 0 are valid calls that launch nothing; no workspace; one launch each.  CPPF_EINVAL for null required
+ * pointers, negative counts, m outside [0, 3 nf], a non-finite origin and cell or lam not positive and finite; all before any
+ * device work.  Experimental while the stage is opt-in and young: the stable interface keeps its 74
+ * entry points. */
+int cppf_cluster_keys(const float* verts, int n, const double* h_origin, float cell, int64_t* keys, void* stream);
+int cppf_cluster_quadrics(const float* verts, int n, const int32_t* faces, int nf, const int32_t* corners, int64_t m,
+                          const int64_t* seg_off, const int64_t* keys, int nc, const double* h_origin, float cell, double lam,
+                          float* pos, void* stream);
 
 #ifdef __cplusplus
 }
