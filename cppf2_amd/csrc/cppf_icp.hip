@@ -70,15 +70,12 @@
 // step of the combined system, [4] model-side inliers of the last iteration, [5] sqrt(sum e^2 / inliers) of those (plain sums),
 // [6] inliers / visible in-image samples, [7] the visible in-image samples.
 #include "cppf_common.h"
+#include "cppf_icp_solve.h"
 
 #define ICP_THREADS 256
 #define ICP_TILE 1024          // model samples per LDS tile (16 KiB of float4)
-#define ICP_TERMS 30           // 21 (J^T J upper) + 6 (J^T e) + count + sum e^2 + sum |q|^2
 #define ICP_SLOT 32            // doubles per block slot
 #define ICP_REFINED 16         // CppfSceneResult.flags bit4: pose refined by ICP
-#define ICP_TAU 1e-9           // eigenvalues of S A S at or below ICP_TAU * lambda_max are dropped (unobservable directions)
-#define ICP_JEPS 1e-17         // Jacobi: an off-diagonal entry this small next to its two diagonal entries counts as 0
-#define ICP_SWEEPS 16          // Jacobi sweeps at most (measured: 3-8, the last of them rotating nothing)
 
 __global__ __launch_bounds__(ICP_THREADS) void icp_match_kernel(const float* __restrict__ pts, const int32_t* __restrict__ pt_off,
                                                                 int max_n, int nblk, const float* __restrict__ model_pts,
@@ -256,8 +253,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp_project_kernel(const float* _
   if (threadIdx.x == 0) vis[(int64_t)b * (slots - nblk) + blockIdx.x] = (s_v[0] + s_v[1]) + (s_v[2] + s_v[3]);
 }
 
-// One wavefront per instance; lane 0 does the 6x6 solve and the pose update in LDS (no register array with a loop-varying
-// index, so nothing goes to scratch memory).  DEPTH = false is cppf_icp_refine's solve: rows of nblk observed slots, 4 stats.
+// One wavefront per instance; lane 0 does the 6x6 solve and the pose update in LDS (cppf_icp_solve.h, shared with
+// cppf_track.hip).  DEPTH = false is cppf_icp_refine's solve: rows of nblk observed slots, 4 stats.
 // DEPTH = true is cppf_icp_refine_depth's: nblk is the whole row (ceil(max_n / 256) observed slots, then the model slots, then
 // behind all rows the visible counts), the sums run on from the observed slots over the model slots, 8 stats.
 template <bool DEPTH>
@@ -266,7 +263,7 @@ __global__ __launch_bounds__(CPPF_WAVE) void icp_solve_kernel(const int32_t* __r
                                                               CppfSceneResult* __restrict__ results, float* __restrict__ stats) {
   __shared__ double s_t[ICP_SLOT];
   __shared__ double s_o[DEPTH ? ICP_SLOT : 1];
-  __shared__ double s_A[36], s_V[36], s_s[6], s_y[6], s_x[6], s_K[9], s_R[9], s_dR[9], s_Rn[9];
+  __shared__ IcpSolveLds L;
   const int b = blockIdx.x;
   CppfSceneResult& rec = results[b];
   float* st = stats + (DEPTH ? 8 : 4) * (int64_t)b;
@@ -295,102 +292,13 @@ __global__ __launch_bounds__(CPPF_WAVE) void icp_solve_kernel(const int32_t* __r
   __syncthreads();
   if (threadIdx.x != 0) return;
   const double cnt = s_t[27];
-  bool ok = cnt >= 6.0;
+  const bool ok = cnt >= 6.0 && icp_min_norm_step(s_t, cnt, L);
   if (ok) {
-    const double L2 = s_t[29] / cnt;
-    const double r = L2 > 0.0 ? 1.0 / sqrt(L2) : 0.0;
-    for (int j = 0; j < 6; ++j) s_s[j] = j < 3 ? r : 1.0;
-    int o = 0;
-    for (int a = 0; a < 6; ++a)
-      for (int c = a; c < 6; ++c) {
-        const double v = (s_s[a] * s_t[o]) * s_s[c];
-        s_A[a * 6 + c] = v;
-        s_A[c * 6 + a] = v;
-        s_V[a * 6 + c] = a == c ? 1.0 : 0.0;
-        s_V[c * 6 + a] = a == c ? 1.0 : 0.0;
-        ++o;
-      }
-    for (int sweep = 0; sweep < ICP_SWEEPS; ++sweep) {       // cyclic Jacobi: S A S = V diag(a_ii) V^T
-      bool rotated = false;
-      for (int p = 0; p < 5; ++p)
-        for (int q = p + 1; q < 6; ++q) {
-          const double apq = s_A[p * 6 + q], app = s_A[p * 7], aqq = s_A[q * 7];
-          if (apq == 0.0) continue;
-          if (fabs(apq) <= ICP_JEPS * (fabs(app) + fabs(aqq))) {
-            s_A[p * 6 + q] = 0.0;
-            s_A[q * 6 + p] = 0.0;
-            continue;
-          }
-          const double th = (aqq - app) / (2.0 * apq);
-          const double t = (th >= 0.0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-          const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
-          s_A[p * 7] = app - t * apq;
-          s_A[q * 7] = aqq + t * apq;
-          s_A[p * 6 + q] = 0.0;
-          s_A[q * 6 + p] = 0.0;
-          for (int k = 0; k < 6; ++k) {
-            if (k != p && k != q) {
-              const double akp = s_A[k * 6 + p], akq = s_A[k * 6 + q];
-              const double np_ = c * akp - sn * akq, nq = sn * akp + c * akq;
-              s_A[k * 6 + p] = np_;
-              s_A[p * 6 + k] = np_;
-              s_A[k * 6 + q] = nq;
-              s_A[q * 6 + k] = nq;
-            }
-            const double vkp = s_V[k * 6 + p], vkq = s_V[k * 6 + q];
-            s_V[k * 6 + p] = c * vkp - sn * vkq;
-            s_V[k * 6 + q] = sn * vkp + c * vkq;
-          }
-          rotated = true;
-        }
-      if (!rotated) break;
-    }
-    double lmax = 0.0;
-    for (int i = 0; i < 6; ++i)
-      if (s_A[i * 7] > lmax) lmax = s_A[i * 7];
-    for (int j = 0; j < 6; ++j) s_y[j] = 0.0;
-    int rank = 0;
-    for (int i = 0; i < 6; ++i) {                            // y = -sum_kept V_i (V_i . S b) / lambda_i
-      const double lam = s_A[i * 7];
-      if (!(lam > ICP_TAU * lmax)) continue;
-      double g = 0.0;
-      for (int j = 0; j < 6; ++j) g += s_V[j * 6 + i] * (s_s[j] * s_t[21 + j]);
-      const double f = -g / lam;
-      for (int j = 0; j < 6; ++j) s_y[j] += f * s_V[j * 6 + i];
-      ++rank;
-    }
-    bool nonzero = false, finite = true;
-    for (int j = 0; j < 6; ++j) {
-      s_x[j] = s_s[j] * s_y[j];
-      nonzero = nonzero || s_x[j] != 0.0;
-      finite = finite && fabs(s_x[j]) < __builtin_inf();
-    }
-    ok = rank > 0 && nonzero && finite;
-  }
-  if (ok) {
-    const double w0 = s_x[0], w1 = s_x[1], w2 = s_x[2];
-    const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-    double a, c;
-    if (th2 < 1e-8) {
-      a = 1.0 - th2 / 6.0;
-      c = 0.5 - th2 / 24.0;
-    } else {
-      const double th = sqrt(th2);
-      a = sin(th) / th;
-      c = (1.0 - cos(th)) / th2;
-    }
-    s_K[0] = 0.0; s_K[1] = -w2; s_K[2] = w1;
-    s_K[3] = w2; s_K[4] = 0.0; s_K[5] = -w0;
-    s_K[6] = -w1; s_K[7] = w0; s_K[8] = 0.0;
-    for (int r = 0; r < 3; ++r)
-      for (int q = 0; q < 3; ++q) s_dR[r * 3 + q] = ((r == q ? 1.0 - c * th2 : 0.0) + a * s_K[r * 3 + q]) + (c * s_x[r]) * s_x[q];
-    for (int j = 0; j < 9; ++j) s_R[j] = rec.R[j];
-    for (int r = 0; r < 3; ++r)                      // R dR^T
-      for (int q = 0; q < 3; ++q)
-        s_Rn[r * 3 + q] = (s_R[r * 3] * s_dR[q * 3] + s_R[r * 3 + 1] * s_dR[q * 3 + 1]) + s_R[r * 3 + 2] * s_dR[q * 3 + 2];
+    for (int j = 0; j < 9; ++j) L.R[j] = rec.R[j];
+    icp_rotation_update(L);
     for (int r = 0; r < 3; ++r) {
-      rec.t[r] = rec.t[r] - ((s_Rn[r * 3] * s_x[3] + s_Rn[r * 3 + 1] * s_x[4]) + s_Rn[r * 3 + 2] * s_x[5]);
-      for (int q = 0; q < 3; ++q) rec.R[r * 3 + q] = s_Rn[r * 3 + q];
+      rec.t[r] = rec.t[r] - ((L.Rn[r * 3] * L.x[3] + L.Rn[r * 3 + 1] * L.x[4]) + L.Rn[r * 3 + 2] * L.x[5]);
+      for (int q = 0; q < 3; ++q) rec.R[r * 3 + q] = L.Rn[r * 3 + q];
     }
   }
   const double ocnt = DEPTH ? s_o[27] : cnt, sse = DEPTH ? s_o[28] : s_t[28];

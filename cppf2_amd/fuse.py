@@ -8,13 +8,16 @@ custom-object path starts from a mesh (train_custom.ipynb).
     mesh = extract(vol)                                             # render.Mesh, vertices welded; mesh.boundary_edges
     mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002)
     python -m cppf2_amd.fuse --views <bop scene dir> --obj-id 15 --voxel 0.002 --out obj_000015.ply [--simplify-cell 0.006]
+    python -m cppf2_amd.fuse --views <dir> --track --voxel 0.004 --out obj.ply          # only the first image's pose is used
 
 The surface has one or two triangles per voxel it crosses; simplify_cell / --simplify-cell hands it to cppf2_amd.simplify
  before it is returned or written.
 
 The kernels are cppf_tsdf_integrate and cppf_tsdf_extract (include/cppf_hip_experimental.h; the definitions are stated in
 cppf2_amd/csrc/cppf_fuse.hip and restated in tests/fuse_ref.py).  Not done: no weighting by viewing angle or distance, no
-colour, no hole filling (what no view saw stays open: mesh.boundary_edges counts it), no pose optimisation (the poses are trusted).
+colour, no hole filling (what no view saw stays open: mesh.boundary_edges counts it).  The poses are trusted as given; --track
+(cppf2_amd/track.py) is for a sequence of which only the first pose is known: every later frame is aligned
+to the volume built so far before it is integrated (cppf_tsdf_track).  No loop closure, no bundle adjustment.
 """
 from __future__ import annotations
 
@@ -260,11 +263,12 @@ class ViewsError(ValueError):
     """A --views folder that cannot be read as one BOP-format scene."""
 
 
-def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True):
+def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True, first_pose_only=False):
     """The views of one object in a BOP-format scene folder: scene_camera.json (cam_K, depth_scale), scene_gt.json (cam_R_m2c,
     cam_t_m2c in model units; read directly: no model file has to exist), depth/%06d.png and mask_visib/%06d_%06d.png.  obj_id:
     the object (None: the scene's only one).  Returns a list of batches dict(K, depths [V,H,W] float32 metres, masks [V,H,W]
-    uint8 or None, poses [V,12] float32 model (metres) -> camera, im_ids), one per image size and K, in image order."""
+    uint8 or None, poses [V,12] float32 model (metres) -> camera, im_ids), one per image size and K, in image order.
+    first_pose_only (--track): an entry after the object's first may lack cam_R_m2c / cam_t_m2c; its pose is then NaN."""
     from PIL import Image
     gt_path, cam_path = os.path.join(views_dir, "scene_gt.json"), os.path.join(views_dir, "scene_camera.json")
     for p in (gt_path, cam_path):
@@ -300,8 +304,11 @@ def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True):
                 if mask.shape != depth.shape:
                     raise ViewsError("%s: mask %s for depth %s" % (mpath, mask.shape, depth.shape))
             K = np.asarray(cam[im]["cam_K"], dtype=np.float64).reshape(3, 3)
-            R = np.asarray(g["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
-            t = np.asarray(g["cam_t_m2c"], dtype=np.float64).reshape(3, 1) * float(mesh_scale)
+            if first_pose_only and groups and not ("cam_R_m2c" in g and "cam_t_m2c" in g):
+                R, t = np.full((3, 3), np.nan), np.full((3, 1), np.nan)
+            else:
+                R = np.asarray(g["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
+                t = np.asarray(g["cam_t_m2c"], dtype=np.float64).reshape(3, 1) * float(mesh_scale)
             b = groups.setdefault((K.tobytes(), depth.shape), dict(K=K, depths=[], masks=[], poses=[], im_ids=[]))
             b["depths"].append(depth)
             b["masks"].append(mask)
@@ -348,6 +355,13 @@ def main(argv=None):
     ap.add_argument("--mesh-scale", type=float, default=0.001, help="model units to metres (0.001: a model in mm, as BOP's)")
     ap.add_argument("--simplify-cell", type=float, default=None,
                     help="simplify the mesh by vertex clustering with cells of this edge in metres, e.g. 3 voxels (default: not at all)")
+    ap.add_argument("--track", action="store_true",
+                    help="use the first image's pose only: track every later image against the volume before integrating it")
+    ap.add_argument("--track-iters", type=int, default=10, help="--track: iterations per frame")
+    ap.add_argument("--track-stride", type=int, default=1, help="--track: use every n-th pixel row and column")
+    ap.add_argument("--track-sweeps", type=int, default=1, help="--track: passes that re-track all frames against the finished volume")
+    ap.add_argument("--track-extent", type=float, default=None,
+                    help="--track: metres of volume beyond the first image's box (default: that box's longest side)")
     ap.add_argument("--report", default=None, help="write the report as JSON here")
     ap.add_argument("--out", required=True, help="the .ply to write, in model units")
     a = ap.parse_args(argv)
@@ -363,9 +377,18 @@ def main(argv=None):
         ap.error("--out is a .ply file")
     if a.simplify_cell is not None and not (a.simplify_cell > 0 and np.isfinite(a.simplify_cell)):
         ap.error("--simplify-cell is a positive length in metres")
+    if a.track_iters < 1 or a.track_stride < 1 or a.track_sweeps < 0:
+        ap.error("--track-iters and --track-stride are at least 1, --track-sweeps at least 0")
+    if a.track_extent is not None and not (a.track_extent >= 0 and np.isfinite(a.track_extent)):
+        ap.error("--track-extent is a length in metres")
     from . import bop_data
-    mesh, report = fuse_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset, a.mesh_scale,
-                              a.simplify_cell)
+    if a.track:
+        from . import track
+        mesh, report = track.onboard_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset,
+                                           a.mesh_scale, a.simplify_cell, a.track_iters, a.track_stride, a.track_sweeps, a.track_extent)
+    else:
+        mesh, report = fuse_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset, a.mesh_scale,
+                                  a.simplify_cell)
     if not mesh.faces.shape[0]:
         raise CppfError("fuse: the volume has no surface (no node behind a reading); check the poses, --mesh-scale and --pixel-offset")
     bop_data.write_ply(a.out, mesh.verts / a.mesh_scale, mesh.faces)

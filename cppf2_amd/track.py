@@ -1,0 +1,174 @@
+"""Depth frames tracked against a signed distance volume: what lets fuse.py take a sequence of which only
+the first frame's pose is known (a hand-held sequence, BOP's dynamic onboarding) or whose poses are only nominal (a turntable).
+Direct alignment of the frame's points to the volume's value and gradient (Bylow et al., RSS 2013) -- no mesh, no raycast, no
+nearest-neighbour search -- with the minimum-norm Gauss-Newton step of the ICP of section 13.  The reference has no such step.
+
+    poses, stats = track(volume, depths, K, poses, masks=masks)               # B frames in one call, each from its own start
+    volume, poses, report = onboard(depths, masks, K, pose0, voxel=0.004)     # frame by frame: track, then integrate
+    python -m cppf2_amd.fuse --views <dir> --track --voxel 0.004 --out obj.ply
+
+The kernel is cppf_tsdf_track (include/cppf_hip_experimental.h; the definitions are stated in cppf2_amd/csrc/cppf_track.hip and
+restated in tests/track_ref.py).  Capture range: a frame whose surface lies farther than trunc from the volume's surface has no
+gradient to follow; report["max_step"] beside report["trunc"] says how close a sequence came.  Not done: coarse-to-fine
+pyramids, loop closure, bundle adjustment, colour, weights.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import time
+
+import numpy as np
+import torch
+
+from . import _lib, fuse, hostargs, ops, render
+from ._lib import CppfError
+
+MAX_FRAMES = 65535               # frames per cppf_tsdf_track call
+GATE_START = 0.8                 # the first iteration's inlier gate, in units of trunc; the last one's is one voxel
+MIN_INLIER_SHARE = 0.5           # a frame with a smaller share of inliers among its gated pixels is reported lost
+
+_WS = hostargs.ScratchCache("cppf_tsdf_track_workspace_bytes", CppfError)
+
+
+def gates(iters, d0, d1):
+    """float32 [iters]: the inlier gates d_k = d0 (d1 / d0)^(k / (iters - 1)) (d0 when iters = 1), float64 on the host and rounded
+    once: cppf_icp_refine's schedule."""
+    d0, d1 = float(np.float32(d0)), float(np.float32(d1))
+    if not (0 < d0 < np.inf and 0 < d1 < np.inf):
+        raise ValueError("track: the gates are positive and finite lengths, not (%r, %r)" % (d0, d1))
+    if iters == 1:
+        return np.array([d0], dtype=np.float32)
+    return np.array([np.float32(d0 * (d1 / d0) ** (k / (iters - 1))) for k in range(iters)], dtype=np.float32)
+
+
+def track(volume, depths, K, poses, masks=None, iters=10, gate=None, stride=1, pixel_offset=0.0, min_weight=1):
+    """cppf_tsdf_track: (poses float64 [B,12], stats float32 [B,4]), device tensors, of the frames depths [B,H,W] (metres; 0 = no
+    reading) started at poses [B,12] or [B,3,4] (model -> OpenCV camera; the argument is not written) against the volume, one
+    batched call.  masks [B,H,W] (non-zero = the object; None: every pixel with a reading); gate = (first, last) inlier distance
+    in metres on the volume's value (default 0.8 trunc down to one voxel, geometric over the iterations); the pixels (r, c) with
+    r and c multiples of stride take part; pixel_offset as fuse.integrate's.  stats: inliers of the last iteration, their RMS
+    distance, inliers / masked pixels with a reading, iterations that moved the pose.  A frame that finds fewer than 6 inliers
+    keeps its pose byte for byte."""
+    dev = fuse._device_of(volume)
+    d = hostargs.image_batch(depths, dev, "track.track", max_images=MAX_FRAMES, max_dim=fuse.MAX_IMAGE)
+    B, H, W = d.shape
+    m = None if masks is None else hostargs.mask_batch(masks, d, dev, "track.track", same_shape=True)
+    P = hostargs.tensor(poses, torch.float64, dev).reshape(-1, 12).clone()
+    if P.shape[0] != B:
+        raise ValueError("track.track: %d poses for %d frames" % (P.shape[0], B))
+    iters, stride = int(iters), int(stride)
+    if iters < 0 or stride < 1 or int(min_weight) < 1:
+        raise ValueError("track.track: iters >= 0, stride >= 1 and min_weight >= 1")
+    d0, d1 = (GATE_START * volume.trunc, volume.voxel) if gate is None else gate
+    dk = gates(iters, d0, d1) if iters else np.zeros((0,), dtype=np.float32)
+    stats = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+    L = _lib.load()
+    ws = _WS.get(hostargs.stream_key(dev), int(L.cppf_tsdf_track_workspace_bytes(B, H, W, stride)), dev)
+    nx, ny, nz = volume.dims
+    _lib.check(L.cppf_tsdf_track(B, ops._p(d), ops._p(m), H, W, hostargs.camera4(K), C.c_float(pixel_offset), stride,
+                                 ops._p(volume.acc), ops._p(volume.wsum), fuse._host3(volume.origin), C.c_float(volume.voxel), nx, ny,
+                                 nz, C.c_float(volume.trunc), int(min_weight), iters, dk.ctypes.data_as(C.c_void_p), ops._p(P),
+                                 ops._p(stats), ops._p(ws), ws.numel(), ops._stream()), "cppf_tsdf_track")
+    return P, stats
+
+
+def box_corners(box):
+    """float64 [8,3]: the corners of the box [2,3] = (lo, hi)."""
+    box = np.asarray(box, dtype=np.float64).reshape(2, 3)
+    return np.array([[box[(k >> a) & 1, a] for a in range(3)] for k in range(8)])
+
+
+def max_step(poses, corners):
+    """The largest distance, in the camera frame, that a corner moves between two consecutive poses [V,12]: how far the object's
+    surface moved from one frame to the next, the length to hold against trunc."""
+    P = np.asarray(poses, dtype=np.float64).reshape(-1, 3, 4)
+    x = np.einsum("vij,kj->vki", P[:, :, :3], corners) + P[:, None, :, 3]
+    return float(np.linalg.norm(x[1:] - x[:-1], axis=2).max()) if len(P) > 1 else 0.0
+
+
+def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, stride=1, sweeps=1, gate=None, pixel_offset=0.0,
+            min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, dev=None, track_fn=None, integrate_fn=None):
+    """A volume from a sequence of which only the first frame's pose is known: (volume, poses float64 [V,12] on the host, report).
+    The volume is Volume.around the first frame at pose0, padded by extent (+ trunc + voxel) on every side: the first frame shows
+    one side only, so extent defaults to the longest side of the first frame's box.  Frame 0 is integrated at pose0; every
+    later frame is tracked from the previous frame's result and integrated at its own.  Then `sweeps` times: frames 1.. are
+    tracked in ONE batched call against the finished volume, each from its own pose, and all frames are integrated into a fresh
+    volume (frame 0 stays at pose0: it fixes the object's frame).
+    report: dict(frames: per frame dict(inliers, rms, inlier_share, moved, lost), lost: how many, max_step: the largest motion
+    of the first frame's box corners between consecutive estimates, metres, trunc, voxel, dims, sweeps, seconds).  lost =
+    inlier_share < min_inlier_share; max_step above trunc means the next surface may have lain outside the band that has a
+    gradient.  track_fn / integrate_fn stand for track / fuse.integrate (tests/test_track.py passes the
+    NumPy restatements and dev="cpu")."""
+    track_fn = track if track_fn is None else track_fn
+    integrate_fn = fuse.integrate if integrate_fn is None else integrate_fn
+    dev = ops._dev() if dev is None else torch.device(dev)
+    t0 = time.perf_counter()
+    d = hostargs.image_batch(depths, dev, "track.onboard", max_dim=fuse.MAX_IMAGE)
+    V = d.shape[0]
+    m = None if masks is None else hostargs.mask_batch(masks, d, dev, "track.onboard", same_shape=True)
+    pose0 = np.asarray(pose0, dtype=np.float64).reshape(1, 12)
+    sweeps = int(sweeps)
+    if sweeps < 0:
+        raise ValueError("track.onboard: sweeps >= 0")
+
+    def sl(x, a, b):
+        return None if x is None else x[a:b]
+    box = fuse.Volume.bounds(d[:1], sl(m, 0, 1), pose0, K, pixel_offset, dev)
+    extent = float((box[1] - box[0]).max()) if extent is None else float(extent)
+    voxel = float(np.float32(voxel))
+    trunc = float(np.float32(fuse.TRUNC_VOXELS * voxel if trunc is None else trunc))
+    volume = fuse.Volume.around(d[:1], sl(m, 0, 1), pose0, K, voxel, extent + trunc + voxel, trunc, pixel_offset, dev)
+    kw = dict(iters=iters, gate=gate, stride=stride, pixel_offset=pixel_offset, min_weight=min_weight)
+    P = torch.zeros((V, 12), dtype=torch.float64, device=dev)
+    S = torch.zeros((V, 4), dtype=torch.float32, device=dev)
+    P[0] = torch.from_numpy(pose0[0]).to(dev)
+    integrate_fn(volume, d[:1], P[:1], K, sl(m, 0, 1), pixel_offset, znear)
+    for v in range(1, V):
+        p, s = track_fn(volume, d[v:v + 1], K, P[v - 1:v], sl(m, v, v + 1), **kw)
+        P[v], S[v] = p.reshape(12).to(dev), s.reshape(4).to(dev)
+        integrate_fn(volume, d[v:v + 1], P[v:v + 1], K, sl(m, v, v + 1), pixel_offset, znear)
+    for _ in range(sweeps if V > 1 else 0):
+        p, s = track_fn(volume, d[1:], K, P[1:], sl(m, 1, V), **kw)
+        P[1:], S[1:] = p.reshape(-1, 12).to(dev), s.reshape(-1, 4).to(dev)
+        volume = fuse.Volume(volume.origin, voxel, volume.dims, trunc, dev)
+        integrate_fn(volume, d, P, K, m, pixel_offset, znear)
+    poses, stats = P.cpu().numpy(), S.cpu().numpy().astype(np.float64)
+    frames = [dict(inliers=int(s[0]), rms=float(s[1]), inlier_share=float(s[2]), moved=int(s[3]),
+                   lost=bool(v > 0 and s[2] < min_inlier_share)) for v, s in enumerate(stats)]
+    report = dict(frames=frames, lost=sum(f["lost"] for f in frames), max_step=max_step(poses, box_corners(box)), trunc=trunc,
+                  voxel=voxel, dims=list(volume.dims), sweeps=sweeps, seconds=time.perf_counter() - t0)
+    return volume, poses, report
+
+
+def pose_differences(poses, recorded):
+    """Per frame (rotation difference in degrees, translation difference in metres) of poses [V,12] against recorded ones; None
+    where the recorded pose is not finite (the folder had none)."""
+    out = []
+    for p, g in zip(np.asarray(poses, dtype=np.float64).reshape(-1, 3, 4), np.asarray(recorded, dtype=np.float64).reshape(-1, 3, 4)):
+        if not np.isfinite(g).all():
+            out.append(None)
+            continue
+        c = np.clip((np.trace(p[:, :3].T @ g[:, :3]) - 1) / 2, -1, 1)
+        out.append(dict(rotation_deg=float(np.degrees(np.arccos(c))), translation_m=float(np.linalg.norm(p[:, 3] - g[:, 3]))))
+    return out
+
+
+def onboard_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
+                  simplify_cell=None, iters=10, stride=1, sweeps=1, extent=None):
+    """fuse.fuse_scene for a folder of which only the first image's pose is used: (mesh in metres, report); the report gains
+    `track` (onboard's report, and per frame `recorded`: the difference to the pose the folder has for it, where it has one --
+    recorded, not judged)."""
+    batches = fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=True)
+    if len(batches) != 1:
+        raise fuse.ViewsError("%s: --track takes images of one size and camera matrix, not %d kinds" % (views_dir, len(batches)))
+    b = batches[0]
+    t0 = time.perf_counter()
+    volume, poses, rep = onboard(b["depths"], b["masks"], b["K"], b["poses"][0], voxel, extent, trunc, iters, stride, sweeps,
+                                 pixel_offset=pixel_offset, min_weight=min_weight)
+    t1 = fuse._sync(volume.device)
+    mesh = fuse.extract(volume, min_weight)
+    t2 = fuse._sync(volume.device)
+    for f, im, diff in zip(rep["frames"], b["im_ids"], pose_differences(poses, b["poses"])):
+        f["im_id"], f["recorded"] = int(im), diff
+    mesh, report = fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell)
+    return mesh, dict(report, track=rep)

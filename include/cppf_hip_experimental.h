@@ -14,7 +14,9 @@
  *   - the oriented-box IoU of the NOCS scorer (cppf2_amd/box_iou.py): opt-in and new;
  *   - depth-view fusion into a signed distance volume and its surface mesh (cppf2_amd/fuse.py): new;
  *   - mesh simplification by vertex clustering with quadric representatives (cppf2_amd/simplify.py):
- *     opt-in and new.
+ *     opt-in and new;
+ *   - depth frames tracked against the fused volume, for sequences with one known pose (cppf2_amd/track.py, DESIGN.md
+ *     section 30): opt-in and new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -276,6 +278,33 @@ int cppf_cluster_keys(const float* verts, int n, const double* h_origin, float c
 int cppf_cluster_quadrics(const float* verts, int n, const int32_t* faces, int nf, const int32_t* corners, int64_t m,
                           const int64_t* seg_off, const int64_t* keys, int nc, const double* h_origin, float cell, double lam,
                           float* pos, void* stream);
+
+/* ---- depth frames tracked against the signed distance volume (the reference has no such step) ----
+ * cppf_tsdf_track: B frames (0 <= B <= 65535; 0 launches nothing) aligned to the volume acc / wsum of cppf_tsdf_integrate
+ * (described above; h_origin, voxel, nx, ny, nz, trunc and h_K = (fx, fy, cx, cy) as there, fx, fy > 0) by point-to-plane
+ * steps on the volume's trilinear value and gradient (Bylow et al., RSS 2013): no mesh, no raycast, no search.  depth float32
+ * [B,H,W] (metres; 0, negative, NaN and infinite = no reading), masks uint8 [B,H,W] or NULL (non-zero = use the pixel),
+ * 1 <= H, W <= 16384; the pixels (r, c) with r and c multiples of stride (>= 1) take part; pixel (r, c) lies on the ray
+ * through (c + pixel_offset, r + pixel_offset), the convention cppf_tsdf_integrate inverts.  poses: float64 [B,12] on the
+ * DEVICE (row-major 3x4, model -> OpenCV camera), each frame's start, updated in place.  iters (>= 0; 0 launches nothing)
+ * iterations of two launches each, no host synchronisation; h_dk: float32 [iters] on the HOST, iteration k's inlier gate in
+ * metres on |trunc * phi|, each positive and finite.  A pixel takes part when its point falls in a cell whose eight nodes
+ * have wsum >= min_weight (>= 1) and the gradient there is not zero.  The step is cppf_icp_refine's minimum-norm Gauss-Newton
+ * step (unobserved directions do not move); fewer than 6 inliers, rank 0 or a zero or non-finite step leave the pose's bytes
+ * as they are.  stats float32 [B,4]: inliers of the last iteration, sqrt(sum e^2 / inliers), inliers / gated pixels (pixels
+ * inside the mask with a reading), iterations that moved the pose; written only when iters > 0.  Deterministic: no atomics,
+ * every sum in a fixed order, so B frames in one call give the bytes of B calls of one frame.  The exact order of the
+ * operations is stated in cppf2_amd/csrc/cppf_track.hip and restated in tests/track_ref.py.
+ * workspace: cppf_tsdf_track_workspace_bytes(B, H, W, stride) bytes (-1 for sizes the call refuses), 8-byte aligned.
+ * CPPF_EINVAL, before any device work, for: h_K, h_origin, acc or wsum NULL; depth, poses, stats or workspace NULL when B > 0;
+ * h_dk NULL when iters > 0; B or iters < 0; stride < 1; H or W outside 1..16384; the volume checks of cppf_tsdf_extract;
+ * min_weight < 1; trunc, fx or fy not positive and finite; a gate that is not positive and finite; a workspace that is too
+ * small.  An axis of one node is valid: no cells, no inliers, the poses keep their bytes. */
+int64_t cppf_tsdf_track_workspace_bytes(int B, int H, int W, int stride);
+int cppf_tsdf_track(int B, const float* depth, const uint8_t* masks, int H, int W, const double* h_K, float pixel_offset,
+                    int stride, const float* acc, const int32_t* wsum, const double* h_origin, float voxel, int nx, int ny, int nz,
+                    float trunc, int min_weight, int iters, const float* h_dk, double* poses, float* stats, void* workspace,
+                    int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
