@@ -53,6 +53,7 @@
 //   The result is a pure function of the integer sizes and labels.  A mask whose img_idx lies outside [0, I): stats
 //   (0, 0, 0, 0), rank 255, seg -1.
 #include "cppf_common.h"
+#include "cppf_cc.h"
 
 #define MASK_THREADS 256
 #define MASK_MAX_DIM 8192          // H, W: H * W <= 2^26 fits int32 with room for c * H + r
@@ -138,28 +139,7 @@ __global__ __launch_bounds__(MASK_THREADS) void rle_decode_kernel(const int32_t*
 }
 
 // ---- components ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cc_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// the root of x's tree as far as this lane sees it; x's own word is lowered to it
-__device__ __forceinline__ int cc_find(int* __restrict__ L, int x) {
-  int r = x, p;
-  while ((p = cc_load(L + r)) != r) r = p;
-  if (r != x) atomicMin(L + x, r);
-  return r;
-}
-
-__device__ __forceinline__ void cc_union(int* __restrict__ L, int a, int b) {
-  a = cc_find(L, a);
-  b = cc_find(L, b);
-  while (a != b) {
-    if (a < b) { const int t = a; a = b; b = t; }         // a > b: lower a's word to b
-    const int old = atomicMin(L + a, b);
-    if (old == a) break;                                  // a was a root: linked
-    a = cc_find(L, old);                                  // it was not: what it held (< a) still has to meet b
-    b = cc_find(L, b);
-  }
-}
-
+// cc_load, cc_find, cc_union: cppf_cc.h (shared with cppf_close.hip)
 __global__ __launch_bounds__(MASK_THREADS) void cc_init_kernel(const uint8_t* __restrict__ masks, const float* __restrict__ depths,
                                                                int I, const int32_t* __restrict__ img_idx, int HW,
                                                                int* __restrict__ labels, int* __restrict__ sizes,

@@ -9,13 +9,18 @@ custom-object path starts from a mesh (train_custom.ipynb).
     mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002)
     python -m cppf2_amd.fuse --views <bop scene dir> --obj-id 15 --voxel 0.002 --out obj_000015.ply [--simplify-cell 0.006]
     python -m cppf2_amd.fuse --views <dir> --track --voxel 0.004 --out obj.ply          # only the first image's pose is used
+    closed, report = close(vol, plane=(a, b, c, d))                 # a new Volume: enclosed unseen space filled, cut at the plane
+    mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002, close=True, support_plane=(a, b, c, d))
+    python -m cppf2_amd.fuse --views <dir> --voxel 0.002 --out obj.ply --close --support-plane auto [--support-lift 0.001]
 
 The surface has one or two triangles per voxel it crosses; simplify_cell / --simplify-cell hands it to cppf2_amd.simplify
  before it is returned or written.
 
 The kernels are cppf_tsdf_integrate and cppf_tsdf_extract (include/cppf_hip_experimental.h; the definitions are stated in
 cppf2_amd/csrc/cppf_fuse.hip and restated in tests/fuse_ref.py).  Not done: no weighting by viewing angle or distance, no
-colour, no hole filling (what no view saw stays open: mesh.boundary_edges counts it).  The poses are trusted as given; --track
+colour.  What no view saw stays open (mesh.boundary_edges counts it) unless close / --close decides it (cppf_tsdf_close,
+cppf2_amd/csrc/cppf_close.hip): unseen space that is enclosed becomes inside, the support plane cuts the
+solid off where the object stands, and unseen space that reaches the volume's border stays open.  The poses are trusted as given; --track
 (cppf2_amd/track.py) is for a sequence of which only the first pose is known: every later frame is aligned
 to the volume built so far before it is integrated (cppf_tsdf_track).  No loop closure, no bundle adjustment.
 """
@@ -41,6 +46,7 @@ MAX_IMAGE = 16384                # H and W
 INITIAL_CAPACITY = 1 << 16       # triangles of the first cppf_tsdf_extract call
 
 _WS = hostargs.ScratchCache("cppf_tsdf_extract_workspace_bytes", CppfError)
+_CLOSE_WS = hostargs.ScratchCache("cppf_tsdf_close_workspace_bytes", CppfError)
 
 
 def _host3(x):
@@ -216,10 +222,75 @@ def extract(volume, min_weight=1, weld=True, drop_degenerate=True):
     return mesh
 
 
+def unit_plane(plane, lift=0.0):
+    """float64 [4]: the plane (a, b, c, d), a x + b y + c z + d = 0 with the object on the positive side, its normal scaled to
+    unit length in float64 and the plane moved `lift` metres towards the object."""
+    p = np.array(plane, dtype=np.float64).reshape(-1)
+    lift = float(lift)
+    if p.size != 4 or not np.isfinite(p).all():
+        raise ValueError("fuse: a plane is four finite numbers a, b, c, d, not %r" % (plane,))
+    n = float(np.linalg.norm(p[:3]))
+    if not (n > 0 and np.isfinite(n)):
+        raise ValueError("fuse: the plane's normal (a, b, c) is zero")
+    if not (lift >= 0 and np.isfinite(lift)):
+        raise ValueError("fuse: the lift is a length in metres >= 0, not %r" % lift)
+    p = p / n
+    p[3] -= lift
+    return p
+
+
+def plane_to_object(plane_cam, pose):
+    """float64 [4]: a plane (n_c, d_c) of the camera frame in the object's frame of pose [12] or [3,4] (model -> camera):
+    n_o = R^T n_c, d_o = n_c . t + d_c."""
+    p = np.asarray(plane_cam, dtype=np.float64).reshape(4)
+    P = np.asarray(pose, dtype=np.float64).reshape(3, 4)
+    return np.concatenate([P[:, :3].T @ p[:3], [p[:3] @ P[:, 3] + p[3]]])
+
+
+def close(volume, plane=None, min_weight=1):
+    """cppf_tsdf_close: (closed Volume, report).  The new Volume has the geometry and `views` of `volume`,
+    wsum 1 at every decided node (extract it with min_weight=1) and .state, a uint8 device tensor [nx,ny,nz]: 0 known, 1
+    enclosed and never seen (filled as inside), 2 unseen and below the plane (outside), 3 unseen and connected to the volume's
+    border (left unknown).  plane: (a, b, c, d) in the object's frame, metres, the object on the positive side (segment.fit_plane's
+    orientation), normalised here in float64; None: no plane.  report: dict(known, filled, below, open, open_share, plane).
+    `volume` is not written."""
+    dev = _device_of(volume)
+    if int(min_weight) < 1:
+        raise ValueError("fuse.close: min_weight >= 1")
+    p = None if plane is None else unit_plane(plane)
+    out = Volume(volume.origin, volume.voxel, volume.dims, volume.trunc, dev)
+    out.views = volume.views
+    out.state = torch.empty(volume.dims, dtype=torch.uint8, device=dev)
+    stats = torch.empty((4,), dtype=torch.int64, device=dev)
+    nx, ny, nz = volume.dims
+    L = _lib.load()
+    ws = _CLOSE_WS.get(hostargs.stream_key(dev), int(L.cppf_tsdf_close_workspace_bytes(nx, ny, nz)), dev)
+    _lib.check(L.cppf_tsdf_close(ops._p(volume.acc), ops._p(volume.wsum), _host3(volume.origin), C.c_float(volume.voxel), nx, ny, nz,
+                                 C.c_float(volume.trunc), int(min_weight), None if p is None else (C.c_double * 4)(*p),
+                                 ops._p(out.acc), ops._p(out.wsum), ops._p(out.state), ops._p(stats), ops._p(ws), ws.numel(),
+                                 ops._stream()), "cppf_tsdf_close")
+    known, filled, below, opened = (int(x) for x in stats.cpu().tolist())
+    return out, dict(known=known, filled=filled, below=below, open=opened, open_share=opened / float(nx * ny * nz),
+                     plane=None if p is None else [float(x) for x in p])
+
+
 def _sync(dev):
     if torch.device(dev).type == "cuda":
         torch.cuda.synchronize(dev)
     return time.perf_counter()
+
+
+def _surface(volume, min_weight, close_it, support_plane, support_lift):
+    """(mesh, close's report or None): the volume's surface; with close_it the surface of close(volume, the plane lifted by
+    support_lift (default: half a voxel)) instead."""
+    if not close_it:
+        if support_plane is not None or support_lift is not None:
+            raise ValueError("fuse: support_plane and support_lift belong to close=True")
+        return extract(volume, min_weight), None
+    lift = 0.5 * volume.voxel if support_lift is None else support_lift
+    plane = None if support_plane is None else unit_plane(support_plane, lift)
+    closed, report = close(volume, plane, min_weight)
+    return extract(closed, 1), dict(report, lift=None if plane is None else float(lift))
 
 
 def _report(volume, mesh, t_volume, t_integrate, t_extract):
@@ -228,32 +299,38 @@ def _report(volume, mesh, t_volume, t_integrate, t_extract):
                 unknown_share=volume.unknown_share, seconds=dict(volume=t_volume, integrate=t_integrate, extract=t_extract))
 
 
-def _finish(volume, mesh, seconds, simplify_cell):
+def _finish(volume, mesh, seconds, simplify_cell, closed=None):
     """(mesh, report) of the mesh extracted from a volume.  With simplify_cell the mesh goes through simplify.cluster first, the
-    cells on the voxel lattice (the origin is the volume's), and the report gains `simplify`, cluster's own report."""
+    cells on the voxel lattice (the origin is the volume's), and the report gains `simplify`, cluster's own report.  closed:
+    _surface's report of the close stage, the report's `close` (None: no such stage, no such key)."""
+    extra = {} if closed is None else dict(close=closed)
     if simplify_cell is None:
-        return mesh, _report(volume, mesh, *seconds)
+        return mesh, dict(_report(volume, mesh, *seconds), **extra)
     from . import simplify
     mesh, simplified = simplify.cluster(mesh, simplify_cell, origin=volume.origin)
-    return mesh, dict(_report(volume, mesh, *seconds), simplify=simplified)
+    return mesh, dict(_report(volume, mesh, *seconds), simplify=simplified, **extra)
 
 
 def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weight=1, pixel_offset=0.0, znear=render.ZNEAR,
-               volume=None, simplify_cell=None):
+               volume=None, simplify_cell=None, close=False, support_plane=None, support_lift=None):
     """Both stages on one batch of views: (mesh, report).  `volume`: an existing Volume to add to (else Volume.around the views).
     report: dict(views, dims, voxel, trunc, triangles, vertices, boundary_edges, unknown_share (nodes no view observed),
     seconds: dict(volume, integrate, extract)).  simplify_cell (metres; None: no such stage): the welded mesh goes through
     simplify.cluster with cells of that edge on the voxel lattice; triangles, vertices and boundary_edges then describe the
-    simplified mesh and report["simplify"] is cluster's report (triangles_in: what was extracted)."""
+    simplified mesh and report["simplify"] is cluster's report (triangles_in: what was extracted).
+    close=True: the volume goes through close() before it is extracted (the seconds count it under extract); support_plane (a, b,
+    c, d) as close()'s plane (None: none), moved support_lift metres towards the object first (default: half a voxel; the mesh's
+    bottom then lies that far above the plane).  report["close"] is close()'s report plus `lift`, and triangles, vertices and
+    boundary_edges describe the closed mesh."""
     t0 = time.perf_counter()
     if volume is None:
         volume = Volume.around(depths, masks, poses, K, voxel, margin, trunc, pixel_offset)
     t1 = _sync(volume.device)
     integrate(volume, depths, poses, K, masks, pixel_offset, znear)
     t2 = _sync(volume.device)
-    mesh = extract(volume, min_weight)
+    mesh, closed = _surface(volume, min_weight, close, support_plane, support_lift)
     t3 = _sync(volume.device)
-    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell)
+    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -323,11 +400,38 @@ def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True, first_p
     return out
 
 
+def auto_support_plane(batch, tau, pixel_offset=0.0, views_dir="the folder"):
+    """The support plane of a read_views batch's first view in the object's frame (metres): segment.fit_plane (seed 0) on the
+    whole depth image, taken over by that view's pose.  tau: the fit's inlier distance, the same statement of the table's noise
+    as the lift.  pixel_offset as integrate's: the fit takes pixel (r, c) for the ray through (c, r), so the principal point
+    moves by the offset.  ViewsError when the fit finds no plane."""
+    from . import segment
+    K = np.array(batch["K"], dtype=np.float64).reshape(3, 3)
+    K[:2, 2] -= float(pixel_offset)
+    plane, stats = segment.fit_plane(batch["depths"][:1], K, 0, tau=tau)
+    plane, winner = plane.reshape(4).cpu().numpy().astype(np.float64), int(stats.reshape(4)[0])
+    if winner < 0 or not np.isfinite(plane).all() or not np.linalg.norm(plane[:3]) > 0:
+        raise ViewsError("%s: --support-plane auto found no plane in the first view's depth image (image %s); give the plane as "
+                         "a,b,c,d" % (views_dir, batch["im_ids"][0]))
+    return plane_to_object(plane, batch["poses"][0])
+
+
+def _scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, views_dir):
+    """support_plane as given, or for "auto" the first view's fitted plane (inliers within the lift; half a voxel if that is
+    None or 0)."""
+    if not (isinstance(support_plane, str) and support_plane == "auto"):
+        return support_plane
+    tau = support_lift if support_lift else 0.5 * float(np.float32(voxel))
+    return auto_support_plane(batches[0], tau, pixel_offset, views_dir)
+
+
 def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
-               simplify_cell=None):
-    """read_views fused into one volume (one integrate call per image size and K): (mesh in metres, report).  simplify_cell: as
-    fuse_views'."""
+               simplify_cell=None, close=False, support_plane=None, support_lift=None):
+    """read_views fused into one volume (one integrate call per image size and K): (mesh in metres, report).  simplify_cell, close,
+    support_plane and support_lift: as fuse_views'; support_plane "auto": auto_support_plane of the first view, found before
+    anything is fused."""
     batches = read_views(views_dir, obj_id, mesh_scale, use_masks)
+    support_plane = _scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, views_dir)
     t0 = time.perf_counter()
     boxes = np.stack([Volume.bounds(b["depths"], b["masks"], b["poses"], b["K"], pixel_offset) for b in batches])
     voxel = float(np.float32(voxel))
@@ -338,9 +442,19 @@ def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_mask
     for b in batches:
         integrate(volume, b["depths"], b["poses"], b["K"], b["masks"], pixel_offset)
     t2 = _sync(volume.device)
-    mesh = extract(volume, min_weight)
+    mesh, closed = _surface(volume, min_weight, close, support_plane, support_lift)
     t3 = _sync(volume.device)
-    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell)
+    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed)
+
+
+def _plane_argument(text):
+    """--support-plane: "auto" or the unit plane of "a,b,c,d"."""
+    if text == "auto":
+        return text
+    try:
+        return unit_plane([float(x) for x in text.split(",")])
+    except ValueError as e:
+        raise argparse.ArgumentTypeError("'auto' or four numbers a,b,c,d with a normal that is not zero (%s)" % e) from None
 
 
 def main(argv=None):
@@ -362,6 +476,15 @@ def main(argv=None):
     ap.add_argument("--track-sweeps", type=int, default=1, help="--track: passes that re-track all frames against the finished volume")
     ap.add_argument("--track-extent", type=float, default=None,
                     help="--track: metres of volume beyond the first image's box (default: that box's longest side)")
+    ap.add_argument("--close", action="store_true",
+                    help="close the mesh: unseen space that is enclosed becomes inside; unseen space that reaches the volume's border stays open")
+    ap.add_argument("--support-plane", type=_plane_argument, default=None,
+                    help="--close: the plane the object stands on, a,b,c,d with a x + b y + c z + d = 0 in the object's frame, "
+                         "lengths in metres, the object on the positive side; 'auto': fitted to the first image's whole depth "
+                         "image (inliers within --support-lift) and taken into the object's frame by that image's pose")
+    ap.add_argument("--support-lift", type=float, default=None,
+                    help="--close: metres the plane is moved towards the object before the volume is cut, the statement of the "
+                         "sensor's noise on the table (default: half a voxel); the mesh's bottom then lies this far above the table")
     ap.add_argument("--report", default=None, help="write the report as JSON here")
     ap.add_argument("--out", required=True, help="the .ply to write, in model units")
     a = ap.parse_args(argv)
@@ -381,14 +504,22 @@ def main(argv=None):
         ap.error("--track-iters and --track-stride are at least 1, --track-sweeps at least 0")
     if a.track_extent is not None and not (a.track_extent >= 0 and np.isfinite(a.track_extent)):
         ap.error("--track-extent is a length in metres")
+    if not a.close and (a.support_plane is not None or a.support_lift is not None):
+        ap.error("--support-plane and --support-lift belong to --close")
+    if a.support_lift is not None and not (a.support_lift >= 0 and np.isfinite(a.support_lift)):
+        ap.error("--support-lift is a length in metres, 0 or more")
+    if a.support_lift is not None and a.support_plane is None:
+        ap.error("--support-lift moves the --support-plane; there is none")
+    closing = dict(close=a.close, support_plane=a.support_plane, support_lift=a.support_lift)
     from . import bop_data
     if a.track:
         from . import track
         mesh, report = track.onboard_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset,
-                                           a.mesh_scale, a.simplify_cell, a.track_iters, a.track_stride, a.track_sweeps, a.track_extent)
+                                           a.mesh_scale, a.simplify_cell, a.track_iters, a.track_stride, a.track_sweeps, a.track_extent,
+                                           **closing)
     else:
         mesh, report = fuse_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset, a.mesh_scale,
-                                  a.simplify_cell)
+                                  a.simplify_cell, **closing)
     if not mesh.faces.shape[0]:
         raise CppfError("fuse: the volume has no surface (no node behind a reading); check the poses, --mesh-scale and --pixel-offset")
     bop_data.write_ply(a.out, mesh.verts / a.mesh_scale, mesh.faces)

@@ -154,21 +154,23 @@ def pose_differences(poses, recorded):
 
 
 def onboard_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
-                  simplify_cell=None, iters=10, stride=1, sweeps=1, extent=None):
+                  simplify_cell=None, iters=10, stride=1, sweeps=1, extent=None, close=False, support_plane=None, support_lift=None):
     """fuse.fuse_scene for a folder of which only the first image's pose is used: (mesh in metres, report); the report gains
     `track` (onboard's report, and per frame `recorded`: the difference to the pose the folder has for it, where it has one --
-    recorded, not judged)."""
+    recorded, not judged).  close, support_plane, support_lift: as fuse.fuse_scene's (the first image's pose, the one that is
+    known, takes an "auto" plane into the object's frame)."""
     batches = fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=True)
     if len(batches) != 1:
         raise fuse.ViewsError("%s: --track takes images of one size and camera matrix, not %d kinds" % (views_dir, len(batches)))
     b = batches[0]
+    support_plane = fuse._scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, views_dir)
     t0 = time.perf_counter()
     volume, poses, rep = onboard(b["depths"], b["masks"], b["K"], b["poses"][0], voxel, extent, trunc, iters, stride, sweeps,
                                  pixel_offset=pixel_offset, min_weight=min_weight)
     t1 = fuse._sync(volume.device)
-    mesh = fuse.extract(volume, min_weight)
+    mesh, closed = fuse._surface(volume, min_weight, close, support_plane, support_lift)
     t2 = fuse._sync(volume.device)
     for f, im, diff in zip(rep["frames"], b["im_ids"], pose_differences(poses, b["poses"])):
         f["im_id"], f["recorded"] = int(im), diff
-    mesh, report = fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell)
+    mesh, report = fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed)
     return mesh, dict(report, track=rep)

@@ -306,6 +306,30 @@ int cppf_tsdf_track(int B, const float* depth, const uint8_t* masks, int H, int 
                     float trunc, int min_weight, int iters, const float* h_dk, double* poses, float* stats, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* ---- a fused volume closed where no view saw it: support-plane bottom, enclosed unseen space (the reference has no such step) ----
+ * cppf_tsdf_close: reads the volume acc / wsum of cppf_tsdf_integrate (described above; h_origin, voxel, nx, ny, nz, trunc as
+ * there) and writes a NEW volume acc_out float32 / wsum_out int32 [nx,ny,nz], state uint8 [nx,ny,nz] and stats int64 [4] (the
+ * nodes per state), all on the device.  h_plane: double[4] = (a, b, c, d) on the HOST or NULL: the support plane a x + b y +
+ * c z + d = 0 in the object's frame, metres, unit normal (|a^2 + b^2 + c^2 - 1| <= 1e-3), the object on the positive side;
+ * rounded to float32 once.  Per node, float32: known = wsum >= min_weight (>= 1), t = acc / (float)wsum for a known node and -1
+ * otherwise; with a plane h = ((a x + b y) + c z) + d at the node, b = (-h) / trunc clamped to [-1, 1], below = h <= 0 (without:
+ * b = -1, below = false).  The nodes that are neither known nor below are joined by 6-connectivity; such a component is open
+ * iff it holds a node on a face of the volume.  An open node: acc_out = 0, wsum_out = 0, state 3 (still unknown to
+ * cppf_tsdf_extract).  Every other node: acc_out = (b > t) ? b : t, wsum_out = 1, state 0 (known), 1 (enclosed and never seen:
+ * inside, sharpened to the plane within trunc of it) or 2 (unseen and below the plane: outside) -- the solid (observed, or
+ * enclosed and never seen) intersected with the half-space above the plane.  cppf_tsdf_extract(acc_out, wsum_out,
+ * min_weight = 1) then sees acc_out bit for bit.  The outputs depend on component membership only: two calls give the same
+ * bytes.  The stats are cleared, then four launches; no host synchronisation.  The exact order of the operations is stated in
+ * cppf2_amd/csrc/cppf_close.hip and restated in tests/close_ref.py.
+ * workspace: cppf_tsdf_close_workspace_bytes(nx, ny, nz) bytes (-1 for sizes the call refuses), 8-byte aligned.
+ * CPPF_EINVAL, before any device work, for: the volume checks of cppf_tsdf_extract; a NULL pointer other than h_plane; an
+ * output (the workspace included) that overlaps acc, wsum or another output; a plane that is not finite or whose normal is not
+ * a unit vector; trunc not positive and finite; min_weight < 1; a workspace that is too small. */
+int64_t cppf_tsdf_close_workspace_bytes(int nx, int ny, int nz);
+int cppf_tsdf_close(const float* acc, const int32_t* wsum, const double* h_origin, float voxel, int nx, int ny, int nz, float trunc,
+                    int min_weight, const double* h_plane, float* acc_out, int32_t* wsum_out, uint8_t* state, int64_t* stats,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
