@@ -14,10 +14,14 @@
 
 extern thread_local char g_cppf_err[256];
 
+// CPPF_FN: the name the messages below begin with.  A host function that several entry points share redefines it to the
+// name its caller passes.
+#define CPPF_FN __func__
+
 #define CPPF_CHECK_ARG(cond)                                                                  \
   do {                                                                                        \
     if (!(cond)) {                                                                            \
-      snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: invalid argument: %s", __func__, #cond);   \
+      snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: invalid argument: %s", CPPF_FN, #cond);    \
       return CPPF_EINVAL;                                                                     \
     }                                                                                         \
   } while (0)
@@ -26,7 +30,7 @@ extern thread_local char g_cppf_err[256];
   do {                                                                                        \
     hipError_t e_ = (call);                                                                   \
     if (e_ != hipSuccess) {                                                                   \
-      snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: %s failed: %s", __func__, #call,           \
+      snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: %s failed: %s", CPPF_FN, #call,            \
                hipGetErrorString(e_));                                                        \
       return CPPF_EHIP;                                                                       \
     }                                                                                         \
@@ -36,7 +40,7 @@ extern thread_local char g_cppf_err[256];
   do {                                                                                        \
     hipError_t e_ = hipGetLastError();                                                        \
     if (e_ != hipSuccess) {                                                                   \
-      snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: kernel launch failed: %s", __func__,       \
+      snprintf(g_cppf_err, sizeof(g_cppf_err), "%s: kernel launch failed: %s", CPPF_FN,        \
                hipGetErrorString(e_));                                                        \
       return CPPF_EHIP;                                                                       \
     }                                                                                         \

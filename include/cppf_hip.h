@@ -582,7 +582,7 @@ int cppf_scene_explain(int I, int H, int W, const float* depth, const uint8_t* r
                        int64_t* gain, int64_t* net, int64_t* stat, uint8_t* labels, int64_t* summary, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
-/* cppf_scene_explain_wide: cppf_scene_explain with up to 512 candidates per image (cppf2_amd/csrc/cppf_scene_wide.hip).  The same
+/* cppf_scene_explain_wide: cppf_scene_explain with up to 512 candidates per image (cppf2_amd/csrc/cppf_scene.hip: the same bits kernel template and host code, the round kernel over word planes).  The same
  * definition and the same outputs, byte for byte (for images of at most 64 candidates: cppf_scene_explain's own); the key's
  * candidate index goes up to 511.  max_candidates (1 .. 512): the largest per-image candidate count of the call; it fixes
  * G = ceil(max_candidates / 64) planes of one 64-bit word per pixel.  workspace: cppf_scene_explain_wide_workspace_bytes(I, H, W,
