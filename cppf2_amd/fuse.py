@@ -9,6 +9,7 @@ custom-object path starts from a mesh (train_custom.ipynb).
     mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002)
     python -m cppf2_amd.fuse --views <bop scene dir> --obj-id 15 --voxel 0.002 --out obj_000015.ply [--simplify-cell 0.006]
     python -m cppf2_amd.fuse --views <dir> --track --voxel 0.004 --out obj.ply          # only the first image's pose is used
+    python -m cppf2_amd.fuse --views <dir> --join <dir of the object turned over> --voxel 0.004 --out obj.ply    # section 32
     closed, report = close(vol, plane=(a, b, c, d))                 # a new Volume: enclosed unseen space filled, cut at the plane
     mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002, close=True, support_plane=(a, b, c, d))
     python -m cppf2_amd.fuse --views <dir> --voxel 0.002 --out obj.ply --close --support-plane auto [--support-lift 0.001]
@@ -340,12 +341,13 @@ class ViewsError(ValueError):
     """A --views folder that cannot be read as one BOP-format scene."""
 
 
-def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True, first_pose_only=False):
+def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True, first_pose_only=False, no_poses=False):
     """The views of one object in a BOP-format scene folder: scene_camera.json (cam_K, depth_scale), scene_gt.json (cam_R_m2c,
     cam_t_m2c in model units; read directly: no model file has to exist), depth/%06d.png and mask_visib/%06d_%06d.png.  obj_id:
     the object (None: the scene's only one).  Returns a list of batches dict(K, depths [V,H,W] float32 metres, masks [V,H,W]
     uint8 or None, poses [V,12] float32 model (metres) -> camera, im_ids), one per image size and K, in image order.
-    first_pose_only (--track): an entry after the object's first may lack cam_R_m2c / cam_t_m2c; its pose is then NaN."""
+    first_pose_only (--track): an entry after the object's first may lack cam_R_m2c / cam_t_m2c; its pose is then NaN.
+    no_poses (--join's folder): every entry may."""
     from PIL import Image
     gt_path, cam_path = os.path.join(views_dir, "scene_gt.json"), os.path.join(views_dir, "scene_camera.json")
     for p in (gt_path, cam_path):
@@ -381,7 +383,7 @@ def read_views(views_dir, obj_id=None, mesh_scale=0.001, use_masks=True, first_p
                 if mask.shape != depth.shape:
                     raise ViewsError("%s: mask %s for depth %s" % (mpath, mask.shape, depth.shape))
             K = np.asarray(cam[im]["cam_K"], dtype=np.float64).reshape(3, 3)
-            if first_pose_only and groups and not ("cam_R_m2c" in g and "cam_t_m2c" in g):
+            if (no_poses or (first_pose_only and groups)) and not ("cam_R_m2c" in g and "cam_t_m2c" in g):
                 R, t = np.full((3, 3), np.nan), np.full((3, 1), np.nan)
             else:
                 R = np.asarray(g["cam_R_m2c"], dtype=np.float64).reshape(3, 3)
@@ -476,6 +478,16 @@ def main(argv=None):
     ap.add_argument("--track-sweeps", type=int, default=1, help="--track: passes that re-track all frames against the finished volume")
     ap.add_argument("--track-extent", type=float, default=None,
                     help="--track: metres of volume beyond the first image's box (default: that box's longest side)")
+    ap.add_argument("--join", default=None, metavar="VIEWS",
+                    help="a second BOP-format scene folder of the same object, turned over, whose poses are not used: its first image "
+                         "is found against the volume of --views by an exhaustive pose search, the rest are tracked, all are fused")
+    ap.add_argument("--join-step-deg", type=float, default=15.0, help="--join: degrees between neighbours of the rotation grid")
+    ap.add_argument("--join-top", type=int, default=32, help="--join: candidates that are refined")
+    ap.add_argument("--join-coarse", type=int, default=2, help="--join: voxels of --voxel per node of the volume that is searched")
+    ap.add_argument("--join-points", type=int, default=256, help="--join: points of the first image that score a candidate")
+    ap.add_argument("--join-turned-over", action="store_true",
+                    help="--join: among the refined candidates that the volume does not contradict, keep the one that shows the most "
+                         "unseen space (for an object with symmetries, whose seen side the second folder fits as well as its own)")
     ap.add_argument("--close", action="store_true",
                     help="close the mesh: unseen space that is enclosed becomes inside; unseen space that reaches the volume's border stays open")
     ap.add_argument("--support-plane", type=_plane_argument, default=None,
@@ -504,6 +516,8 @@ def main(argv=None):
         ap.error("--track-iters and --track-stride are at least 1, --track-sweeps at least 0")
     if a.track_extent is not None and not (a.track_extent >= 0 and np.isfinite(a.track_extent)):
         ap.error("--track-extent is a length in metres")
+    if a.join is not None and not (0 < a.join_step_deg <= 180 and a.join_top >= 1 and a.join_coarse >= 1 and 1 <= a.join_points <= 2048):
+        ap.error("--join-step-deg is in (0, 180], --join-top and --join-coarse at least 1, --join-points 1 to 2048")
     if not a.close and (a.support_plane is not None or a.support_lift is not None):
         ap.error("--support-plane and --support-lift belong to --close")
     if a.support_lift is not None and not (a.support_lift >= 0 and np.isfinite(a.support_lift)):
@@ -512,7 +526,13 @@ def main(argv=None):
         ap.error("--support-lift moves the --support-plane; there is none")
     closing = dict(close=a.close, support_plane=a.support_plane, support_lift=a.support_lift)
     from . import bop_data
-    if a.track:
+    if a.join is not None:
+        from . import track
+        mesh, report = track.join_scene(a.views, a.join, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset,
+                                        a.mesh_scale, a.simplify_cell, a.track_iters, a.track_stride, a.track_sweeps if a.track else None,
+                                        a.track_extent, np.deg2rad(a.join_step_deg), a.join_top, a.join_coarse, a.join_points,
+                                        turned_over=a.join_turned_over, **closing)
+    elif a.track:
         from . import track
         mesh, report = track.onboard_scene(a.views, a.voxel, a.obj_id, a.trunc, a.min_weight, not a.no_masks, a.pixel_offset,
                                            a.mesh_scale, a.simplify_cell, a.track_iters, a.track_stride, a.track_sweeps, a.track_extent,

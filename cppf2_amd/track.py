@@ -5,6 +5,7 @@ nearest-neighbour search -- with the minimum-norm Gauss-Newton step of the ICP o
 
     poses, stats = track(volume, depths, K, poses, masks=masks)               # B frames in one call, each from its own start
     volume, poses, report = onboard(depths, masks, K, pose0, voxel=0.004)     # frame by frame: track, then integrate
+    volume, poses_b, report = join(first, second, voxel=0.004)                # a second sequence without poses (section 32)
     python -m cppf2_amd.fuse --views <dir> --track --voxel 0.004 --out obj.ply
 
 The kernel is cppf_tsdf_track (include/cppf_hip_experimental.h; the definitions are stated in cppf2_amd/csrc/cppf_track.hip and
@@ -86,6 +87,20 @@ def max_step(poses, corners):
     return float(np.linalg.norm(x[1:] - x[:-1], axis=2).max()) if len(P) > 1 else 0.0
 
 
+def _follow(volume, d, m, K, P, S, kw, pixel_offset, znear, track_fn, integrate_fn):
+    """The frame loop of onboard and join: frame 0 is integrated at P[0]; every later frame is tracked from the previous frame's
+    result (written to P[v], its stats to S[v]) and integrated at its own."""
+    dev = P.device
+
+    def sl(x, a, b):
+        return None if x is None else x[a:b]
+    integrate_fn(volume, d[:1], P[:1], K, sl(m, 0, 1), pixel_offset, znear)
+    for v in range(1, d.shape[0]):
+        p, s = track_fn(volume, d[v:v + 1], K, P[v - 1:v], sl(m, v, v + 1), **kw)
+        P[v], S[v] = p.reshape(12).to(dev), s.reshape(4).to(dev)
+        integrate_fn(volume, d[v:v + 1], P[v:v + 1], K, sl(m, v, v + 1), pixel_offset, znear)
+
+
 def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, stride=1, sweeps=1, gate=None, pixel_offset=0.0,
             min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, dev=None, track_fn=None, integrate_fn=None):
     """A volume from a sequence of which only the first frame's pose is known: (volume, poses float64 [V,12] on the host, report).
@@ -122,21 +137,84 @@ def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, s
     P = torch.zeros((V, 12), dtype=torch.float64, device=dev)
     S = torch.zeros((V, 4), dtype=torch.float32, device=dev)
     P[0] = torch.from_numpy(pose0[0]).to(dev)
-    integrate_fn(volume, d[:1], P[:1], K, sl(m, 0, 1), pixel_offset, znear)
-    for v in range(1, V):
-        p, s = track_fn(volume, d[v:v + 1], K, P[v - 1:v], sl(m, v, v + 1), **kw)
-        P[v], S[v] = p.reshape(12).to(dev), s.reshape(4).to(dev)
-        integrate_fn(volume, d[v:v + 1], P[v:v + 1], K, sl(m, v, v + 1), pixel_offset, znear)
+    _follow(volume, d, m, K, P, S, kw, pixel_offset, znear, track_fn, integrate_fn)
     for _ in range(sweeps if V > 1 else 0):
         p, s = track_fn(volume, d[1:], K, P[1:], sl(m, 1, V), **kw)
         P[1:], S[1:] = p.reshape(-1, 12).to(dev), s.reshape(-1, 4).to(dev)
         volume = fuse.Volume(volume.origin, voxel, volume.dims, trunc, dev)
         integrate_fn(volume, d, P, K, m, pixel_offset, znear)
     poses, stats = P.cpu().numpy(), S.cpu().numpy().astype(np.float64)
-    frames = [dict(inliers=int(s[0]), rms=float(s[1]), inlier_share=float(s[2]), moved=int(s[3]),
-                   lost=bool(v > 0 and s[2] < min_inlier_share)) for v, s in enumerate(stats)]
+    frames = _frame_reports(stats, min_inlier_share, first_fixed=True)
     report = dict(frames=frames, lost=sum(f["lost"] for f in frames), max_step=max_step(poses, box_corners(box)), trunc=trunc,
                   voxel=voxel, dims=list(volume.dims), sweeps=sweeps, seconds=time.perf_counter() - t0)
+    return volume, poses, report
+
+
+def _frame_reports(stats, min_inlier_share, first_fixed):
+    return [dict(inliers=int(s[0]), rms=float(s[1]), inlier_share=float(s[2]), moved=int(s[3]),
+                 lost=bool((v > 0 or not first_fixed) and s[2] < min_inlier_share)) for v, s in enumerate(stats)]
+
+
+def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad(15.0), reach=None, top=32, iters=10, stride=1,
+         sweeps=0, gate=None, pixel_offset=0.0, min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, seed=0, dev=None,
+         track_fn=None, integrate_fn=None, score_fn=None, turned_over=False):
+    """A second sequence without any pose joined to a first one whose poses are known: the object turned
+    over between the two, BOP's model-free static onboarding.  (volume, poses_second float64 [V,12] on the host, report).
+    first = dict(depths, masks, K, poses): poses given, or onboard's result; second = dict(depths, masks, K); masks may be None.
+    The fine volume is Volume.around all of first's frames at `voxel` (trunc: default 3 voxels), the coarse one at coarse * voxel
+    with trunc 3 * coarse * voxel; first is integrated into both.  relocalise.relocalise finds second's frame 0 against (coarse,
+    fine) -- points, step, reach, top, seed are its arguments --, then onboard's frame loop runs on the fine volume from that
+    pose: every later frame is tracked from the previous one's result and integrated.  The volume only covers what first saw,
+    padded by trunc + voxel: the sequences show one object.  sweeps times: all of second is tracked in ONE batched call against
+    the finished volume and both sequences are integrated into a fresh one.  turned_over: relocalise's (for an object with
+    symmetries, whose seen side the turned-over sequence fits as well as its own: the frame goes where it shows unseen space).
+    report: dict(relocalise: relocalise's report, frames: per frame of second dict(inliers, rms, inlier_share, moved, lost) --
+    frame 0's are the refinement's --, lost, max_step, trunc, voxel, dims, coarse_dims, sweeps, seconds).  track_fn,
+    integrate_fn, score_fn stand for track, fuse.integrate and relocalise.pose_scores (the tests pass the NumPy restatements
+    and dev="cpu")."""
+    from . import relocalise as RL
+    track_fn = track if track_fn is None else track_fn
+    integrate_fn = fuse.integrate if integrate_fn is None else integrate_fn
+    dev = ops._dev() if dev is None else torch.device(dev)
+    t0 = time.perf_counter()
+    da = hostargs.image_batch(first["depths"], dev, "track.join", max_dim=fuse.MAX_IMAGE)
+    db = hostargs.image_batch(second["depths"], dev, "track.join", max_dim=fuse.MAX_IMAGE)
+    ma = None if first.get("masks") is None else hostargs.mask_batch(first["masks"], da, dev, "track.join", same_shape=True)
+    mb = None if second.get("masks") is None else hostargs.mask_batch(second["masks"], db, dev, "track.join", same_shape=True)
+    Ka, Kb = first["K"], second["K"]
+    Pa = hostargs.tensor(first["poses"], torch.float64, dev).reshape(-1, 12)
+    coarse, sweeps = int(coarse), int(sweeps)
+    if Pa.shape[0] != da.shape[0] or not bool(torch.isfinite(Pa).all()):
+        raise ValueError("track.join: the first sequence has one finite pose per frame")
+    if coarse < 1 or sweeps < 0:
+        raise ValueError("track.join: coarse >= 1 and sweeps >= 0")
+    voxel = float(np.float32(voxel))
+    trunc = float(np.float32(fuse.TRUNC_VOXELS * voxel if trunc is None else trunc))
+    box = fuse.Volume.bounds(da, ma, Pa, Ka, pixel_offset, dev)
+    volume = fuse.Volume.around(da, ma, Pa, Ka, voxel, None, trunc, pixel_offset, dev)
+    rough = fuse.Volume.around(da, ma, Pa, Ka, coarse * voxel, None, fuse.TRUNC_VOXELS * coarse * voxel, pixel_offset, dev)
+    integrate_fn(volume, da, Pa, Ka, ma, pixel_offset, znear)
+    integrate_fn(rough, da, Pa, Ka, ma, pixel_offset, znear)
+    pose0, found = RL.relocalise([rough, volume], db[0], Kb, None if mb is None else mb[0], points, step, reach, top, iters, stride,
+                                 pixel_offset, seed, min_weight, score_fn, track_fn, turned_over)
+    V = db.shape[0]
+    kw = dict(iters=iters, gate=gate, stride=stride, pixel_offset=pixel_offset, min_weight=min_weight)
+    P = torch.zeros((V, 12), dtype=torch.float64, device=dev)
+    S = torch.zeros((V, 4), dtype=torch.float32, device=dev)
+    P[0] = torch.from_numpy(pose0).to(dev)
+    S[0] = torch.tensor(found["stats"], dtype=torch.float32, device=dev)
+    _follow(volume, db, mb, Kb, P, S, kw, pixel_offset, znear, track_fn, integrate_fn)
+    for _ in range(sweeps):
+        p, s = track_fn(volume, db, Kb, P, mb, **kw)
+        P, S = p.reshape(-1, 12).to(dev), s.reshape(-1, 4).to(dev)
+        volume = fuse.Volume(volume.origin, voxel, volume.dims, trunc, dev)
+        integrate_fn(volume, da, Pa, Ka, ma, pixel_offset, znear)
+        integrate_fn(volume, db, P, Kb, mb, pixel_offset, znear)
+    poses = P.cpu().numpy()
+    frames = _frame_reports(S.cpu().numpy().astype(np.float64), min_inlier_share, first_fixed=False)
+    report = dict(relocalise=found, frames=frames, lost=sum(f["lost"] for f in frames), max_step=max_step(poses, box_corners(box)),
+                  trunc=trunc, voxel=voxel, dims=list(volume.dims), coarse_dims=list(rough.dims), sweeps=sweeps,
+                  seconds=time.perf_counter() - t0)
     return volume, poses, report
 
 
@@ -174,3 +252,37 @@ def onboard_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_m
         f["im_id"], f["recorded"] = int(im), diff
     mesh, report = fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed)
     return mesh, dict(report, track=rep)
+
+
+def join_scene(views_dir, join_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
+               simplify_cell=None, iters=10, stride=1, track_sweeps=None, extent=None, step=np.deg2rad(15.0), top=32, coarse=2,
+               points=256, close=False, support_plane=None, support_lift=None, turned_over=False):
+    """fuse.fuse_scene for two folders of one object, the second (join_dir: the object turned over) read without its poses:
+    (mesh in metres, report); the report gains `join` (join's report, and per frame of the second folder `recorded`, as
+    onboard_scene's).  track_sweeps not None (--track): the first folder's poses come from onboard (first pose only, that many
+    sweeps) and the report gains `track` too.  close, support_plane, support_lift: as fuse.fuse_scene's, on the first folder."""
+    tracked = track_sweeps is not None
+    batches = fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=tracked)
+    others = fuse.read_views(join_dir, obj_id, mesh_scale, use_masks, no_poses=True)
+    if len(batches) != 1 or len(others) != 1:
+        raise fuse.ViewsError("--join takes images of one size and camera matrix per folder, not %d and %d kinds" % (len(batches), len(others)))
+    a, b = batches[0], others[0]
+    support_plane = fuse._scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, views_dir)
+    t0 = time.perf_counter()
+    extra, poses_a = {}, a["poses"]
+    if tracked:
+        _, poses_a, rep_a = onboard(a["depths"], a["masks"], a["K"], a["poses"][0], voxel, extent, trunc, iters, stride, track_sweeps,
+                                    pixel_offset=pixel_offset, min_weight=min_weight)
+        for f, im, diff in zip(rep_a["frames"], a["im_ids"], pose_differences(poses_a, a["poses"])):
+            f["im_id"], f["recorded"] = int(im), diff
+        extra["track"] = rep_a
+    volume, poses_b, rep = join(dict(depths=a["depths"], masks=a["masks"], K=a["K"], poses=poses_a),
+                                dict(depths=b["depths"], masks=b["masks"], K=b["K"]), voxel, coarse, trunc, points, step, None, top, iters,
+                                stride, pixel_offset=pixel_offset, min_weight=min_weight, turned_over=turned_over)
+    t1 = fuse._sync(volume.device)
+    mesh, closed = fuse._surface(volume, min_weight, close, support_plane, support_lift)
+    t2 = fuse._sync(volume.device)
+    for f, im, diff in zip(rep["frames"], b["im_ids"], pose_differences(poses_b, b["poses"])):
+        f["im_id"], f["recorded"] = int(im), diff
+    mesh, report = fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed)
+    return mesh, dict(report, join=rep, **extra)

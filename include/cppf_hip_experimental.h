@@ -16,7 +16,9 @@
  *   - mesh simplification by vertex clustering with quadric representatives (cppf2_amd/simplify.py):
  *     opt-in and new;
  *   - depth frames tracked against the fused volume, for sequences with one known pose (cppf2_amd/track.py, DESIGN.md
- *     section 30): opt-in and new.
+ *     section 30): opt-in and new;
+ *   - a depth frame's pose searched against the fused volume with no starting pose, which joins a second sequence of the object
+ *     turned over (cppf2_amd/relocalise.py): opt-in and new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -329,6 +331,27 @@ int64_t cppf_tsdf_close_workspace_bytes(int nx, int ny, int nz);
 int cppf_tsdf_close(const float* acc, const int32_t* wsum, const double* h_origin, float voxel, int nx, int ny, int nz, float trunc,
                     int min_weight, const double* h_plane, float* acc_out, int32_t* wsum_out, uint8_t* state, int64_t* stats,
                     void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- the pose of a depth frame against a fused volume with no starting pose: exhaustive search (the reference has no such step) ----
+ * cppf_tsdf_pose_scores: scores int32 [NR,NT,4] on the device = (inliers, misses, unknown, outside) of candidate (r, j), summing
+ * to P.  The volume acc / wsum, h_origin, voxel, nx, ny, nz, trunc and min_weight as cppf_tsdf_track takes them.  points float32
+ * [P,3], camera frame, 1 <= P <= 2048; rotations float64 [NR,9], row-major, model -> camera, cast to float32 entry by entry;
+ * offsets int32 [NT,3], whole nodes of the model frame (all three on the device); h_pivot_cam c and h_pivot_model m0: float[3]
+ * on the HOST; tau float32: the inlier distance on the volume's value, metres.  Per point p and rotation R, float32 in this
+ * order: d = p - c; x = R^T d in cppf_tsdf_track's expression; q = x + m0; g = (q - o) / voxel per axis.  A point with a g that
+ * is not finite or has |g| >= 2^20 on any axis is outside for every offset.  Otherwise fl = floorf(g), f = g - fl, and for offset
+ * j the cell is i = (int)fl + off_j: outside unless 0 <= i <= n - 2 on every axis; unknown if any of the cell's 8 corners has
+ * wsum < min_weight; otherwise phi is cppf_tsdf_track's trilinear value of acc / (float)wsum at fractions f, and the point is an
+ * inlier iff fabsf(trunc * phi) <= tau, else a miss.  The pose of candidate (r, j) is R_r, t = c - R_r (m0 + off_j voxel).  One
+ * launch, no atomics, no workspace, no host synchronisation; the exact order of the operations is stated in
+ * cppf2_amd/csrc/cppf_relocalise.hip and restated in tests/relocalise_ref.py.  NR = 0 or NT = 0: valid, nothing is written.
+ * CPPF_EINVAL, before any device work, for: a NULL acc, wsum, h_origin, points or pivot (rotations, offsets and scores too
+ * unless NR = 0 or NT = 0); P outside 1..2048; NR or NT < 0 or NR * NT > 2^29; the volume checks of cppf_tsdf_extract; voxel,
+ * trunc or tau not positive and finite; a pivot that is not finite; min_weight < 1. */
+int cppf_tsdf_pose_scores(const float* acc, const int32_t* wsum, const double* h_origin, float voxel, int nx, int ny, int nz,
+                          float trunc, int min_weight, const float* points, int P, const double* rotations, int NR,
+                          const float* h_pivot_cam, const float* h_pivot_model, const int32_t* offsets, int NT, float tau,
+                          int32_t* scores, void* stream);
 
 #ifdef __cplusplus
 }
