@@ -312,8 +312,24 @@ def _finish(volume, mesh, seconds, simplify_cell, closed=None):
     return mesh, dict(_report(volume, mesh, *seconds), simplify=simplified, **extra)
 
 
+def _conditioned(result, conditioned):
+    """(mesh, report) with the report's `condition` (depthfilter's summary; None: no such stage, no such key)."""
+    mesh, report = result
+    return mesh, report if conditioned is None else dict(report, condition=conditioned)
+
+
+def condition_batches(batches, condition):
+    """read_views' batches with their depths conditioned (device tensors then), and the summary over all of them; (batches, None)
+    as they are when condition is None."""
+    if condition is None:
+        return batches, None
+    from . import depthfilter
+    done = [depthfilter.apply(b["depths"], condition, "fuse") for b in batches]
+    return [dict(b, depths=d) for b, (d, _) in zip(batches, done)], depthfilter.merged([c for _, c in done])
+
+
 def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weight=1, pixel_offset=0.0, znear=render.ZNEAR,
-               volume=None, simplify_cell=None, close=False, support_plane=None, support_lift=None):
+               volume=None, simplify_cell=None, close=False, support_plane=None, support_lift=None, condition=None):
     """Both stages on one batch of views: (mesh, report).  `volume`: an existing Volume to add to (else Volume.around the views).
     report: dict(views, dims, voxel, trunc, triangles, vertices, boundary_edges, unknown_share (nodes no view observed),
     seconds: dict(volume, integrate, extract)).  simplify_cell (metres; None: no such stage): the welded mesh goes through
@@ -322,8 +338,13 @@ def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weig
     close=True: the volume goes through close() before it is extracted (the seconds count it under extract); support_plane (a, b,
     c, d) as close()'s plane (None: none), moved support_lift metres towards the object first (default: half a voxel; the mesh's
     bottom then lies that far above the plane).  report["close"] is close()'s report plus `lift`, and triangles, vertices and
-    boundary_edges describe the closed mesh."""
+    boundary_edges describe the closed mesh.
+    condition: a depthfilter.Settings record (None: the readings as they are): the views are conditioned (depthfilter.condition,
+    DESIGN.md section 33) before Volume.around and integrate see them, and report["condition"] holds the settings and the
+    counts summed over the views."""
+    from . import depthfilter
     t0 = time.perf_counter()
+    depths, conditioned = depthfilter.apply(depths, condition, "fuse.fuse_views")
     if volume is None:
         volume = Volume.around(depths, masks, poses, K, voxel, margin, trunc, pixel_offset)
     t1 = _sync(volume.device)
@@ -331,7 +352,7 @@ def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weig
     t2 = _sync(volume.device)
     mesh, closed = _surface(volume, min_weight, close, support_plane, support_lift)
     t3 = _sync(volume.device)
-    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed)
+    return _conditioned(_finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed), conditioned)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -428,11 +449,11 @@ def _scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, view
 
 
 def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
-               simplify_cell=None, close=False, support_plane=None, support_lift=None):
+               simplify_cell=None, close=False, support_plane=None, support_lift=None, condition=None):
     """read_views fused into one volume (one integrate call per image size and K): (mesh in metres, report).  simplify_cell, close,
     support_plane and support_lift: as fuse_views'; support_plane "auto": auto_support_plane of the first view, found before
-    anything is fused."""
-    batches = read_views(views_dir, obj_id, mesh_scale, use_masks)
+    anything is fused.  condition: as fuse_views'; every batch is conditioned right after it is read."""
+    batches, conditioned = condition_batches(read_views(views_dir, obj_id, mesh_scale, use_masks), condition)
     support_plane = _scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, views_dir)
     t0 = time.perf_counter()
     boxes = np.stack([Volume.bounds(b["depths"], b["masks"], b["poses"], b["K"], pixel_offset) for b in batches])
@@ -446,7 +467,7 @@ def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_mask
     t2 = _sync(volume.device)
     mesh, closed = _surface(volume, min_weight, close, support_plane, support_lift)
     t3 = _sync(volume.device)
-    return _finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed)
+    return _conditioned(_finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed), conditioned)
 
 
 def _plane_argument(text):
@@ -497,6 +518,14 @@ def main(argv=None):
     ap.add_argument("--support-lift", type=float, default=None,
                     help="--close: metres the plane is moved towards the object before the volume is cut, the statement of the "
                          "sensor's noise on the table (default: half a voxel); the mesh's bottom then lies this far above the table")
+    ap.add_argument("--condition-depth", action="store_true",
+                    help="condition every depth image before anything reads it: drop mixed pixels on silhouettes, and smooth within "
+                         "a surface with --smooth-radius (default: the readings as they are)")
+    ap.add_argument("--flying-radius", type=int, default=None, help="--condition-depth: half the window a reading's support is counted in (1; 0: off)")
+    ap.add_argument("--flying-support", type=int, default=None, help="--condition-depth: neighbours within the gate that a reading needs to stay (4)")
+    ap.add_argument("--smooth-radius", type=int, default=None, help="--condition-depth: half the window of the paired mean (0: no smoothing)")
+    ap.add_argument("--depth-jump", type=float, default=None, help="--condition-depth: the gate in metres (0.01)")
+    ap.add_argument("--depth-jump-rel", type=float, default=None, help="--condition-depth: the gate's share of the reading, added to --depth-jump (0)")
     ap.add_argument("--report", default=None, help="write the report as JSON here")
     ap.add_argument("--out", required=True, help="the .ply to write, in model units")
     a = ap.parse_args(argv)
@@ -524,7 +553,13 @@ def main(argv=None):
         ap.error("--support-lift is a length in metres, 0 or more")
     if a.support_lift is not None and a.support_plane is None:
         ap.error("--support-lift moves the --support-plane; there is none")
-    closing = dict(close=a.close, support_plane=a.support_plane, support_lift=a.support_lift)
+    from . import depthfilter
+    try:
+        condition = depthfilter.from_flags(a.condition_depth, {k: getattr(a, k) for k in depthfilter.FLAGS},
+                                           lambda name: "--" + name.replace("_", "-"), who="--condition-depth")
+    except ValueError as e:
+        ap.error(str(e))
+    closing = dict(close=a.close, support_plane=a.support_plane, support_lift=a.support_lift, condition=condition)
     from . import bop_data
     if a.join is not None:
         from . import track

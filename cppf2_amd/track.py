@@ -21,7 +21,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, fuse, hostargs, ops, render
+from . import _lib, depthfilter, fuse, hostargs, ops, render
 from ._lib import CppfError
 
 MAX_FRAMES = 65535               # frames per cppf_tsdf_track call
@@ -102,7 +102,8 @@ def _follow(volume, d, m, K, P, S, kw, pixel_offset, znear, track_fn, integrate_
 
 
 def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, stride=1, sweeps=1, gate=None, pixel_offset=0.0,
-            min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, dev=None, track_fn=None, integrate_fn=None):
+            min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, dev=None, track_fn=None, integrate_fn=None,
+            condition=None):
     """A volume from a sequence of which only the first frame's pose is known: (volume, poses float64 [V,12] on the host, report).
     The volume is Volume.around the first frame at pose0, padded by extent (+ trunc + voxel) on every side: the first frame shows
     one side only, so extent defaults to the longest side of the first frame's box.  Frame 0 is integrated at pose0; every
@@ -112,13 +113,15 @@ def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, s
     report: dict(frames: per frame dict(inliers, rms, inlier_share, moved, lost), lost: how many, max_step: the largest motion
     of the first frame's box corners between consecutive estimates, metres, trunc, voxel, dims, sweeps, seconds).  lost =
     inlier_share < min_inlier_share; max_step above trunc means the next surface may have lain outside the band that has a
-    gradient.  track_fn / integrate_fn stand for track / fuse.integrate (tests/test_track.py passes the
-    NumPy restatements and dev="cpu")."""
+    gradient.  condition: a depthfilter.Settings record (None: the readings as they are): the frames are
+    conditioned before anything sees them, and the report gains `condition`.  track_fn / integrate_fn
+    stand for track / fuse.integrate (tests/test_track.py passes the NumPy restatements and dev="cpu")."""
     track_fn = track if track_fn is None else track_fn
     integrate_fn = fuse.integrate if integrate_fn is None else integrate_fn
     dev = ops._dev() if dev is None else torch.device(dev)
     t0 = time.perf_counter()
     d = hostargs.image_batch(depths, dev, "track.onboard", max_dim=fuse.MAX_IMAGE)
+    d, conditioned = depthfilter.apply(d, condition, "track.onboard")
     V = d.shape[0]
     m = None if masks is None else hostargs.mask_batch(masks, d, dev, "track.onboard", same_shape=True)
     pose0 = np.asarray(pose0, dtype=np.float64).reshape(1, 12)
@@ -147,6 +150,8 @@ def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, s
     frames = _frame_reports(stats, min_inlier_share, first_fixed=True)
     report = dict(frames=frames, lost=sum(f["lost"] for f in frames), max_step=max_step(poses, box_corners(box)), trunc=trunc,
                   voxel=voxel, dims=list(volume.dims), sweeps=sweeps, seconds=time.perf_counter() - t0)
+    if conditioned is not None:
+        report["condition"] = conditioned
     return volume, poses, report
 
 
@@ -157,7 +162,7 @@ def _frame_reports(stats, min_inlier_share, first_fixed):
 
 def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad(15.0), reach=None, top=32, iters=10, stride=1,
          sweeps=0, gate=None, pixel_offset=0.0, min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, seed=0, dev=None,
-         track_fn=None, integrate_fn=None, score_fn=None, turned_over=False):
+         track_fn=None, integrate_fn=None, score_fn=None, turned_over=False, condition=None):
     """A second sequence without any pose joined to a first one whose poses are known: the object turned
     over between the two, BOP's model-free static onboarding.  (volume, poses_second float64 [V,12] on the host, report).
     first = dict(depths, masks, K, poses): poses given, or onboard's result; second = dict(depths, masks, K); masks may be None.
@@ -169,7 +174,8 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
     the finished volume and both sequences are integrated into a fresh one.  turned_over: relocalise's (for an object with
     symmetries, whose seen side the turned-over sequence fits as well as its own: the frame goes where it shows unseen space).
     report: dict(relocalise: relocalise's report, frames: per frame of second dict(inliers, rms, inlier_share, moved, lost) --
-    frame 0's are the refinement's --, lost, max_step, trunc, voxel, dims, coarse_dims, sweeps, seconds).  track_fn,
+    frame 0's are the refinement's --, lost, max_step, trunc, voxel, dims, coarse_dims, sweeps, seconds).  condition: as
+    onboard's, on both sequences (the report's `condition` sums them).  track_fn,
     integrate_fn, score_fn stand for track, fuse.integrate and relocalise.pose_scores (the tests pass the NumPy restatements
     and dev="cpu")."""
     from . import relocalise as RL
@@ -179,6 +185,8 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
     t0 = time.perf_counter()
     da = hostargs.image_batch(first["depths"], dev, "track.join", max_dim=fuse.MAX_IMAGE)
     db = hostargs.image_batch(second["depths"], dev, "track.join", max_dim=fuse.MAX_IMAGE)
+    da, cond_a = depthfilter.apply(da, condition, "track.join")
+    db, cond_b = depthfilter.apply(db, condition, "track.join")
     ma = None if first.get("masks") is None else hostargs.mask_batch(first["masks"], da, dev, "track.join", same_shape=True)
     mb = None if second.get("masks") is None else hostargs.mask_batch(second["masks"], db, dev, "track.join", same_shape=True)
     Ka, Kb = first["K"], second["K"]
@@ -215,6 +223,8 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
     report = dict(relocalise=found, frames=frames, lost=sum(f["lost"] for f in frames), max_step=max_step(poses, box_corners(box)),
                   trunc=trunc, voxel=voxel, dims=list(volume.dims), coarse_dims=list(rough.dims), sweeps=sweeps,
                   seconds=time.perf_counter() - t0)
+    if condition is not None:
+        report["condition"] = depthfilter.merged([cond_a, cond_b])
     return volume, poses, report
 
 
@@ -232,12 +242,13 @@ def pose_differences(poses, recorded):
 
 
 def onboard_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
-                  simplify_cell=None, iters=10, stride=1, sweeps=1, extent=None, close=False, support_plane=None, support_lift=None):
+                  simplify_cell=None, iters=10, stride=1, sweeps=1, extent=None, close=False, support_plane=None, support_lift=None,
+                  condition=None):
     """fuse.fuse_scene for a folder of which only the first image's pose is used: (mesh in metres, report); the report gains
     `track` (onboard's report, and per frame `recorded`: the difference to the pose the folder has for it, where it has one --
     recorded, not judged).  close, support_plane, support_lift: as fuse.fuse_scene's (the first image's pose, the one that is
-    known, takes an "auto" plane into the object's frame)."""
-    batches = fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=True)
+    known, takes an "auto" plane into the object's frame).  condition: as fuse.fuse_scene's."""
+    batches, conditioned = fuse.condition_batches(fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=True), condition)
     if len(batches) != 1:
         raise fuse.ViewsError("%s: --track takes images of one size and camera matrix, not %d kinds" % (views_dir, len(batches)))
     b = batches[0]
@@ -250,20 +261,21 @@ def onboard_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_m
     t2 = fuse._sync(volume.device)
     for f, im, diff in zip(rep["frames"], b["im_ids"], pose_differences(poses, b["poses"])):
         f["im_id"], f["recorded"] = int(im), diff
-    mesh, report = fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed)
+    mesh, report = fuse._conditioned(fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed), conditioned)
     return mesh, dict(report, track=rep)
 
 
 def join_scene(views_dir, join_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
                simplify_cell=None, iters=10, stride=1, track_sweeps=None, extent=None, step=np.deg2rad(15.0), top=32, coarse=2,
-               points=256, close=False, support_plane=None, support_lift=None, turned_over=False):
+               points=256, close=False, support_plane=None, support_lift=None, turned_over=False, condition=None):
     """fuse.fuse_scene for two folders of one object, the second (join_dir: the object turned over) read without its poses:
     (mesh in metres, report); the report gains `join` (join's report, and per frame of the second folder `recorded`, as
     onboard_scene's).  track_sweeps not None (--track): the first folder's poses come from onboard (first pose only, that many
-    sweeps) and the report gains `track` too.  close, support_plane, support_lift: as fuse.fuse_scene's, on the first folder."""
+    sweeps) and the report gains `track` too.  close, support_plane, support_lift: as fuse.fuse_scene's, on the first folder.
+    condition: as fuse.fuse_scene's, on both folders."""
     tracked = track_sweeps is not None
-    batches = fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=tracked)
-    others = fuse.read_views(join_dir, obj_id, mesh_scale, use_masks, no_poses=True)
+    batches, cond_a = fuse.condition_batches(fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=tracked), condition)
+    others, cond_b = fuse.condition_batches(fuse.read_views(join_dir, obj_id, mesh_scale, use_masks, no_poses=True), condition)
     if len(batches) != 1 or len(others) != 1:
         raise fuse.ViewsError("--join takes images of one size and camera matrix per folder, not %d and %d kinds" % (len(batches), len(others)))
     a, b = batches[0], others[0]
@@ -284,5 +296,6 @@ def join_scene(views_dir, join_dir, voxel, obj_id=None, trunc=None, min_weight=1
     t2 = fuse._sync(volume.device)
     for f, im, diff in zip(rep["frames"], b["im_ids"], pose_differences(poses_b, b["poses"])):
         f["im_id"], f["recorded"] = int(im), diff
-    mesh, report = fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed)
+    conditioned = None if condition is None else depthfilter.merged([cond_a, cond_b])
+    mesh, report = fuse._conditioned(fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed), conditioned)
     return mesh, dict(report, join=rep, **extra)

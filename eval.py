@@ -106,6 +106,14 @@ What the image cannot provide is stated, not faked:
     ineligible once more than that share of the smaller solid of it and an earlier instance lies inside the other by more
     than solid_tau (cppf_solid_overlap): reason `inside`, `inside_of` the instance's index.  The report gains `support` and
     `refused` per hypothesis under `verify`, `support_counts` per candidate of the scene, `scene.passes` and `solid_checks`.
+  * `--condition_depth [--flying_radius=1 --flying_support=4 --smooth_radius=0 --depth_jump=0.01 --depth_jump_rel=0]`
+    (--data=depth and --data=bop; cppf2_amd.depthfilter, cppf_depth_condition; not in the reference)
+    conditions every depth image once, right after it is read and scaled: a reading with fewer than --flying_support of its
+    (2 flying_radius + 1)^2 - 1 neighbours within depth_jump + depth_jump_rel * z of it -- a mixed pixel on a silhouette --
+    becomes 0, and with --smooth_radius > 0 every kept reading becomes the mean of itself and the pairs of opposite neighbours
+    within that gate.  Mask cleaning, proposals, back-projection, verification, --icp_depth and the scene explanation then all
+    read the conditioned image.  The report gains `depth_condition` (the settings; valid, removed and smoothed pixels).  Off
+    by default, and without it nothing changes.
 Swapped flag names are kept: geo_branch gates model 0 (DINO), visual_branch gates model 1 (SHOT) (eval.py:367).
 """
 import collections
@@ -415,7 +423,7 @@ def _icp_depth_flag(icp_depth, icp_model_weight, icp_iters):
 
 def main_bop(setup, vote, stages, bop_root, split, out_csv, targets=None, mesh_scale=0.001, batch_instances=16, teacher_prior=False,
              visib_gt_min=None, debug=False, out=None, detections=None, det_score_min=0.0, clean_masks=False, mask_jump=None,
-             pair_tables=None):
+             pair_tables=None, condition=None):
     """The instance-level path over one split of a BOP-format dataset (cppf2_amd.bop_data.Dataset): one estimate per valid
     ground-truth instance of every target, from its visible mask; poses written to `out_csv` in BOP's frame and scored with
     bop_data.score.  Instances of one object (and one K and image size) are evaluated in batches of `batch_instances` across
@@ -425,11 +433,14 @@ def main_bop(setup, vote, stages, bop_root, split, out_csv, targets=None, mesh_s
     pair_tables: a folder of obj_%06d.npz pair-feature tables (python -m cppf2_amd.pair_table): each object's instances are then
     voted from its table (run_table) instead of the two model passes; no prior.
     clean_masks: every mask is cut down to its largest depth-connected component (masks.clean, mask_jump metres) before
-    back-projection and verification.  Returns the report (report["bop"] = bop_data.score's)."""
+    back-projection and verification.  condition: a depthfilter.Settings record or None; every depth image is then conditioned
+    once, right after it is read, and every step reads the conditioned image (the report's `depth_condition`: the counts summed
+    over the images).  Returns the report (report["bop"] = bop_data.score's)."""
     import time
-    from cppf2_amd import bop, bop_data, icp, masks
+    from cppf2_amd import bop, bop_data, depthfilter, icp, masks
     dev = ops._dev()
     cfg, seed = setup[0], vote.seed
+    conditioned = []
     if pair_tables and teacher_prior:             # main() has checked this; kept for callers of this function, which is public
         raise ValueError("--pair_tables votes from the tables: it cannot be combined with --teacher_prior")
     up_sym = bool(cfg.get("up_sym", False))
@@ -552,6 +563,11 @@ def main_bop(setup, vote, stages, bop_root, split, out_csv, targets=None, mesh_s
         t0 = time.perf_counter()
         if (s_id, im) not in depth_of:
             depth_of = {(s_id, im): ds.depth(s_id, im)}                                    # (the last image's is kept)
+            if condition is not None:
+                raw = depth_of[(s_id, im)]
+                dc, counted = depthfilter.apply(raw.astype(np.float32), condition, "eval.py")
+                depth_of[(s_id, im)] = dc[0].cpu().numpy().astype(raw.dtype)
+                conditioned.append(counted)
         depth = depth_of[(s_id, im)]
         cands = candidates(s_id, im, o, info, sc["gt"].get(im, []), depth)
         if clean_masks and cands:
@@ -595,6 +611,9 @@ def main_bop(setup, vote, stages, bop_root, split, out_csv, targets=None, mesh_s
     cleaning = ("largest depth-connected component of each mask, neighbours within %g m (cppf_mask_components)" % mask_jump
                 if clean_masks else None)
     report.update(stage_notes("each object's model", stages, cleaning))
+    if condition is not None:
+        report["depth_condition"] = (depthfilter.merged(conditioned) if conditioned
+                                     else depthfilter.summary(condition, np.zeros((0, 3), np.int64)))
     return _emit(report, debug, out)
 
 
@@ -808,6 +827,10 @@ def _checked_flags(**kw):
     if f.iou_device and f.data != "nocs":
         raise ValueError("--iou_device scores the NOCS scorer's box overlaps on the GPU: it needs --data=nocs")
     f.solid = _solid_flags(f)
+    from cppf2_amd import depthfilter
+    f.condition = depthfilter.from_flags(bool(f.condition_depth), {k_: getattr(f, k_) for k_ in depthfilter.FLAGS})
+    if f.condition is not None and f.data not in ("depth", "bop"):
+        raise ValueError("--condition_depth conditions the depth image before anything reads it: it needs --data=depth or --data=bop")
     from cppf2_amd import verify
     f.stages = Stages(f.icp_iters, f.icp_depth, f.icp_model_weight, f.hypotheses,
                       verify.TAU if f.verify_tau is None else float(f.verify_tau), f.centre_peaks)
@@ -1017,7 +1040,7 @@ def _explain_scene(cands, objs, d, region, K, tau, explain, solid=None):
 
 # what the instance loop of one depth image reads besides its masks and objects: the depth in metres and K, the categories'
 # setups, the Vote and Stages settings, what the ICP refined against (the report's words), and where the report goes
-DepthRun = collections.namedtuple("DepthRun", "d K setups vote stages against debug out out_pkl")
+DepthRun = collections.namedtuple("DepthRun", "d K setups vote stages against debug out out_pkl conditioned", defaults=(None,))
 
 
 def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, explain=None, cleaning=None, pair_tables=None,
@@ -1128,20 +1151,24 @@ def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, ex
         report["solid_checks"] = solid
     if symmetries is not None:
         report["symmetries"] = symmetries
+    if ctx.conditioned is not None:
+        report["depth_condition"] = ctx.conditioned
     return _finish(report, acc, categories, ctx.debug, ctx.out, ctx.out_pkl)
 
 
 def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=None, depth_scale=1000.0, mesh=None, mesh_scale=1.0,
                gt_pose=None, models_info=None, clean_mask=False, mask_jump=None, pair_table=None, debug=False, out=None, out_pkl=None,
                propose=None, explain=None, models_dir=None, pair_tables=None, obj_ids=None, model_scale=0.001, solid=None,
-               sym_tol=None):
+               sym_tol=None, condition=None):
     """One depth + mask PNG pair (example_data layout): one instance, evaluated once per category of `categories`; with `mesh`
     its pose is refined (stages.icp_iters), verified (stages.hypotheses) and scored against gt_pose (BOP errors), see the module
     docstring.  propose: segment.propose's keyword arguments; the proposed masks then stand where the one of `mask` stood, one
     instance each in one batch per category.  explain: _explain_flags' dict (the report's `scene`); models_dir, pair_tables,
     obj_ids, model_scale: the objects of the multi-object form, which stand where mesh and pair_table stood.  solid:
     _solid_flags' dict (the support and overlap checks of cppf2_amd/solid.py).  sym_tol: --detect_symmetries' tolerance or None;
-    the detected entry then stands where the one of models_info stood.  This reads the inputs; _depth_instances runs them."""
+    the detected entry then stands where the one of models_info stood.  condition: a depthfilter.Settings record or None; the
+    depth image is then conditioned once, right after it is read and scaled, and every later step reads the conditioned image
+    (the report's `depth_condition`).  This reads the inputs; _depth_instances runs them."""
     from PIL import Image
     from cppf2_amd import bop, icp, masks, render, segment
     gt = symmetries = None
@@ -1164,8 +1191,13 @@ def main_depth(setups, categories, vote, stages, depth, mask=None, intrinsics=No
             obj = bop.ObjectInfo.from_mesh(render.load_mesh(mesh, mesh_scale))
         objects, against = [dict(obj=obj, icp_model=icp_model, pair_table=pair_table)], os.path.basename(mesh or "")
     d = np.array(Image.open(depth)).astype(np.float64) / float(depth_scale)
+    conditioned = None
+    if condition is not None:
+        from cppf2_amd import depthfilter
+        dc, conditioned = depthfilter.apply(d.astype(np.float32), condition, "eval.py")
+        d = dc[0].cpu().numpy().astype(np.float64)
     K = np.array(intrinsics if intrinsics is not None else REAL_INTRINSICS, dtype=np.float64).reshape(3, 3)
-    ctx = DepthRun(d, K, setups, vote, stages, against, debug, out, out_pkl)
+    ctx = DepthRun(d, K, setups, vote, stages, against, debug, out, out_pkl, conditioned)
     if propose is not None:
         pm, props, plane = segment.propose(d.astype(np.float32), K, vote.seed, **propose)
         return _depth_instances(ctx, pm.cpu().numpy() > 0, objects, categories, (props, plane, propose), gt, explain,
@@ -1196,7 +1228,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          max_proposals=None, explain_scene=False, explain_min_score=None, explain_min_gain=None, explain_viol_weight=None,
          explain_max=None, models_dir=None, obj_ids=None, explain_hypotheses=False, explain_min_support=None,
          support_check=False, support_tau=None, support_max_share=None, explain_solid=False, solid_tau=None, solid_max_share=None,
-         detect_symmetries=False, sym_tol=None, iou_device=False):
+         detect_symmetries=False, sym_tol=None, iou_device=False, condition_depth=False, flying_radius=None, flying_support=None,
+         smooth_radius=None, depth_jump=None, depth_jump_rel=None):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()
@@ -1205,7 +1238,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
         return main_bop(load_custom(ckpt_shot, ckpt_dino, device=dev, models=not pair_tables), vote, f.stages, bop_root, split, out_csv,
                         targets=targets, mesh_scale=float(model_scale), batch_instances=batch_instances,
                         teacher_prior=bool(teacher_prior), debug=debug, out=out, detections=detections,
-                        det_score_min=float(det_score_min), clean_masks=f.clean_masks, mask_jump=mask_jump, pair_tables=pair_tables)
+                        det_score_min=float(det_score_min), clean_masks=f.clean_masks, mask_jump=mask_jump, pair_tables=pair_tables,
+                        condition=f.condition)
     custom = False
     if categories is None:
         if category:
@@ -1234,7 +1268,7 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
                           mesh_scale=mesh_scale, gt_pose=gt_pose, models_info=models_info, clean_mask=f.clean_masks,
                           mask_jump=mask_jump, pair_table=pair_table, debug=debug, out=out, out_pkl=out_pkl, propose=f.propose,
                           explain=f.explain, models_dir=models_dir, pair_tables=pair_tables, obj_ids=f.obj_ids,
-                          model_scale=float(model_scale), solid=f.solid, sym_tol=f.sym_tol)
+                          model_scale=float(model_scale), solid=f.solid, sym_tol=f.sym_tol, condition=f.condition)
     return main_synthetic(setups, categories, vote, num_scenes=num_scenes, num_points=num_points, debug=debug, out=out,
                           out_pkl=out_pkl)
 

@@ -353,6 +353,27 @@ int cppf_tsdf_pose_scores(const float* acc, const int32_t* wsum, const double* h
                           const float* h_pivot_cam, const float* h_pivot_model, const int32_t* offsets, int NT, float tau,
                           int32_t* scores, void* stream);
 
+/* ---- sensor depth conditioned before anything reads it: mixed pixels dropped, smoothing within a surface (the reference has no such step) ----
+ * cppf_depth_condition: depth float32 [I,H,W] (metres) -> out float32 [I,H,W] and counts int32 [I,3], all on the device.  A
+ * reading is valid if it is finite and > 0 (a denormal is).  tol(z) = jump + (jump_rel * z), float32, product and sum rounded
+ * each; every comparison is fabsf(q - z) <= tol(z) with z the CENTRE pixel's reading.  Stage 1 (flying pixels): for a valid
+ * pixel, support = the number of offsets (dy, dx) != (0, 0) in [-r1, r1]^2 whose position lies outside the image or holds a
+ * valid reading within tol; d1 = z if support >= min_support, else 0; an invalid pixel gives 0 (NaN, infinities and negatives
+ * leave as 0).  It reads the input only and is not iterated; with r1 = 0 there is no offset, and min_support = 0 keeps every
+ * valid pixel.  Stage 2 (smoothing, r2 = 0 switches it off) runs on d1: for a pixel with d1 > 0, s = z, n = 1, then over the
+ * first half of the window in row-major order (dy = -r2 .. -1 with every dx, then dy = 0 with dx = -r2 .. -1) the pair
+ * a = d1(p + o), b = d1(p - o) enters -- s = (s + a) + b, n += 2 -- iff both positions are inside the image, both values are
+ * > 0 and both are within tol(z); out = s / (float)n, correctly rounded; 0 where d1 = 0.  counts[i] = (valid readings of image
+ * i, valid readings that stage 1 removed, pixels with n > 1).  The counts are cleared, then one launch for all I images; no
+ * atomics but the integer counts, no workspace, no host synchronisation: two calls give the same bytes.  The exact order of the
+ * operations is stated in cppf2_amd/csrc/cppf_depthfilter.hip and restated in tests/depth_condition_ref.py.  I = 0: valid,
+ * nothing is written.
+ * CPPF_EINVAL, before any device work (out and counts keep their bytes), for: I < 0; H or W outside 1..16384; r1 or r2 outside
+ * 0..4; min_support outside 0..(2 r1 + 1)^2; jump or jump_rel negative or not finite; and, when I > 0, a NULL depth, out or
+ * counts, or an out that overlaps depth (stage 1 reads neighbours: the operation cannot run in place). */
+int cppf_depth_condition(const float* depth, int I, int H, int W, int r1, int min_support, int r2, float jump, float jump_rel,
+                         float* out, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
