@@ -12,7 +12,8 @@ LIB = os.path.join(PKG, "libcppf_hip.so")
 SOURCES = ["cppf_core.hip", "cppf_vote_center.hip", "cppf_backvote.hip", "cppf_rot_bins.hip", "cppf_shot.hip", "cppf_prep.hip", "cppf_refine.hip", "cppf_mlp.hip",
            "cppf_mlp_split.hip", "cppf_render.hip", "cppf_icp.hip", "cppf_bop.hip", "cppf_verify.hip", "cppf_mask.hip", "cppf_table.hip", "cppf_segment.hip",
            "cppf_scene.hip", "cppf_solid.hip", "cppf_symmetry.hip", "cppf_box_iou.hip", "cppf_fuse.hip",
-           "cppf_simplify.hip", "cppf_track.hip", "cppf_close.hip", "cppf_relocalise.hip", "cppf_depthfilter.hip"]
+           "cppf_simplify.hip", "cppf_track.hip", "cppf_close.hip", "cppf_relocalise.hip", "cppf_depthfilter.hip",
+           "cppf_depthweights.hip"]
 # -ffp-contract=off: every float op rounds where it is written (bit-exact vote grid); fused ops are explicit fmaf().
 # -munsafe-fp-atomics: native ds/global float64 atomic add for the rotation-bin partial sums.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt",

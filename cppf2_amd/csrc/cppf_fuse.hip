@@ -21,6 +21,16 @@
 //     outside the mask:               obs = 1 if sdf > 0 (free space in front of whatever the pixel shows), else skip
 //     acc += obs;  wsum += 1
 //
+// cppf_tsdf_integrate_weighted: the same kernel template with WEIGHTED set; weights uint8 [V,H,W], one per
+//   reading (cppf_depth_weights), and carve_weight in 0..255.  Everything up to obs is as above; then
+//     inside the mask (or no masks) and sdf / trunc < 1:  w = weights[v,row,col]
+//     obs is the constant 1 (inside the mask with sdf / trunc not < 1; free space outside the mask):  w = carve_weight
+//     skip if w == 0;  acc = acc + (float)w * obs;  wsum += w
+//   acc is then the weighted sum and wsum the sum of the weights: acc / (float)wsum, what every reader of the volume forms, is
+//   the weighted mean, and their min_weight a threshold in units of weight.  (float)w * 1.0f and (float)1 * obs are exact, so
+//   weights of 1 and carve_weight 1 give the unweighted bytes.  wsum is int32: one call adds at most 65 536 x 255 per node, the
+//   caller owns the total.
+//
 // cppf_tsdf_extract: marching tetrahedra over the cells (i,j,k), i < nx-1, j < ny-1, k < nz-1, in the linear cell order
 //   ((i * (ny-1) + j) * (nz-1) + k).  tsdf = acc / (float)wsum; a node is known iff wsum >= min_weight and inside iff tsdf < 0
 //   (exactly 0, and -0, are outside); a cell is processed iff its 8 corners are known.  The six tetrahedra of a cell follow the
@@ -52,9 +62,12 @@ struct TsdfGrid {
   int nx, ny, nz;
 };
 
+template <bool WEIGHTED>
 __global__ __launch_bounds__(TSDF_THREADS) void tsdf_integrate_kernel(int V, const float* __restrict__ depth,
                                                                       const uint8_t* __restrict__ masks,
-                                                                      const float* __restrict__ poses, int H, int W, float fx,
+                                                                      const float* __restrict__ poses,
+                                                                      const uint8_t* __restrict__ weights, int carve_weight,
+                                                                      int H, int W, float fx,
                                                                       float fy, float cx, float cy, float pixel_offset, TsdfGrid g,
                                                                       float trunc, float znear, int64_t nodes,
                                                                       float* __restrict__ acc, int32_t* __restrict__ wsum) {
@@ -83,16 +96,25 @@ __global__ __launch_bounds__(TSDF_THREADS) void tsdf_integrate_kernel(int V, con
     const float sdf = d - zc;
     const bool in_mask = masks == nullptr || masks[px] != 0;
     float obs;
+    bool carves = true;                                              // obs is the constant 1
     if (in_mask) {
       if (sdf < -trunc) continue;
       const float q = sdf / trunc;
-      obs = q < 1.0f ? q : 1.0f;
+      carves = !(q < 1.0f);
+      obs = carves ? 1.0f : q;
     } else {
       if (!(sdf > 0.0f)) continue;
       obs = 1.0f;
     }
-    a = a + obs;
-    w += 1;
+    if constexpr (WEIGHTED) {
+      const int wv = carves ? carve_weight : (int)weights[px];
+      if (wv == 0) continue;
+      a = a + (float)wv * obs;
+      w += wv;
+    } else {
+      a = a + obs;
+      w += 1;
+    }
   }
   acc[lin] = a;
   wsum[lin] = w;
@@ -313,23 +335,47 @@ static bool tsdf_grid(const double* h_origin, float voxel, int nx, int ny, int n
 
 static int64_t tsdf_cells(int nx, int ny, int nz) { return (int64_t)(nx - 1) * (ny - 1) * (nz - 1); }
 
-extern "C" int cppf_tsdf_integrate(int V, const float* depth, const uint8_t* masks, const float* poses, int H, int W,
-                                   const double* h_K, float pixel_offset, const double* h_origin, float voxel, int nx, int ny,
-                                   int nz, float trunc, float znear, float* acc, int32_t* wsum, void* stream) {
+#undef CPPF_FN
+#define CPPF_FN fn                       // the shared host function reports under its entry point's name
+template <bool WEIGHTED>
+static int tsdf_integrate(int V, const float* depth, const uint8_t* masks, const float* poses, const uint8_t* weights,
+                          int carve_weight, int H, int W, const double* h_K, float pixel_offset, const double* h_origin, float voxel,
+                          int nx, int ny, int nz, float trunc, float znear, float* acc, int32_t* wsum, void* stream) {
+  const char* fn = WEIGHTED ? "cppf_tsdf_integrate_weighted" : "cppf_tsdf_integrate";
   TsdfGrid g;
   CPPF_CHECK_ARG(tsdf_grid(h_origin, voxel, nx, ny, nz, &g));
   CPPF_CHECK_ARG(V >= 0 && V <= TSDF_MAX_VIEWS);
   CPPF_CHECK_ARG(H >= 1 && H <= TSDF_MAX_IMAGE && W >= 1 && W <= TSDF_MAX_IMAGE);
   CPPF_CHECK_ARG(tsdf_positive(trunc) && tsdf_positive(znear) && __builtin_isfinite(pixel_offset));
   CPPF_CHECK_ARG(h_K && acc && wsum);
+  CPPF_CHECK_ARG(!WEIGHTED || (carve_weight >= 0 && carve_weight <= 255));
   if (V == 0) return CPPF_OK;
   CPPF_CHECK_ARG(depth && poses);
+  CPPF_CHECK_ARG(!WEIGHTED || weights);
   const int64_t nodes = (int64_t)nx * ny * nz;
   const unsigned int nb = (unsigned int)((nodes + TSDF_THREADS - 1) / TSDF_THREADS);
-  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(nb), dim3(TSDF_THREADS), 0, (hipStream_t)stream, V, depth, masks, poses, H, W,
-                     (float)h_K[0], (float)h_K[1], (float)h_K[2], (float)h_K[3], pixel_offset, g, trunc, znear, nodes, acc, wsum);
+  hipLaunchKernelGGL(tsdf_integrate_kernel<WEIGHTED>, dim3(nb), dim3(TSDF_THREADS), 0, (hipStream_t)stream, V, depth, masks, poses,
+                     weights, carve_weight, H, W, (float)h_K[0], (float)h_K[1], (float)h_K[2], (float)h_K[3], pixel_offset, g, trunc,
+                     znear, nodes, acc, wsum);
   CPPF_LAUNCH_CHECK();
   return CPPF_OK;
+}
+#undef CPPF_FN
+#define CPPF_FN __func__
+
+extern "C" int cppf_tsdf_integrate(int V, const float* depth, const uint8_t* masks, const float* poses, int H, int W,
+                                   const double* h_K, float pixel_offset, const double* h_origin, float voxel, int nx, int ny,
+                                   int nz, float trunc, float znear, float* acc, int32_t* wsum, void* stream) {
+  return tsdf_integrate<false>(V, depth, masks, poses, nullptr, 0, H, W, h_K, pixel_offset, h_origin, voxel, nx, ny, nz, trunc, znear,
+                               acc, wsum, stream);
+}
+
+extern "C" int cppf_tsdf_integrate_weighted(int V, const float* depth, const uint8_t* masks, const float* poses,
+                                            const uint8_t* weights, int carve_weight, int H, int W, const double* h_K,
+                                            float pixel_offset, const double* h_origin, float voxel, int nx, int ny, int nz,
+                                            float trunc, float znear, float* acc, int32_t* wsum, void* stream) {
+  return tsdf_integrate<true>(V, depth, masks, poses, weights, carve_weight, H, W, h_K, pixel_offset, h_origin, voxel, nx, ny, nz,
+                              trunc, znear, acc, wsum, stream);
 }
 
 extern "C" int64_t cppf_tsdf_extract_workspace_bytes(int nx, int ny, int nz) {

@@ -13,13 +13,17 @@ custom-object path starts from a mesh (train_custom.ipynb).
     closed, report = close(vol, plane=(a, b, c, d))                 # a new Volume: enclosed unseen space filled, cut at the plane
     mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002, close=True, support_plane=(a, b, c, d))
     python -m cppf2_amd.fuse --views <dir> --voxel 0.002 --out obj.ply --close --support-plane auto [--support-lift 0.001]
+    integrate(vol, depths, poses, K, masks=masks, weights=depthweights.weights(depths, K)[0])       # weighted by viewing angle
+    mesh, report = fuse_views(depths, masks, poses, K, voxel=0.002, weighting=depthweights.checked())
+    python -m cppf2_amd.fuse --views <dir> --voxel 0.002 --out obj.ply --weight-views [--weight-levels 16 --carve-weight 1]
 
 The surface has one or two triangles per voxel it crosses; simplify_cell / --simplify-cell hands it to cppf2_amd.simplify
  before it is returned or written.
 
 The kernels are cppf_tsdf_integrate and cppf_tsdf_extract (include/cppf_hip_experimental.h; the definitions are stated in
-cppf2_amd/csrc/cppf_fuse.hip and restated in tests/fuse_ref.py).  Not done: no weighting by viewing angle or distance, no
-colour.  What no view saw stays open (mesh.boundary_edges counts it) unless close / --close decides it (cppf_tsdf_close,
+cppf2_amd/csrc/cppf_fuse.hip and restated in tests/fuse_ref.py).  Every observation counts once unless weighting / --weight-views
+asks for weights by viewing angle (cppf2_amd/depthweights.py, cppf_tsdf_integrate_weighted).  Not done: no
+weighting by distance, no colour.  What no view saw stays open (mesh.boundary_edges counts it) unless close / --close decides it (cppf_tsdf_close,
 cppf2_amd/csrc/cppf_close.hip): unseen space that is enclosed becomes inside, the support plane cuts the
 solid off where the object stands, and unseen space that reaches the volume's border stays open.  The poses are trusted as given; --track
 (cppf2_amd/track.py) is for a sequence of which only the first pose is known: every later frame is aligned
@@ -134,11 +138,15 @@ def _device_of(volume):
     return volume.device
 
 
-def integrate(volume, depths, poses, K, masks=None, pixel_offset=0.0, znear=render.ZNEAR):
+def integrate(volume, depths, poses, K, masks=None, pixel_offset=0.0, znear=render.ZNEAR, weights=None, carve_weight=1):
     """cppf_tsdf_integrate: adds the views depths [V,H,W] (metres; 0 = no reading) with poses [V,12] or [V,3,4] (model -> OpenCV
     camera), one camera matrix K and masks [V,H,W] (non-zero = the object; None: every pixel is) to the volume, in order.
     pixel_offset: 0 for sensor images (pixel (r,c) lies on the ray through (c,r), ops.backproject's convention), 0.5 for images
-    from render.render_depth, which samples at pixel centres.  Images of another size or K go in another call."""
+    from render.render_depth, which samples at pixel centres.  Images of another size or K go in another call.
+    weights: uint8 [V,H,W] (depthweights.weights; None: cppf_tsdf_integrate, every observation counts once):
+    cppf_tsdf_integrate_weighted adds an observation of the surface with its pixel's weight and the constant observation "free
+    space" with carve_weight (0 .. 255), and skips a weight of 0.  The volume then holds the weighted sum and the sum of the
+    weights, and every min_weight is a threshold in units of weight; wsum is int32 and the caller owns its total."""
     dev = _device_of(volume)
     d = hostargs.image_batch(depths, dev, "fuse.integrate", max_dim=MAX_IMAGE)
     V, H, W = d.shape
@@ -147,14 +155,25 @@ def integrate(volume, depths, poses, K, masks=None, pixel_offset=0.0, znear=rend
     if P.shape[0] != V:
         raise ValueError("fuse.integrate: %d poses for %d views" % (P.shape[0], V))
     hK = hostargs.camera4(K)
+    wt = None
+    if weights is not None:
+        wt = hostargs.tensor(weights, torch.uint8, dev)
+        wt = wt.reshape((1,) + tuple(wt.shape)) if wt.dim() == 2 else wt
+        if tuple(wt.shape) != (V, H, W):
+            raise ValueError("fuse.integrate: weights %s for depths %s" % (tuple(wt.shape), (V, H, W)))
+        if not 0 <= int(carve_weight) <= 255:
+            raise ValueError("fuse.integrate: carve_weight is in 0 .. 255, not %r" % (carve_weight,))
     L = _lib.load()
     nx, ny, nz = volume.dims
     for a in range(0, V, MAX_VIEWS):
         n = min(MAX_VIEWS, V - a)
-        _lib.check(L.cppf_tsdf_integrate(n, ops._p(d[a:]), ops._p(m[a:] if m is not None else None), ops._p(P[a:]), H, W, hK,
-                                         C.c_float(pixel_offset), _host3(volume.origin), C.c_float(volume.voxel), nx, ny, nz,
-                                         C.c_float(volume.trunc), C.c_float(znear), ops._p(volume.acc), ops._p(volume.wsum),
-                                         ops._stream()), "cppf_tsdf_integrate")
+        grid = (H, W, hK, C.c_float(pixel_offset), _host3(volume.origin), C.c_float(volume.voxel), nx, ny, nz, C.c_float(volume.trunc),
+                C.c_float(znear), ops._p(volume.acc), ops._p(volume.wsum), ops._stream())
+        views = (n, ops._p(d[a:]), ops._p(m[a:] if m is not None else None), ops._p(P[a:]))
+        if wt is None:
+            _lib.check(L.cppf_tsdf_integrate(*views, *grid), "cppf_tsdf_integrate")
+        else:
+            _lib.check(L.cppf_tsdf_integrate_weighted(*views, ops._p(wt[a:]), int(carve_weight), *grid), "cppf_tsdf_integrate_weighted")
     volume.views += V
     return volume
 
@@ -318,6 +337,17 @@ def _conditioned(result, conditioned):
     return mesh, report if conditioned is None else dict(report, condition=conditioned)
 
 
+def _weighted(result, weighted):
+    """(mesh, report) with the report's `weighting` (depthweights' summary; None: no such stage, no such key)."""
+    mesh, report = result
+    return mesh, report if weighted is None else dict(report, weighting=weighted)
+
+
+def _weights_kw(w, weighting):
+    """integrate's keyword arguments for a batch's weights (none when weighting is off: the call is what it always was)."""
+    return {} if w is None else dict(weights=w, carve_weight=weighting.carve_weight)
+
+
 def condition_batches(batches, condition):
     """read_views' batches with their depths conditioned (device tensors then), and the summary over all of them; (batches, None)
     as they are when condition is None."""
@@ -329,7 +359,7 @@ def condition_batches(batches, condition):
 
 
 def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weight=1, pixel_offset=0.0, znear=render.ZNEAR,
-               volume=None, simplify_cell=None, close=False, support_plane=None, support_lift=None, condition=None):
+               volume=None, simplify_cell=None, close=False, support_plane=None, support_lift=None, condition=None, weighting=None):
     """Both stages on one batch of views: (mesh, report).  `volume`: an existing Volume to add to (else Volume.around the views).
     report: dict(views, dims, voxel, trunc, triangles, vertices, boundary_edges, unknown_share (nodes no view observed),
     seconds: dict(volume, integrate, extract)).  simplify_cell (metres; None: no such stage): the welded mesh goes through
@@ -341,18 +371,23 @@ def fuse_views(depths, masks, poses, K, voxel, trunc=None, margin=None, min_weig
     boundary_edges describe the closed mesh.
     condition: a depthfilter.Settings record (None: the readings as they are): the views are conditioned (depthfilter.condition,
     DESIGN.md section 33) before Volume.around and integrate see them, and report["condition"] holds the settings and the
-    counts summed over the views."""
-    from . import depthfilter
+    counts summed over the views.
+    weighting: a depthweights.Settings record (None: every observation counts once): the views get weights by viewing angle
+    (depthweights.weights, after conditioning when both are on; DESIGN.md section 34) and are integrated with them;
+    report["weighting"] holds the settings and the counts summed over the views, and min_weight is in units of weight (with 16
+    levels one face-on view adds 16)."""
+    from . import depthfilter, depthweights
     t0 = time.perf_counter()
     depths, conditioned = depthfilter.apply(depths, condition, "fuse.fuse_views")
+    w, weighted = depthweights.apply(depths, K, weighting, pixel_offset, "fuse.fuse_views")
     if volume is None:
         volume = Volume.around(depths, masks, poses, K, voxel, margin, trunc, pixel_offset)
     t1 = _sync(volume.device)
-    integrate(volume, depths, poses, K, masks, pixel_offset, znear)
+    integrate(volume, depths, poses, K, masks, pixel_offset, znear, **_weights_kw(w, weighting))
     t2 = _sync(volume.device)
     mesh, closed = _surface(volume, min_weight, close, support_plane, support_lift)
     t3 = _sync(volume.device)
-    return _conditioned(_finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed), conditioned)
+    return _weighted(_conditioned(_finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed), conditioned), weighted)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -449,11 +484,15 @@ def _scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, view
 
 
 def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
-               simplify_cell=None, close=False, support_plane=None, support_lift=None, condition=None):
+               simplify_cell=None, close=False, support_plane=None, support_lift=None, condition=None, weighting=None):
     """read_views fused into one volume (one integrate call per image size and K): (mesh in metres, report).  simplify_cell, close,
     support_plane and support_lift: as fuse_views'; support_plane "auto": auto_support_plane of the first view, found before
-    anything is fused.  condition: as fuse_views'; every batch is conditioned right after it is read."""
+    anything is fused.  condition: as fuse_views'; every batch is conditioned right after it is read.  weighting: as
+    fuse_views'; every batch gets its weights after that."""
+    from . import depthweights
     batches, conditioned = condition_batches(read_views(views_dir, obj_id, mesh_scale, use_masks), condition)
+    weighed = [depthweights.apply(b["depths"], b["K"], weighting, pixel_offset, "fuse.fuse_scene") for b in batches]
+    weighted = None if weighting is None else depthweights.merged([c for _, c in weighed])
     support_plane = _scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, views_dir)
     t0 = time.perf_counter()
     boxes = np.stack([Volume.bounds(b["depths"], b["masks"], b["poses"], b["K"], pixel_offset) for b in batches])
@@ -462,12 +501,12 @@ def fuse_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_mask
     lo, hi = boxes[:, 0].min(0) - (trunc + voxel), boxes[:, 1].max(0) + (trunc + voxel)
     volume = Volume(lo, voxel, np.ceil((hi - lo) / voxel).astype(np.int64) + 1, trunc)
     t1 = _sync(volume.device)
-    for b in batches:
-        integrate(volume, b["depths"], b["poses"], b["K"], b["masks"], pixel_offset)
+    for b, (w, _) in zip(batches, weighed):
+        integrate(volume, b["depths"], b["poses"], b["K"], b["masks"], pixel_offset, **_weights_kw(w, weighting))
     t2 = _sync(volume.device)
     mesh, closed = _surface(volume, min_weight, close, support_plane, support_lift)
     t3 = _sync(volume.device)
-    return _conditioned(_finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed), conditioned)
+    return _weighted(_conditioned(_finish(volume, mesh, (t1 - t0, t2 - t1, t3 - t2), simplify_cell, closed), conditioned), weighted)
 
 
 def _plane_argument(text):
@@ -486,7 +525,9 @@ def main(argv=None):
     ap.add_argument("--obj-id", type=int, default=None, help="the object to fuse (default: the scene's only one)")
     ap.add_argument("--voxel", type=float, required=True, help="node spacing in metres, e.g. 0.002")
     ap.add_argument("--trunc", type=float, default=None, help="truncation distance in metres (default: 3 voxels)")
-    ap.add_argument("--min-weight", type=int, default=1, help="observations a node needs to count as known")
+    ap.add_argument("--min-weight", type=int, default=1,
+                    help="observations a node needs to count as known; with --weight-views in units of weight: with 16 levels one "
+                         "face-on view adds 16")
     ap.add_argument("--no-masks", action="store_true", help="fuse every pixel (no mask_visib/ is read)")
     ap.add_argument("--pixel-offset", type=float, default=0.0, help="0 for sensor images, 0.5 for images rendered at pixel centres")
     ap.add_argument("--mesh-scale", type=float, default=0.001, help="model units to metres (0.001: a model in mm, as BOP's)")
@@ -526,6 +567,15 @@ def main(argv=None):
     ap.add_argument("--smooth-radius", type=int, default=None, help="--condition-depth: half the window of the paired mean (0: no smoothing)")
     ap.add_argument("--depth-jump", type=float, default=None, help="--condition-depth: the gate in metres (0.01)")
     ap.add_argument("--depth-jump-rel", type=float, default=None, help="--condition-depth: the gate's share of the reading, added to --depth-jump (0)")
+    ap.add_argument("--weight-views", action="store_true",
+                    help="weight every reading by its viewing angle: face-on counts --weight-levels times, grazing once, a pixel "
+                         "without a normal (silhouettes, rims of holes) not at all (default: every observation counts once)")
+    ap.add_argument("--weight-step", type=int, default=None, help="--weight-views: pixels to the neighbours the normal is taken from (1; up to 4)")
+    ap.add_argument("--weight-levels", type=int, default=None, help="--weight-views: the weight of a face-on reading (16; up to 255)")
+    ap.add_argument("--weight-cos-min", type=float, default=None, help="--weight-views: readings whose ray meets the surface at a smaller cosine get weight 0 (0.2)")
+    ap.add_argument("--weight-jump", type=float, default=None, help="--weight-views: the gate on a neighbour's reading in metres (0.01)")
+    ap.add_argument("--weight-jump-rel", type=float, default=None, help="--weight-views: the gate's share of the reading, added to --weight-jump (0)")
+    ap.add_argument("--carve-weight", type=int, default=None, help="--weight-views: the weight of 'the space in front of this pixel is empty' (1; 0 .. 255)")
     ap.add_argument("--report", default=None, help="write the report as JSON here")
     ap.add_argument("--out", required=True, help="the .ply to write, in model units")
     a = ap.parse_args(argv)
@@ -559,7 +609,12 @@ def main(argv=None):
                                            lambda name: "--" + name.replace("_", "-"), who="--condition-depth")
     except ValueError as e:
         ap.error(str(e))
-    closing = dict(close=a.close, support_plane=a.support_plane, support_lift=a.support_lift, condition=condition)
+    from . import depthweights
+    try:
+        weighting = depthweights.from_flags(a.weight_views, {k: getattr(a, k) for k in depthweights.FLAGS})
+    except ValueError as e:
+        ap.error(str(e))
+    closing = dict(close=a.close, support_plane=a.support_plane, support_lift=a.support_lift, condition=condition, weighting=weighting)
     from . import bop_data
     if a.join is not None:
         from . import track

@@ -9,9 +9,10 @@ nearest-neighbour search -- with the minimum-norm Gauss-Newton step of the ICP o
     python -m cppf2_amd.fuse --views <dir> --track --voxel 0.004 --out obj.ply
 
 The kernel is cppf_tsdf_track (include/cppf_hip_experimental.h; the definitions are stated in cppf2_amd/csrc/cppf_track.hip and
-restated in tests/track_ref.py).  Capture range: a frame whose surface lies farther than trunc from the volume's surface has no
+restated in tests/track_ref.py).  weighting= weights what is integrated, never the tracker's residuals.
+Capture range: a frame whose surface lies farther than trunc from the volume's surface has no
 gradient to follow; report["max_step"] beside report["trunc"] says how close a sequence came.  Not done: coarse-to-fine
-pyramids, loop closure, bundle adjustment, colour, weights.
+pyramids, loop closure, bundle adjustment, colour, weights on the tracker's residuals.
 """
 from __future__ import annotations
 
@@ -21,7 +22,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, depthfilter, fuse, hostargs, ops, render
+from . import _lib, depthfilter, depthweights, fuse, hostargs, ops, render
 from ._lib import CppfError
 
 MAX_FRAMES = 65535               # frames per cppf_tsdf_track call
@@ -87,23 +88,30 @@ def max_step(poses, corners):
     return float(np.linalg.norm(x[1:] - x[:-1], axis=2).max()) if len(P) > 1 else 0.0
 
 
-def _follow(volume, d, m, K, P, S, kw, pixel_offset, znear, track_fn, integrate_fn):
+def _weights_kw(w, weighting, a=None, b=None):
+    """integrate_fn's keyword arguments for the frames a..b of a sequence's weights w (none when weighting is off: the call is
+    what it always was)."""
+    return {} if w is None else dict(weights=w[a:b], carve_weight=weighting.carve_weight)
+
+
+def _follow(volume, d, m, K, P, S, kw, pixel_offset, znear, track_fn, integrate_fn, w=None, weighting=None):
     """The frame loop of onboard and join: frame 0 is integrated at P[0]; every later frame is tracked from the previous frame's
-    result (written to P[v], its stats to S[v]) and integrated at its own."""
+    result (written to P[v], its stats to S[v]) and integrated at its own.  w: the frames' weights (None: unweighted), handed to
+    integrate_fn frame by frame; the tracker does not see them."""
     dev = P.device
 
     def sl(x, a, b):
         return None if x is None else x[a:b]
-    integrate_fn(volume, d[:1], P[:1], K, sl(m, 0, 1), pixel_offset, znear)
+    integrate_fn(volume, d[:1], P[:1], K, sl(m, 0, 1), pixel_offset, znear, **_weights_kw(w, weighting, 0, 1))
     for v in range(1, d.shape[0]):
         p, s = track_fn(volume, d[v:v + 1], K, P[v - 1:v], sl(m, v, v + 1), **kw)
         P[v], S[v] = p.reshape(12).to(dev), s.reshape(4).to(dev)
-        integrate_fn(volume, d[v:v + 1], P[v:v + 1], K, sl(m, v, v + 1), pixel_offset, znear)
+        integrate_fn(volume, d[v:v + 1], P[v:v + 1], K, sl(m, v, v + 1), pixel_offset, znear, **_weights_kw(w, weighting, v, v + 1))
 
 
 def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, stride=1, sweeps=1, gate=None, pixel_offset=0.0,
             min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, dev=None, track_fn=None, integrate_fn=None,
-            condition=None):
+            condition=None, weighting=None, weights_fn=None):
     """A volume from a sequence of which only the first frame's pose is known: (volume, poses float64 [V,12] on the host, report).
     The volume is Volume.around the first frame at pose0, padded by extent (+ trunc + voxel) on every side: the first frame shows
     one side only, so extent defaults to the longest side of the first frame's box.  Frame 0 is integrated at pose0; every
@@ -114,14 +122,20 @@ def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, s
     of the first frame's box corners between consecutive estimates, metres, trunc, voxel, dims, sweeps, seconds).  lost =
     inlier_share < min_inlier_share; max_step above trunc means the next surface may have lain outside the band that has a
     gradient.  condition: a depthfilter.Settings record (None: the readings as they are): the frames are
-    conditioned before anything sees them, and the report gains `condition`.  track_fn / integrate_fn
-    stand for track / fuse.integrate (tests/test_track.py passes the NumPy restatements and dev="cpu")."""
+    conditioned before anything sees them, and the report gains `condition`.  weighting: a
+    depthweights.Settings record (None: every observation counts once): every frame gets weights by viewing angle (after
+    conditioning; DESIGN.md section 34) and is integrated with them, the same weights in the frame loop and in every sweep;
+    the tracker is not weighted; the report gains `weighting` and min_weight is in units of weight.  track_fn / integrate_fn /
+    weights_fn stand for track / fuse.integrate / depthweights.apply (tests/test_track.py passes the NumPy restatements and
+    dev="cpu")."""
+    weights_fn = depthweights.apply if weights_fn is None else weights_fn
     track_fn = track if track_fn is None else track_fn
     integrate_fn = fuse.integrate if integrate_fn is None else integrate_fn
     dev = ops._dev() if dev is None else torch.device(dev)
     t0 = time.perf_counter()
     d = hostargs.image_batch(depths, dev, "track.onboard", max_dim=fuse.MAX_IMAGE)
     d, conditioned = depthfilter.apply(d, condition, "track.onboard")
+    w, weighted = weights_fn(d, K, weighting, pixel_offset, "track.onboard")
     V = d.shape[0]
     m = None if masks is None else hostargs.mask_batch(masks, d, dev, "track.onboard", same_shape=True)
     pose0 = np.asarray(pose0, dtype=np.float64).reshape(1, 12)
@@ -140,18 +154,20 @@ def onboard(depths, masks, K, pose0, voxel, extent=None, trunc=None, iters=10, s
     P = torch.zeros((V, 12), dtype=torch.float64, device=dev)
     S = torch.zeros((V, 4), dtype=torch.float32, device=dev)
     P[0] = torch.from_numpy(pose0[0]).to(dev)
-    _follow(volume, d, m, K, P, S, kw, pixel_offset, znear, track_fn, integrate_fn)
+    _follow(volume, d, m, K, P, S, kw, pixel_offset, znear, track_fn, integrate_fn, w, weighting)
     for _ in range(sweeps if V > 1 else 0):
         p, s = track_fn(volume, d[1:], K, P[1:], sl(m, 1, V), **kw)
         P[1:], S[1:] = p.reshape(-1, 12).to(dev), s.reshape(-1, 4).to(dev)
         volume = fuse.Volume(volume.origin, voxel, volume.dims, trunc, dev)
-        integrate_fn(volume, d, P, K, m, pixel_offset, znear)
+        integrate_fn(volume, d, P, K, m, pixel_offset, znear, **_weights_kw(w, weighting))
     poses, stats = P.cpu().numpy(), S.cpu().numpy().astype(np.float64)
     frames = _frame_reports(stats, min_inlier_share, first_fixed=True)
     report = dict(frames=frames, lost=sum(f["lost"] for f in frames), max_step=max_step(poses, box_corners(box)), trunc=trunc,
                   voxel=voxel, dims=list(volume.dims), sweeps=sweeps, seconds=time.perf_counter() - t0)
     if conditioned is not None:
         report["condition"] = conditioned
+    if weighted is not None:
+        report["weighting"] = weighted
     return volume, poses, report
 
 
@@ -162,7 +178,7 @@ def _frame_reports(stats, min_inlier_share, first_fixed):
 
 def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad(15.0), reach=None, top=32, iters=10, stride=1,
          sweeps=0, gate=None, pixel_offset=0.0, min_weight=1, min_inlier_share=MIN_INLIER_SHARE, znear=render.ZNEAR, seed=0, dev=None,
-         track_fn=None, integrate_fn=None, score_fn=None, turned_over=False, condition=None):
+         track_fn=None, integrate_fn=None, score_fn=None, turned_over=False, condition=None, weighting=None, weights_fn=None):
     """A second sequence without any pose joined to a first one whose poses are known: the object turned
     over between the two, BOP's model-free static onboarding.  (volume, poses_second float64 [V,12] on the host, report).
     first = dict(depths, masks, K, poses): poses given, or onboard's result; second = dict(depths, masks, K); masks may be None.
@@ -175,10 +191,12 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
     symmetries, whose seen side the turned-over sequence fits as well as its own: the frame goes where it shows unseen space).
     report: dict(relocalise: relocalise's report, frames: per frame of second dict(inliers, rms, inlier_share, moved, lost) --
     frame 0's are the refinement's --, lost, max_step, trunc, voxel, dims, coarse_dims, sweeps, seconds).  condition: as
-    onboard's, on both sequences (the report's `condition` sums them).  track_fn,
-    integrate_fn, score_fn stand for track, fuse.integrate and relocalise.pose_scores (the tests pass the NumPy restatements
-    and dev="cpu")."""
+    onboard's, on both sequences (the report's `condition` sums them).  weighting: as onboard's, on both sequences and in
+    every volume a frame is integrated into (fine, coarse, sweeps); the pose search and the tracker are not weighted.  track_fn,
+    integrate_fn, score_fn, weights_fn stand for track, fuse.integrate, relocalise.pose_scores and depthweights.apply (the
+    tests pass the NumPy restatements and dev="cpu")."""
     from . import relocalise as RL
+    weights_fn = depthweights.apply if weights_fn is None else weights_fn
     track_fn = track if track_fn is None else track_fn
     integrate_fn = fuse.integrate if integrate_fn is None else integrate_fn
     dev = ops._dev() if dev is None else torch.device(dev)
@@ -187,6 +205,8 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
     db = hostargs.image_batch(second["depths"], dev, "track.join", max_dim=fuse.MAX_IMAGE)
     da, cond_a = depthfilter.apply(da, condition, "track.join")
     db, cond_b = depthfilter.apply(db, condition, "track.join")
+    wa, weighted_a = weights_fn(da, first["K"], weighting, pixel_offset, "track.join")
+    wb, weighted_b = weights_fn(db, second["K"], weighting, pixel_offset, "track.join")
     ma = None if first.get("masks") is None else hostargs.mask_batch(first["masks"], da, dev, "track.join", same_shape=True)
     mb = None if second.get("masks") is None else hostargs.mask_batch(second["masks"], db, dev, "track.join", same_shape=True)
     Ka, Kb = first["K"], second["K"]
@@ -201,8 +221,8 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
     box = fuse.Volume.bounds(da, ma, Pa, Ka, pixel_offset, dev)
     volume = fuse.Volume.around(da, ma, Pa, Ka, voxel, None, trunc, pixel_offset, dev)
     rough = fuse.Volume.around(da, ma, Pa, Ka, coarse * voxel, None, fuse.TRUNC_VOXELS * coarse * voxel, pixel_offset, dev)
-    integrate_fn(volume, da, Pa, Ka, ma, pixel_offset, znear)
-    integrate_fn(rough, da, Pa, Ka, ma, pixel_offset, znear)
+    integrate_fn(volume, da, Pa, Ka, ma, pixel_offset, znear, **_weights_kw(wa, weighting))
+    integrate_fn(rough, da, Pa, Ka, ma, pixel_offset, znear, **_weights_kw(wa, weighting))
     pose0, found = RL.relocalise([rough, volume], db[0], Kb, None if mb is None else mb[0], points, step, reach, top, iters, stride,
                                  pixel_offset, seed, min_weight, score_fn, track_fn, turned_over)
     V = db.shape[0]
@@ -211,13 +231,13 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
     S = torch.zeros((V, 4), dtype=torch.float32, device=dev)
     P[0] = torch.from_numpy(pose0).to(dev)
     S[0] = torch.tensor(found["stats"], dtype=torch.float32, device=dev)
-    _follow(volume, db, mb, Kb, P, S, kw, pixel_offset, znear, track_fn, integrate_fn)
+    _follow(volume, db, mb, Kb, P, S, kw, pixel_offset, znear, track_fn, integrate_fn, wb, weighting)
     for _ in range(sweeps):
         p, s = track_fn(volume, db, Kb, P, mb, **kw)
         P, S = p.reshape(-1, 12).to(dev), s.reshape(-1, 4).to(dev)
         volume = fuse.Volume(volume.origin, voxel, volume.dims, trunc, dev)
-        integrate_fn(volume, da, Pa, Ka, ma, pixel_offset, znear)
-        integrate_fn(volume, db, P, Kb, mb, pixel_offset, znear)
+        integrate_fn(volume, da, Pa, Ka, ma, pixel_offset, znear, **_weights_kw(wa, weighting))
+        integrate_fn(volume, db, P, Kb, mb, pixel_offset, znear, **_weights_kw(wb, weighting))
     poses = P.cpu().numpy()
     frames = _frame_reports(S.cpu().numpy().astype(np.float64), min_inlier_share, first_fixed=False)
     report = dict(relocalise=found, frames=frames, lost=sum(f["lost"] for f in frames), max_step=max_step(poses, box_corners(box)),
@@ -225,6 +245,8 @@ def join(first, second, voxel, coarse=2, trunc=None, points=256, step=np.deg2rad
                   seconds=time.perf_counter() - t0)
     if condition is not None:
         report["condition"] = depthfilter.merged([cond_a, cond_b])
+    if weighting is not None:
+        report["weighting"] = depthweights.merged([weighted_a, weighted_b])
     return volume, poses, report
 
 
@@ -243,11 +265,11 @@ def pose_differences(poses, recorded):
 
 def onboard_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
                   simplify_cell=None, iters=10, stride=1, sweeps=1, extent=None, close=False, support_plane=None, support_lift=None,
-                  condition=None):
+                  condition=None, weighting=None):
     """fuse.fuse_scene for a folder of which only the first image's pose is used: (mesh in metres, report); the report gains
     `track` (onboard's report, and per frame `recorded`: the difference to the pose the folder has for it, where it has one --
     recorded, not judged).  close, support_plane, support_lift: as fuse.fuse_scene's (the first image's pose, the one that is
-    known, takes an "auto" plane into the object's frame).  condition: as fuse.fuse_scene's."""
+    known, takes an "auto" plane into the object's frame).  condition and weighting: as fuse.fuse_scene's."""
     batches, conditioned = fuse.condition_batches(fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=True), condition)
     if len(batches) != 1:
         raise fuse.ViewsError("%s: --track takes images of one size and camera matrix, not %d kinds" % (views_dir, len(batches)))
@@ -255,24 +277,25 @@ def onboard_scene(views_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_m
     support_plane = fuse._scene_plane(support_plane, support_lift, voxel, pixel_offset, batches, views_dir)
     t0 = time.perf_counter()
     volume, poses, rep = onboard(b["depths"], b["masks"], b["K"], b["poses"][0], voxel, extent, trunc, iters, stride, sweeps,
-                                 pixel_offset=pixel_offset, min_weight=min_weight)
+                                 pixel_offset=pixel_offset, min_weight=min_weight, weighting=weighting)
     t1 = fuse._sync(volume.device)
     mesh, closed = fuse._surface(volume, min_weight, close, support_plane, support_lift)
     t2 = fuse._sync(volume.device)
     for f, im, diff in zip(rep["frames"], b["im_ids"], pose_differences(poses, b["poses"])):
         f["im_id"], f["recorded"] = int(im), diff
     mesh, report = fuse._conditioned(fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed), conditioned)
+    mesh, report = fuse._weighted((mesh, report), rep.get("weighting"))
     return mesh, dict(report, track=rep)
 
 
 def join_scene(views_dir, join_dir, voxel, obj_id=None, trunc=None, min_weight=1, use_masks=True, pixel_offset=0.0, mesh_scale=0.001,
                simplify_cell=None, iters=10, stride=1, track_sweeps=None, extent=None, step=np.deg2rad(15.0), top=32, coarse=2,
-               points=256, close=False, support_plane=None, support_lift=None, turned_over=False, condition=None):
+               points=256, close=False, support_plane=None, support_lift=None, turned_over=False, condition=None, weighting=None):
     """fuse.fuse_scene for two folders of one object, the second (join_dir: the object turned over) read without its poses:
     (mesh in metres, report); the report gains `join` (join's report, and per frame of the second folder `recorded`, as
     onboard_scene's).  track_sweeps not None (--track): the first folder's poses come from onboard (first pose only, that many
     sweeps) and the report gains `track` too.  close, support_plane, support_lift: as fuse.fuse_scene's, on the first folder.
-    condition: as fuse.fuse_scene's, on both folders."""
+    condition and weighting: as fuse.fuse_scene's, on both folders."""
     tracked = track_sweeps is not None
     batches, cond_a = fuse.condition_batches(fuse.read_views(views_dir, obj_id, mesh_scale, use_masks, first_pose_only=tracked), condition)
     others, cond_b = fuse.condition_batches(fuse.read_views(join_dir, obj_id, mesh_scale, use_masks, no_poses=True), condition)
@@ -284,13 +307,13 @@ def join_scene(views_dir, join_dir, voxel, obj_id=None, trunc=None, min_weight=1
     extra, poses_a = {}, a["poses"]
     if tracked:
         _, poses_a, rep_a = onboard(a["depths"], a["masks"], a["K"], a["poses"][0], voxel, extent, trunc, iters, stride, track_sweeps,
-                                    pixel_offset=pixel_offset, min_weight=min_weight)
+                                    pixel_offset=pixel_offset, min_weight=min_weight, weighting=weighting)
         for f, im, diff in zip(rep_a["frames"], a["im_ids"], pose_differences(poses_a, a["poses"])):
             f["im_id"], f["recorded"] = int(im), diff
         extra["track"] = rep_a
     volume, poses_b, rep = join(dict(depths=a["depths"], masks=a["masks"], K=a["K"], poses=poses_a),
                                 dict(depths=b["depths"], masks=b["masks"], K=b["K"]), voxel, coarse, trunc, points, step, None, top, iters,
-                                stride, pixel_offset=pixel_offset, min_weight=min_weight, turned_over=turned_over)
+                                stride, pixel_offset=pixel_offset, min_weight=min_weight, turned_over=turned_over, weighting=weighting)
     t1 = fuse._sync(volume.device)
     mesh, closed = fuse._surface(volume, min_weight, close, support_plane, support_lift)
     t2 = fuse._sync(volume.device)
@@ -298,4 +321,5 @@ def join_scene(views_dir, join_dir, voxel, obj_id=None, trunc=None, min_weight=1
         f["im_id"], f["recorded"] = int(im), diff
     conditioned = None if condition is None else depthfilter.merged([cond_a, cond_b])
     mesh, report = fuse._conditioned(fuse._finish(volume, mesh, (0.0, t1 - t0, t2 - t1), simplify_cell, closed), conditioned)
+    mesh, report = fuse._weighted((mesh, report), rep.get("weighting"))
     return mesh, dict(report, join=rep, **extra)

@@ -374,6 +374,42 @@ int cppf_tsdf_pose_scores(const float* acc, const int32_t* wsum, const double* h
 int cppf_depth_condition(const float* depth, int I, int H, int W, int r1, int min_support, int r2, float jump, float jump_rel,
                          float* out, int32_t* counts, void* stream);
 
+/* ---- depth views fused with weights by viewing angle: small integer weights per pixel (the reference has no such step) ----
+ * cppf_depth_weights: depth float32 [I,H,W] (metres) -> weights uint8 [I,H,W] and counts int32 [I,3], all on the device.  h_K =
+ * (fx, fy, cx, cy): double[4] on the HOST, cast to float32 like cppf_tsdf_integrate's; pixel (r, c) lies on the ray through
+ * (c + pixel_offset, r + pixel_offset).  valid(q), tol(z) = jump + (jump_rel * z) and near(q, z) are cppf_depth_condition's, z
+ * the centre's reading.  P(c, r, d) = ((((float)c + pixel_offset) - cx) / fx * d, (((float)r + pixel_offset) - cy) / fy * d, d).
+ * A valid pixel p = P(c, r, z) gets weight 0 unless the four positions (c -+ step, r), (c, r -+ step) lie inside the image and
+ * hold valid readings near z.  Otherwise tx = P(right) - P(left), ty = P(down) - P(up), n = tx x ty (each component a*b - c*d),
+ * a = (n.x*p.x + n.y*p.y) + n.z*p.z, nn = n.n and pp = p.p summed the same way, den = nn * pp; weight 0 unless 0 < den < inf;
+ * c = sqrtf((a * a) / den), the cosine between the pixel's ray and the surface normal; weight 0 unless c >= cos_min; otherwise
+ * t = floorf(c * (float)levels + 0.5f) clamped to [1, levels].  An invalid pixel gets 0.  counts[i] = (valid readings of image
+ * i, valid readings with weight 0, readings with weight `levels`).  Every float32 operation is rounded where it is written
+ * (no fused multiply-add), divide and square root correctly rounded; the exact order is stated in
+ * cppf2_amd/csrc/cppf_depthweights.hip and restated in tests/depth_weights_ref.py.  The counts are cleared, then one launch for
+ * all I images; no workspace, no host synchronisation, no atomics but the integer counts.  I = 0: valid, nothing is written.
+ * CPPF_EINVAL, before any device work, for: I < 0; H or W outside 1..16384; step outside 1..4; levels outside 1..255; cos_min
+ * outside [0, 1) or NaN; jump or jump_rel negative or not finite; a pixel_offset that is not finite; h_K NULL; and, when I > 0,
+ * a NULL depth, weights or counts, or an output that overlaps depth.
+ *
+ * cppf_tsdf_integrate_weighted: cppf_tsdf_integrate (above) with a weight per observation.  weights uint8 [V,H,W] on the device
+ * (required when V > 0), carve_weight in 0..255.  Per node and view everything up to the observation is cppf_tsdf_integrate's;
+ * then an observation q = sdf / trunc < 1 inside the mask (or without masks) has w = weights[v,row,col], and the constant
+ * observation 1 (q not < 1 inside the mask; free space outside the mask) has w = carve_weight: a silhouette pixel has no normal
+ * but still says that the space in front of it is empty.  w = 0 skips; otherwise acc = acc + (float)w * obs, wsum += w.  The
+ * volume keeps its layout: acc is the weighted sum, wsum the sum of the weights, acc / (float)wsum the weighted mean, and
+ * min_weight of cppf_tsdf_extract, cppf_tsdf_track, cppf_tsdf_close and cppf_tsdf_pose_scores is then a threshold in units of
+ * weight.  The views are summed in order inside the kernel: one call gives the bytes of any split into consecutive calls; all
+ * weights 1 and carve_weight 1 give cppf_tsdf_integrate's bytes.  wsum is int32 and one call adds at most 65 536 x 255 to a
+ * node: the caller owns the total over its calls.  CPPF_EINVAL as cppf_tsdf_integrate, and for carve_weight outside 0..255 and,
+ * when V > 0, a NULL weights. */
+int cppf_depth_weights(const float* depth, int I, int H, int W, const double* h_K, float pixel_offset, int step, float jump,
+                       float jump_rel, int levels, float cos_min, uint8_t* weights, int32_t* counts, void* stream);
+int cppf_tsdf_integrate_weighted(int V, const float* depth, const uint8_t* masks, const float* poses, const uint8_t* weights,
+                                 int carve_weight, int H, int W, const double* h_K, float pixel_offset, const double* h_origin,
+                                 float voxel, int nx, int ny, int nz, float trunc, float znear, float* acc, int32_t* wsum,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
