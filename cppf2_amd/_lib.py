@@ -171,6 +171,7 @@ EXPERIMENTAL = {
     "cppf_depth_condition": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p]),
     "cppf_depth_weights": (_i, [_p, _i, _i, _i, _p, _f, _i, _f, _f, _i, _f, _p, _p, _p]),
     "cppf_tsdf_integrate_weighted": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _p, _f, _p, _f, _i, _i, _i, _f, _f, _p, _p, _p]),
+    "cppf_concave_edges": (_i, [_i, _i, _i, _p, _p, _p, _i, _f, _f, _f, _p, _p, _p]),
 }
 
 SIGNATURES = dict(STABLE, **EXPERIMENTAL)

@@ -82,6 +82,12 @@ What the image cannot provide is stated, not faked:
     mask would have; proposals wider than 1000 cells or with too few points are skipped and counted.  The report gains `plane`,
     `proposals` (pixels, bbox, pose; the verification score with --hypotheses > 1) and, with --hypotheses > 1, `best`: the
     proposal with the highest score, ties to the larger one.  --gt_pose scores `best` when it exists, else every proposal.
+    `--propose_concave [--concave_step=3 --concave_angle=15 --concave_floor=0.002 --concave_reach=<step x 0.01>]` removes the
+    locally concave pixels from what is labelled (cppf_concave_edges): touching and stacked objects
+    part, and the contact line with the table is cut where it is.  `--propose_no_plane` (needs --propose_concave) fits no
+    support plane -- a shelf, a bin, a tray: every valid pixel is labelled, the table is a proposal of its own, which goes
+    through the same too-wide and too-few-points skips and otherwise scores low in the verification, and the report's plane
+    is four zeros; --support_check and the --plane_* flags need the plane and are refused beside it.  The report gains `concave` (the settings; valid, edge and kept pixels).
   * `--data=depth --propose_masks --explain_scene [--explain_min_score=0.5 --explain_min_gain=200 --explain_viol_weight=1
     --explain_max=16]` (with --hypotheses > 1 and a mesh) decides per image, not per mask (cppf2_amd.scene, cppf_scene_explain,
     DESIGN.md section 22; not in the reference): the verified pose of every proposal with a verification score of at least
@@ -648,10 +654,16 @@ _PROPOSE_FLAGS = ("plane_tau", "plane_hypotheses", "plane_min_height", "min_segm
 
 def _propose_flags(f):
     """segment.propose's keyword arguments from the --propose_masks flags, or None when it is off."""
+    from cppf2_amd import segment
     given = [k_ for k_ in _PROPOSE_FLAGS if getattr(f, k_) is not None]
+    concave = segment.concave_from_flags(bool(f.propose_concave), {k_: getattr(f, k_) for k_ in segment.CONCAVE_FLAGS})
+    if f.propose_no_plane and concave is None:
+        raise ValueError("--propose_no_plane leaves the concave edges to part the objects from the table: it needs --propose_concave")
     if not f.propose_masks:
         if given:
             raise ValueError("--%s sets how masks are proposed: it needs --propose_masks" % given[0])
+        if concave is not None:
+            raise ValueError("--propose_concave sets how masks are proposed: it needs --propose_masks")
         return None
     if f.data != "depth":
         raise ValueError("--propose_masks proposes the masks of one depth image: it needs --data=depth "
@@ -660,7 +672,13 @@ def _propose_flags(f):
         raise ValueError("--propose_masks replaces --mask: give one of them")
     if bool(f.clean_masks) or bool(f.clean_mask):
         raise ValueError("--clean_mask cleans a given mask: proposals are depth-connected already")
-    from cppf2_amd import masks, segment
+    if f.propose_no_plane:
+        planar = [k_ for k_ in _PROPOSE_FLAGS if k_.startswith("plane_") and getattr(f, k_) is not None]
+        if planar:
+            raise ValueError("--%s sets how the support plane is fitted and dropped: not with --propose_no_plane" % planar[0])
+        if f.support_check:
+            raise ValueError("--support_check tests poses against the plane the proposals were cut with: not with --propose_no_plane")
+    from cppf2_amd import masks
     p = dict(num_hyp=segment.NUM_HYP if f.plane_hypotheses is None else int(f.plane_hypotheses),
              tau=segment.TAU if f.plane_tau is None else float(f.plane_tau),
              min_height=segment.MIN_HEIGHT if f.plane_min_height is None else float(f.plane_min_height),
@@ -677,6 +695,8 @@ def _propose_flags(f):
         raise ValueError("--min_segment_pixels must be >= 0, not %d" % p["min_pixels"])
     if not 1 <= p["max_segments"] <= segment.SEGMENTS_LIMIT:
         raise ValueError("--max_proposals must be in 1 .. %d, not %d" % (segment.SEGMENTS_LIMIT, p["max_segments"]))
+    if concave is not None:                        # without the flag the dict, and with it the report, keeps its keys
+        p.update(concave=concave, plane=not f.propose_no_plane)
     return p
 
 
@@ -1129,6 +1149,9 @@ def _depth_instances(ctx, masks, objects, categories, proposed=None, gt=None, ex
                       proposals=proposals, proposed=len(props), skipped=skipped,
                       mask_proposals=dict(propose, seed=int(vote.seed), components=plane["components"],
                                           large_components=plane["large_components"]))
+        if "concave" in plane:                         # --propose_concave: the settings and the valid, edge and kept pixels
+            report["concave"] = plane["concave"]
+            report["mask_proposals"]["concave"] = dict(propose["concave"]._asdict())
         if best is not None:
             report["best"] = best
     if multi:
@@ -1229,7 +1252,8 @@ def main(angle_tol=1., imp_wt_margin=0.01, backproj_ratio=.1, num_pairs=50000, n
          explain_max=None, models_dir=None, obj_ids=None, explain_hypotheses=False, explain_min_support=None,
          support_check=False, support_tau=None, support_max_share=None, explain_solid=False, solid_tau=None, solid_max_share=None,
          detect_symmetries=False, sym_tol=None, iou_device=False, condition_depth=False, flying_radius=None, flying_support=None,
-         smooth_radius=None, depth_jump=None, depth_jump_rel=None):
+         smooth_radius=None, depth_jump=None, depth_jump_rel=None, propose_concave=False, concave_step=None, concave_angle=None,
+         concave_floor=None, concave_reach=None, propose_no_plane=False):
     f = _checked_flags(**locals())
     vote = Vote(*(getattr(f, k_) for k_ in Vote._fields))
     dev = ops._dev()

@@ -18,7 +18,9 @@
  *   - depth frames tracked against the fused volume, for sequences with one known pose (cppf2_amd/track.py, DESIGN.md
  *     section 30): opt-in and new;
  *   - a depth frame's pose searched against the fused volume with no starting pose, which joins a second sequence of the object
- *     turned over (cppf2_amd/relocalise.py): opt-in and new.
+ *     turned over (cppf2_amd/relocalise.py): opt-in and new;
+ *   - mask proposals cut at concave edges, with or without a support plane (cppf2_amd/segment.py): opt-in
+ *     and new.
  */
 #ifndef CPPF_HIP_EXPERIMENTAL_H_
 #define CPPF_HIP_EXPERIMENTAL_H_
@@ -409,6 +411,27 @@ int cppf_tsdf_integrate_weighted(int V, const float* depth, const uint8_t* masks
                                  int carve_weight, int H, int W, const double* h_K, float pixel_offset, const double* h_origin,
                                  float voxel, int nx, int ny, int nz, float trunc, float znear, float* acc, int32_t* wsum,
                                  void* stream);
+
+/* ---- mask proposals without a support plane: segments cut at concave edges (the reference has no such step) ----
+ * cppf_concave_edges: depths float32 [I,H,W] (metres), Kmat float32 [I,4] = (fx, fy, cx, cy), fg uint8 [I,H,W] or NULL -> keep
+ * uint8 [I,H,W] and counts int32 [I,3], all on the device.  valid and the point of a pixel are cppf_plane_fit's: depth > 0 &&
+ * depth < +inf; z = depth, x = ((float)c - cx) * z / fx, y = ((float)r - cy) * z / fy.  The profile of a pixel B = (r, c) along
+ * e = (0, 1) or (1, 0) uses A = the pixel at -step e and C = the pixel at +step e and gives a verdict only when both lie inside
+ * the image, all three are valid, fabsf(zA - zB) <= reach and fabsf(zC - zB) <= reach.  With u = B - A, t = C - A,
+ * tt = (t.x*t.x + t.y*t.y) + t.z*t.z, ut = (u.x*t.x + u.y*t.y) + u.z*t.z, o = u * tt - t * ut (per component: two rounded
+ * products, one difference; tt times B's offset from the chord AC), ob = (o.x*B.x + o.y*B.y) + o.z*B.z, oo = o.o summed the same
+ * way and t3 = (tt * tt) * tt, the profile is concave iff ob > 0 (B lies behind the chord) && 4.0f * oo > k2 * t3 (the turn
+ * between the two sides exceeds the angle of k2 = (float)tan(angle / 2)^2) && oo > floor2 * (tt * tt) (the offset exceeds the
+ * distance of floor2 = (float)floor^2).  A pixel is an edge when it is valid and either profile is concave; keep = 255 where
+ * the pixel is valid, is no edge and (fg == NULL or fg != 0), else 0; counts[i] = (valid pixels, edge pixels, kept pixels) of
+ * image i.  The profiles read the whole depth image, never only fg.  Every float32 operation is rounded where it is written (no
+ * fused multiply-add), the divide correctly rounded; tests/concave_ref.py restates the order.  The counts are cleared, then one
+ * launch for all I images; no workspace, no host synchronisation, no atomics but the integer counts; an image's outputs do not
+ * depend on its place in the batch.  keep may be fg itself.  I = 0: valid, nothing is written.
+ * CPPF_EINVAL, before any device work, for: I < 0; H or W outside 1..8192; step outside 1..8; k2, floor2 or reach negative or
+ * not finite; and, when I > 0, a NULL depths, Kmat, keep or counts, or a keep that overlaps depths. */
+int cppf_concave_edges(int I, int H, int W, const float* depths, const float* Kmat, const uint8_t* fg, int step, float k2,
+                       float floor2, float reach, uint8_t* keep, int32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }
